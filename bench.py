@@ -12,15 +12,20 @@ With N > 1 the I slabs are sharded over the ranks in contiguous ranges balanced 
 total problem -> "strong" scaling, as BASELINE.json's metric "@1/2/4/8 GPU" states); per step there is one RCCL
 all-reduce of the fp64 C-mode normal equations [G | R] (PARAFAC2 stacks add one small all-reduce per inner iteration);
 the fp64 diagnostic sums of all steps are all-reduced once at the end of each timed region (no stopping rule is active
-in this fixed-iteration workload).  After the run the replicated factor C is checked to be BIT-identical on all ranks.
+in this fixed-iteration workload).  With --full the replicated factor C is checked to be BIT-identical on all ranks.
 
-Timing: W warm-up steps, then R (default 5) timed regions of exactly K steps each, every region bracketed by a barrier
-+ torch.cuda.synchronize(); per region the MAX over ranks; the reported `ms_per_step * steps` is the MEDIAN region
-(`region_ms` lists all of them) - one region of 20 steps lasts ~4 ms and a single sample of that swings by 10 %.
+Timing: an un-timed settling phase on a throw-away trajectory (clock ramp of a fresh device), then from the seeded start
+W warm-up steps and R timed regions of exactly K steps each, every region bracketed by a barrier + torch.cuda.synchronize();
+per region the MAX over ranks; the reported `ms_per_step * steps` is the MEDIAN region (`region_ms` lists all of them).
+A plain run times ONE region (R = 1): --steps is the number of timed steps.  --dump-outputs DIR writes what the last timed
+step computed (A, B, C, its diagnostics vector); with the same arguments every run starts from the same seeded state.
 
-Rank 0 prints ONE JSON line (contract in the task statement) with two extra objects:
+Rank 0 prints ONE JSON line (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).  --full also measures what
+the headline figure does not need: R = 25 regions (one region of 20 steps lasts ~4 ms and a single sample of that swings
+by 10 %), and
   roofline      dominant kernel's algorithmic bytes / HIP-event time (events recorded inside the library on the
                 kernel's own stream) against the 8 TB/s HBM peak
+  api           the public cmf_aoadmm call on the same data
   cpu_baseline  the NumPy oracle (oracle/aoadmm_oracle.py, a restatement of the reference pinned by goldens)
                 timed on this box's host cores on a bounded sample of the same workload
 """
@@ -88,6 +93,23 @@ def leg(name, t_start):
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8 TB/s spec
 MFMA_F32_PEAK_TFLOPS = 157.3  # MI355X_MICROARCH.md: dense fp32 matrix rate (v_mfma_f32_16x16x4_f32: 256 flop/cycle/CU)
+DUMP_BYTES = 60 << 20  # --dump-outputs writes at most this much array data (64 MB in all with room for the .npy headers)
+SETTLE_PROBE_STEPS = 50  # settling probes are at most this long: the settling time does not grow with --steps
+
+
+def dump_outputs(path, arrays):
+    """Write `arrays` (name -> numpy array) as path/<name>.npy, smallest first, each within its share of what is left of
+    DUMP_BYTES: a larger array is replaced by a fixed sample of its rows (RandomState(0), kept in row order)."""
+    os.makedirs(path, exist_ok=True)
+    left = DUMP_BYTES
+    items = sorted(arrays.items(), key=lambda kv: kv[1].nbytes)
+    for i, (name, a) in enumerate(items):
+        share = left // (len(items) - i)
+        if a.nbytes > share:
+            rows = np.random.RandomState(0).choice(len(a), share // (a.nbytes // len(a)), replace=False)
+            a = a[np.sort(rows)]
+        np.save(os.path.join(path, name + ".npy"), a)
+        left -= a.nbytes
 
 
 def make_shard(cfg, rank, world, device, seed=0):
@@ -336,10 +358,20 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
-    ap.add_argument("--regions", type=int, default=25, help="timed regions of --steps steps each; the median is reported")
+    ap.add_argument("--regions", type=int, default=None,
+                    help="timed regions of --steps steps each; the median is reported (default: 1; with --full 25)")
     ap.add_argument("--settle-ms", type=float, default=100.0,
-                    help="un-timed settling after --warmup: keep stepping for at least this long AND until two consecutive "
-                         "probe regions of --steps steps agree within 2 %% (clock ramp of a fresh device); 0 disables")
+                    help="un-timed settling before --warmup, on a trajectory that is then discarded: keep stepping for at least "
+                         f"this long AND until two consecutive probe regions of --steps steps (at most {SETTLE_PROBE_STEPS}) agree "
+                         "within 2 %% (clock ramp of a fresh device); 0 disables")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: 25 timed regions (unless --regions says "
+                         "otherwise), the roofline and per-kernel times (HIP events inside the timed regions), the streaming-read "
+                         "bandwidth, the `api` block, the CPU baseline and, at N > 1, the bit-identity check of the replicated C")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed - the factors A, B, C (rows of every rank) "
+                         "and its fp64 diagnostics vector - as DIR/<name>.npy, at most 64 MB in all (a factor too large for "
+                         "its share is replaced by a fixed sample of its rows)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-api", action="store_true", help="skip the `api` block (timing of the public cmf_aoadmm call)")
     ap.add_argument("--cpu-budget", type=float, default=15.0)
@@ -348,6 +380,10 @@ def main():
                          "block, the CPU baseline) are shortened or skipped - and say so in the JSON line - when the mandatory "
                          "legs (imports, device, data, timed regions) have used the budget up, e.g. on a box with cold caches")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.regions is None:
+        args.regions = 25 if args.full else 1
 
     # RCCL shares device buffers between the ranks of a node through dmabuf IPC; the legacy IPC mode is not supported by the
     # host driver of this pool (hipIpcGetMemHandle: invalid argument) - keep the setting the image exports
@@ -402,8 +438,9 @@ def main():
     from matcouply_amd._engine import DIAG_LEN
 
     n_regions = max(1, args.regions)
-    ring = torch.zeros((max(1, n_regions * args.steps), DIAG_LEN), dtype=torch.float64, device=device)
-    scratch = torch.zeros((max(1, args.warmup, args.steps), DIAG_LEN), dtype=torch.float64, device=device)  # un-timed steps
+    ring = torch.zeros((n_regions * args.steps, DIAG_LEN), dtype=torch.float64, device=device)
+    probe_steps = min(args.steps, SETTLE_PROBE_STEPS)
+    scratch = torch.zeros((max(1, args.warmup, probe_steps), DIAG_LEN), dtype=torch.float64, device=device)  # un-timed steps
     n_coll = [0]  # collectives issued by this rank (counted on the host)
 
     # collectives of the timed loop: RCCL called directly on the engine's stream (matcouply_amd/_rccl.py; self-tested
@@ -461,22 +498,22 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    for it in range(args.warmup):
-        step(scratch[it])
-    eng.flush_diagnostics()
-    sync()
-    t_leg = leg("warmup", t_leg)
-    # Settling (un-timed, on top of --warmup): a fresh device ramps its clocks over the first ~100 ms of work - with 5
+    # Settling (un-timed, before --warmup): a fresh device ramps its clocks over the first ~100 ms of work - with 5
     # warm-up steps (0.8 ms at config 3) the first timed regions of round 2 fell monotonically by 10 %.  Keep stepping in
-    # probe regions of --steps steps until >= --settle-ms have passed AND two consecutive probes agree within 2 %
-    # (bounded by 3 s).  Every rank takes the same decision (the probe time is the MAX over ranks).
+    # probe regions of --steps steps (at most SETTLE_PROBE_STEPS) until >= --settle-ms have passed AND two consecutive probes
+    # agree within 2 % (bounded by 3 s).  Every rank takes the same decision (the probe time is the MAX over ranks).  How many
+    # probes that takes depends on the clock, so the state they leave is discarded: the warm-up and timed steps start from the
+    # seeded state again (the engine keeps nothing between steps but these tensors and the by-products invalidate() drops).
     settle = dict(ms=0.0, probes=0, settled=None)
-    if args.settle_ms > 0 and args.steps > 0:
+    if args.settle_ms > 0:
+        state = [eng.A, eng.B, eng.C] + [t for regs in eng.regs for reg in regs for t in (reg.aux, reg.dual, reg.aux2)
+                                         if t is not None]
+        seeded = [t.clone() for t in state]
         prev, total = None, 0.0
         for probe in range(1000000):
             sync()
             t0 = time.perf_counter()
-            for it in range(args.steps):
+            for it in range(probe_steps):
                 step(scratch[it])
             eng.flush_diagnostics()
             sync()
@@ -491,12 +528,23 @@ def main():
             settle = dict(ms=round(1e3 * total, 2), probes=probe + 1, settled=bool(agree))
             if (1e3 * total >= args.settle_ms and agree) or total > 3.0:
                 break
-    # HIP events inside the library around every `stride`-th launch of the timed region: an event pair opens ~5 us
+        for dst, src in zip(state, seeded):
+            dst.copy_(src)
+        eng.invalidate()
+        del seeded
+        sync()
+    t_leg = leg("settling", t_leg)
+    for it in range(args.warmup):
+        step(scratch[it])
+    eng.flush_diagnostics()
+    sync()
+    t_leg = leg("warmup", t_leg)
+    # --full: HIP events inside the library around every `stride`-th launch of the timed region: an event pair opens ~5 us
     # dispatch gaps before and after the kernel (11 us per step when every launch is bracketed - measured), so the
     # timed loop samples ~10 launches instead of taxing all of them
-    t_leg = leg("settling", t_leg)
     prof_stride = max(1, (n_regions * args.steps) // 10)
-    eng.profile_enable(128, stride=prof_stride)  # at most ~6 launches per step and site: <= ~60 timed launches each
+    if args.full:
+        eng.profile_enable(128, stride=prof_stride)  # at most ~6 launches per step and site: <= ~60 timed launches each
     region_s = []
     coll_before = n_coll[0]
     for reg in range(n_regions):
@@ -517,20 +565,22 @@ def main():
     elapsed = float(np.median(region_s))
     t_leg = leg("timed_regions", t_leg)
     coll_per_step = (n_coll[0] - coll_before - n_regions) / max(1, n_regions * args.steps)  # without the ring reductions
+    final = ring[n_regions * args.steps - 1].cpu().numpy()  # the fp64 diagnostics vector of the last timed step
+    if args.dump_outputs:
+        # what the timed path hands its caller after its last step: the factors - A and B are gathered from every rank in
+        # rank order (the global row order) - and that step's diagnostics vector (summed over the ranks at N > 1)
+        def rows_of_all_ranks(t):
+            if world == 1:
+                return t.cpu().numpy()
+            parts = [None] * world if rank == 0 else None
+            dist.gather_object(t.cpu().numpy(), parts, dst=0)
+            return np.concatenate(parts) if rank == 0 else None
 
-    # the replicated factor must be bit-identical on every rank (a divergent C would silently corrupt the fit)
-    c_identical = None
-    if world > 1:
-        bits = eng.C.view(torch.int32).to(torch.int64)
-        chk = torch.stack([bits.sum(), (bits * torch.arange(1, bits.numel() + 1, device=device).view_as(bits)).sum()])
-        lo_, hi_ = chk.clone(), chk.clone()
-        dist.all_reduce(lo_, op=dist.ReduceOp.MIN)
-        dist.all_reduce(hi_, op=dist.ReduceOp.MAX)
-        c_identical = bool(torch.equal(lo_, hi_))
-
-    # live roofline (HIP events inside the library, same stream as the kernels): EVERY hot launch site of the step is
-    # timed; the block names the site that takes the largest share of the step (launches per step x average duration)
-    from matcouply_amd import _engine as E
+        A_all, B_all = rows_of_all_ranks(eng.A), rows_of_all_ranks(eng.B)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"A": A_all, "B": B_all, "C": eng.C.cpu().numpy(), "diagnostics": final})
+        del A_all, B_all
+        t_leg = leg("dump_outputs", t_leg)
 
     N_loc, K, r = X.shape[0], cfg["K"], cfg["r"]
     N_tot = N_loc
@@ -538,155 +588,179 @@ def main():
         t = torch.tensor([N_loc], dtype=torch.float64, device=device)
         dist.all_reduce(t)
         N_tot = int(t.item())
-    S_X, S_B = 4.0 * N_loc * K, 4.0 * N_loc * r
-    n_B, n_C = len(cfg["regs"][1]), len(cfg["regs"][2])
-    NBk = (r + 15) // 16
-    NBk = 4 if NBk == 3 else NBk
-    xc_fused = "GRAM=" in eng.kernel_variant(E.PROF_XC) and "GRAM=0" not in eng.kernel_variant(E.PROF_XC)
-    swept_now = eng.kernel_variant(E.PROF_SWEEP) != "" and eng.profile_launches(E.PROF_SWEEP) > 0
-    # the partial images the sweep leaves for the C- and A-phase (one per bseg, or per group of bsegs of a slab)
-    n_parts, part_floats = 0, 0
-    if swept_now:
-        pb = eng.internal(E.BUF_BSEG_PART).view(torch.int32).cpu().numpy().astype(np.int64)
-        n_parts = int((pb & 0x0FFFFFFF).max()) + 1 if len(pb) else 0
-        kc = 2 if (K <= 128 and NBk == 1) else 4 * ((K + 255) // 256)
-        part_floats = kc * 64 * 16 * NBk
-    W16 = 16 * NBk
-    n_tiles_B = int(sum((int(row_ptr[i + 1] - row_ptr[i]) + 63) // 64 for i in range(len(row_ptr) - 1)))
-    # ALGORITHMIC bytes per launch of every site (reads + writes the design needs):
-    #   X passes: X once (+ B-sized operands); fused rows / chained passes: their B-sized streams; the sweep: X once, aux / dual
-    #   in, B / aux / dual out (X C never reaches memory); the [G | R] reduction and the A-phase finish: the partial images
-    #   of the sweep (fp32 M, a-weighted Gram / fp64 B^T B); the C-phase finish: [G | R] in fp64, C and its ADMM variables;
-    #   unimodal regressions: y in, fit out, once more for the split search = 16 B per element; PARAFAC2 algebra: the per-tile
-    #   Gram statistics in, T_i out
-    alg_bytes = {
-        E.PROF_XC: S_X + (2 if xc_fused else 1) * S_B, E.PROF_XT: S_X + S_B, E.PROF_ROWS_FUSED: (2 + 4 * n_B) * S_B,
-        E.PROF_SWEEP: S_X + (1 + 4 * n_B) * S_B,
-        E.PROF_REDUCE: (4.0 * n_parts * (part_floats + W16 * W16 + W16) if swept_now else None),
-        E.PROF_C_FINISH: 8.0 * (K * r + r * r) + (1 + 4 * n_C) * 4.0 * K * r + 4.0 * K * W16,
-        E.PROF_A_FINISH: (4.0 * n_parts * part_floats + 8.0 * n_parts * r * r + 4.0 * K * W16) if swept_now else None,
-        E.PROF_ROWS_CHAIN: (3 + 2 * n_B) * S_B, E.PROF_UNIMODAL: 4 * S_B,
-        E.PROF_PF2: 8.0 * n_tiles_B * W16 * W16 + 12.0 * I_loc * r * r,
-    }
-    bound_of = {E.PROF_REDUCE: "latency (hbm figure for reference)", E.PROF_C_FINISH: "latency (hbm figure for reference)",
-                E.PROF_A_FINISH: "latency (hbm figure for reference)", E.PROF_PF2: "fp64 MFMA issue (hbm figure for reference)",
-                E.PROF_UNIMODAL: "latency of the pooling chain, then hbm"}
-    overhead_us = eng.profile_overhead_us()
-    n_steps_timed = n_regions * args.steps
 
-    def pmc_table():
-        """HBM bytes per launch from the committed rocprofv3 --pmc passes (profiles/), if a profile of this configuration
-        exists; counters are collected in separate runs, never inside this one."""
-        if world != 1:
+    if args.full:
+        # the replicated factor must be bit-identical on every rank (a divergent C would silently corrupt the fit)
+        c_identical = None
+        if world > 1:
+            bits = eng.C.view(torch.int32).to(torch.int64)
+            chk = torch.stack([bits.sum(), (bits * torch.arange(1, bits.numel() + 1, device=device).view_as(bits)).sum()])
+            lo_, hi_ = chk.clone(), chk.clone()
+            dist.all_reduce(lo_, op=dist.ReduceOp.MIN)
+            dist.all_reduce(hi_, op=dist.ReduceOp.MAX)
+            c_identical = bool(torch.equal(lo_, hi_))
+
+        # live roofline (HIP events inside the library, same stream as the kernels): EVERY hot launch site of the step is
+        # timed; the block names the site that takes the largest share of the step (launches per step x average duration)
+        from matcouply_amd import _engine as E
+
+        S_X, S_B = 4.0 * N_loc * K, 4.0 * N_loc * r
+        n_B, n_C = len(cfg["regs"][1]), len(cfg["regs"][2])
+        NBk = (r + 15) // 16
+        NBk = 4 if NBk == 3 else NBk
+        xc_fused = "GRAM=" in eng.kernel_variant(E.PROF_XC) and "GRAM=0" not in eng.kernel_variant(E.PROF_XC)
+        swept_now = eng.kernel_variant(E.PROF_SWEEP) != "" and eng.profile_launches(E.PROF_SWEEP) > 0
+        # the partial images the sweep leaves for the C- and A-phase (one per bseg, or per group of bsegs of a slab)
+        n_parts, part_floats = 0, 0
+        if swept_now:
+            pb = eng.internal(E.BUF_BSEG_PART).view(torch.int32).cpu().numpy().astype(np.int64)
+            n_parts = int((pb & 0x0FFFFFFF).max()) + 1 if len(pb) else 0
+            kc = 2 if (K <= 128 and NBk == 1) else 4 * ((K + 255) // 256)
+            part_floats = kc * 64 * 16 * NBk
+        W16 = 16 * NBk
+        n_tiles_B = int(sum((int(row_ptr[i + 1] - row_ptr[i]) + 63) // 64 for i in range(len(row_ptr) - 1)))
+        # ALGORITHMIC bytes per launch of every site (reads + writes the design needs):
+        #   X passes: X once (+ B-sized operands); fused rows / chained passes: their B-sized streams; the sweep: X once, aux / dual
+        #   in, B / aux / dual out (X C never reaches memory); the [G | R] reduction and the A-phase finish: the partial images
+        #   of the sweep (fp32 M, a-weighted Gram / fp64 B^T B); the C-phase finish: [G | R] in fp64, C and its ADMM variables;
+        #   unimodal regressions: y in, fit out, once more for the split search = 16 B per element; PARAFAC2 algebra: the per-tile
+        #   Gram statistics in, T_i out
+        alg_bytes = {
+            E.PROF_XC: S_X + (2 if xc_fused else 1) * S_B, E.PROF_XT: S_X + S_B, E.PROF_ROWS_FUSED: (2 + 4 * n_B) * S_B,
+            E.PROF_SWEEP: S_X + (1 + 4 * n_B) * S_B,
+            E.PROF_REDUCE: (4.0 * n_parts * (part_floats + W16 * W16 + W16) if swept_now else None),
+            E.PROF_C_FINISH: 8.0 * (K * r + r * r) + (1 + 4 * n_C) * 4.0 * K * r + 4.0 * K * W16,
+            E.PROF_A_FINISH: (4.0 * n_parts * part_floats + 8.0 * n_parts * r * r + 4.0 * K * W16) if swept_now else None,
+            E.PROF_ROWS_CHAIN: (3 + 2 * n_B) * S_B, E.PROF_UNIMODAL: 4 * S_B,
+            E.PROF_PF2: 8.0 * n_tiles_B * W16 * W16 + 12.0 * I_loc * r * r,
+        }
+        bound_of = {E.PROF_REDUCE: "latency (hbm figure for reference)", E.PROF_C_FINISH: "latency (hbm figure for reference)",
+                    E.PROF_A_FINISH: "latency (hbm figure for reference)", E.PROF_PF2: "fp64 MFMA issue (hbm figure for reference)",
+                    E.PROF_UNIMODAL: "latency of the pooling chain, then hbm"}
+        overhead_us = eng.profile_overhead_us()
+        n_steps_timed = n_regions * args.steps
+
+        def pmc_table():
+            """HBM bytes per launch from the committed rocprofv3 --pmc passes (profiles/), if a profile of this configuration
+            exists; counters are collected in separate runs, never inside this one."""
+            if world != 1:
+                return None, None
+            for rnd in ("r6", "r5", "r4", "r3", "r2", "r1"):
+                path = os.path.join(REPO, "profiles", f"{rnd}_{args.config}_pmc_traffic.json")
+                if os.path.exists(path):
+                    with open(path) as f:
+                        return json.load(f)["kernels"], os.path.relpath(path, REPO)
             return None, None
-        for rnd in ("r6", "r5", "r4", "r3", "r2", "r1"):
-            path = os.path.join(REPO, "profiles", f"{rnd}_{args.config}_pmc_traffic.json")
-            if os.path.exists(path):
-                with open(path) as f:
-                    return json.load(f)["kernels"], os.path.relpath(path, REPO)
-        return None, None
 
-    pmc_kernels, pmc_source = pmc_table()
+        pmc_kernels, pmc_source = pmc_table()
 
-    def achievable_gbps():
-        """the read bandwidth THIS box delivers to a pure streaming kernel (mcl_read_bandwidth), measured in this process after
-        the timed regions: over up to 2 GiB of X when X exceeds the 256 MB last-level cache, else over a 1 GiB scratch buffer"""
-        try:
-            n_bytes = X.numel() * 4
-            if n_bytes >= (600 << 20):
-                buf = X.view(-1)[: min(X.numel(), (2 << 30) // 4)]
-            else:
-                buf = torch.empty((1 << 30) // 4, dtype=torch.float32, device=device).zero_()
-            return E.read_bandwidth(buf, repeats=10)
-        except Exception as exc:  # a measurement aid: its failure must not cost the line
-            print(f"[bench] read-bandwidth probe failed: {exc}", file=sys.stderr)
-            return None
+        def achievable_gbps():
+            """the read bandwidth THIS box delivers to a pure streaming kernel (mcl_read_bandwidth), measured in this process after
+            the timed regions: over up to 2 GiB of X when X exceeds the 256 MB last-level cache, else over a 1 GiB scratch buffer"""
+            try:
+                n_bytes = X.numel() * 4
+                if n_bytes >= (600 << 20):
+                    buf = X.view(-1)[: min(X.numel(), (2 << 30) // 4)]
+                else:
+                    buf = torch.empty((1 << 30) // 4, dtype=torch.float32, device=device).zero_()
+                return E.read_bandwidth(buf, repeats=10)
+            except Exception as exc:  # a measurement aid: its failure must not cost the line
+                print(f"[bench] read-bandwidth probe failed: {exc}", file=sys.stderr)
+                return None
 
-    hbm_achievable = achievable_gbps() if rank == 0 else None
+        hbm_achievable = achievable_gbps() if rank == 0 else None
 
-    def pmc_traffic(kernel_variant):
-        if not pmc_kernels:
-            return None
-        base = kernel_variant.split("<")[0].split(" ")[0]
-        # a site that launches several kernel forms (chained row passes): the launch-weighted mean of its kernels
-        hits = [v for name, v in pmc_kernels.items() if name.split("<")[0] == base or
-                (base == "k_rows_finish_solve_stats" and name.split("<")[0] in ("k_rows_solve_stats", "k_rows_finish_fused")) or
-                (base == "k_rows_chain_first" and name.split("<")[0].startswith("k_rows_chain_"))]
-        if not hits:
-            return None
-        n = sum(v["launches"] for v in hits)
-        return int(sum((v["fetch_bytes_per_launch"] + v["write_bytes_per_launch"]) * v["launches"] for v in hits) / max(n, 1))
+        def pmc_traffic(kernel_variant):
+            if not pmc_kernels:
+                return None
+            base = kernel_variant.split("<")[0].split(" ")[0]
+            # a site that launches several kernel forms (chained row passes): the launch-weighted mean of its kernels
+            hits = [v for name, v in pmc_kernels.items() if name.split("<")[0] == base or
+                    (base == "k_rows_finish_solve_stats" and name.split("<")[0] in ("k_rows_solve_stats", "k_rows_finish_fused")) or
+                    (base == "k_rows_chain_first" and name.split("<")[0].startswith("k_rows_chain_"))]
+            if not hits:
+                return None
+            n = sum(v["launches"] for v in hits)
+            return int(sum((v["fetch_bytes_per_launch"] + v["write_bytes_per_launch"]) * v["launches"] for v in hits) / max(n, 1))
 
-    per_kernel = []
-    for slot in range(E.PROF_SLOTS):
-        tot_ms, n = eng.profile_read(slot)
-        launches = eng.profile_launches(slot)
-        if not n or not launches:
-            continue
-        avg_us = 1e3 * tot_ms / n
-        # the event pair itself costs `overhead_us` of marker handling (calibrated on an empty pair): the kernel's share
-        net_us = max(avg_us - overhead_us, 0.0)
-        ab = alg_bytes.get(slot)
-        per_step = launches / max(1, n_steps_timed)
-        e = dict(role=E.PROF_ROLE[slot], kernel=eng.kernel_variant(slot), launches_per_step=round(per_step, 3),
-                 avg_us=round(net_us, 2), avg_us_with_event_pair=round(avg_us, 2), launches_timed=n,
-                 us_per_step=round(per_step * net_us, 2),
-                 algorithmic_bytes=int(ab) if ab else None,
-                 achieved_gbps=round(ab / (net_us * 1e-6) / 1e9, 1) if ab and net_us > 0 else None,
-                 frac=round(ab / (net_us * 1e-6) / 1e9 / HBM_PEAK_GBS, 4) if ab and net_us > 0 else None,
-                 frac_achievable=(round(ab / (net_us * 1e-6) / 1e9 / hbm_achievable, 4) if ab and net_us > 0 and hbm_achievable else None),
-                 traffic=pmc_traffic(eng.kernel_variant(slot)), bound=bound_of.get(slot, "hbm"), slot=slot)
-        per_kernel.append(e)
-    per_kernel.sort(key=lambda e: -e["us_per_step"])
+        per_kernel = []
+        for slot in range(E.PROF_SLOTS):
+            tot_ms, n = eng.profile_read(slot)
+            launches = eng.profile_launches(slot)
+            if not n or not launches:
+                continue
+            avg_us = 1e3 * tot_ms / n
+            # the event pair itself costs `overhead_us` of marker handling (calibrated on an empty pair): the kernel's share
+            net_us = max(avg_us - overhead_us, 0.0)
+            ab = alg_bytes.get(slot)
+            per_step = launches / max(1, n_steps_timed)
+            e = dict(role=E.PROF_ROLE[slot], kernel=eng.kernel_variant(slot), launches_per_step=round(per_step, 3),
+                     avg_us=round(net_us, 2), avg_us_with_event_pair=round(avg_us, 2), launches_timed=n,
+                     us_per_step=round(per_step * net_us, 2),
+                     algorithmic_bytes=int(ab) if ab else None,
+                     achieved_gbps=round(ab / (net_us * 1e-6) / 1e9, 1) if ab and net_us > 0 else None,
+                     frac=round(ab / (net_us * 1e-6) / 1e9 / HBM_PEAK_GBS, 4) if ab and net_us > 0 else None,
+                     frac_achievable=(round(ab / (net_us * 1e-6) / 1e9 / hbm_achievable, 4) if ab and net_us > 0 and hbm_achievable else None),
+                     traffic=pmc_traffic(eng.kernel_variant(slot)), bound=bound_of.get(slot, "hbm"), slot=slot)
+            per_kernel.append(e)
+        per_kernel.sort(key=lambda e: -e["us_per_step"])
 
-    def mfma_block(slot, avg_ms):
-        """The kernel's second limiter: fp32 MFMA flops it ISSUES per launch (padded rank / K as the tiles are) over the same
-        HIP-event time, against the dense fp32 matrix peak.  At config 3 the analytic count (10.47 GFLOP) equals
-        SQ_INSTS_VALU_MFMA_MOPS_F32 x 512 of profiles/r2_c3_sq_counters.json; fp32 MFMA and VALU work do not overlap on a
-        SIMD (SQ_VALU_MFMA_COEXEC_CYCLES = 0), so the sweep sits at the SUM of this and its VALU / LDS / wait time."""
-        RPk = 16 * ((r + 15) // 16)
-        Kp = 128 if (slot == E.PROF_SWEEP and K <= 128 and RPk == 16) else 256 * ((K + 255) // 256) if slot == E.PROF_SWEEP else 64 * ((K + 63) // 64)
-        n_inner = 5
-        flops = {E.PROF_XC: 2.0 * N_loc * Kp * RPk + (2.0 * N_loc * RPk * RPk if xc_fused else 0.0),
-                 E.PROF_XT: 2.0 * N_loc * Kp * RPk + 2.0 * N_loc * RPk * RPk,
-                 E.PROF_ROWS_FUSED: 2.0 * N_loc * RPk * RPk * n_inner,
-                 E.PROF_SWEEP: 4.0 * N_loc * Kp * RPk + 2.0 * N_loc * RPk * RPk * (n_inner + 2)}.get(slot)
-        if flops is None or avg_ms <= 0:
-            return None
-        tf = flops / (avg_ms * 1e-3) / 1e12
-        return dict(achieved=round(tf, 2), peak=MFMA_F32_PEAK_TFLOPS, unit="TFLOP/s", frac=round(tf / MFMA_F32_PEAK_TFLOPS, 4),
-                    flops_per_launch=int(flops), counted="issued fp32 MFMA flops (analytic, padded tiles)")
+        def mfma_block(slot, avg_ms):
+            """The kernel's second limiter: fp32 MFMA flops it ISSUES per launch (padded rank / K as the tiles are) over the same
+            HIP-event time, against the dense fp32 matrix peak.  At config 3 the analytic count (10.47 GFLOP) equals
+            SQ_INSTS_VALU_MFMA_MOPS_F32 x 512 of profiles/r2_c3_sq_counters.json; fp32 MFMA and VALU work do not overlap on a
+            SIMD (SQ_VALU_MFMA_COEXEC_CYCLES = 0), so the sweep sits at the SUM of this and its VALU / LDS / wait time."""
+            RPk = 16 * ((r + 15) // 16)
+            Kp = 128 if (slot == E.PROF_SWEEP and K <= 128 and RPk == 16) else 256 * ((K + 255) // 256) if slot == E.PROF_SWEEP else 64 * ((K + 63) // 64)
+            n_inner = 5
+            flops = {E.PROF_XC: 2.0 * N_loc * Kp * RPk + (2.0 * N_loc * RPk * RPk if xc_fused else 0.0),
+                     E.PROF_XT: 2.0 * N_loc * Kp * RPk + 2.0 * N_loc * RPk * RPk,
+                     E.PROF_ROWS_FUSED: 2.0 * N_loc * RPk * RPk * n_inner,
+                     E.PROF_SWEEP: 4.0 * N_loc * Kp * RPk + 2.0 * N_loc * RPk * RPk * (n_inner + 2)}.get(slot)
+            if flops is None or avg_ms <= 0:
+                return None
+            tf = flops / (avg_ms * 1e-3) / 1e12
+            return dict(achieved=round(tf, 2), peak=MFMA_F32_PEAK_TFLOPS, unit="TFLOP/s", frac=round(tf / MFMA_F32_PEAK_TFLOPS, 4),
+                        flops_per_launch=int(flops), counted="issued fp32 MFMA flops (analytic, padded tiles)")
 
-    roofline = None
-    timed_sites = [e for e in per_kernel if e["algorithmic_bytes"]]
-    if timed_sites:
-        dom = timed_sites[0]  # the largest share of the step among the sites with an algorithmic byte count
-        slot = dom["slot"]
-        roofline = dict(bound="hbm", achieved=dom["achieved_gbps"], peak=HBM_PEAK_GBS, unit="GB/s", frac=dom["frac"],
-                        peak_achievable=round(hbm_achievable, 1) if hbm_achievable else None,
-                        frac_achievable=dom["frac_achievable"],
-                        peak_achievable_is=("streaming-read GB/s measured in this process by mcl_read_bandwidth (the data-sheet "
-                                            "8 TB/s is `peak`)"),
-                        traffic=dom["traffic"],
-                        traffic_source=("static: %s (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE of this command in separate "
-                                        "passes, not measured in this run)" % pmc_source) if dom["traffic"] is not None else None,
-                        kernel=dom["kernel"], kernel_role=dom["role"], launches_per_step=dom["launches_per_step"],
-                        avg_us=dom["avg_us"], avg_us_with_event_pair=dom["avg_us_with_event_pair"],
-                        event_pair_overhead_us=round(overhead_us, 2), launches_timed=dom["launches_timed"],
-                        launches_in_timed_regions=int(round(dom["launches_per_step"] * n_steps_timed)), event_stride=prof_stride,
-                        algorithmic_bytes_per_launch=dom["algorithmic_bytes"],
-                        chosen_by="largest launches_per_step x avg_us of the step (per_kernel is sorted by it)",
-                        note=dom["bound"] if dom["bound"] != "hbm" else None,
-                        mfma=mfma_block(slot, dom["avg_us"] * 1e-3),
-                        per_kernel=[{k: v for k, v in e.items() if k != "slot"} for e in per_kernel],
-                        kernels_us_per_step=round(sum(e["us_per_step"] for e in per_kernel), 2))
+        roofline = None
+        timed_sites = [e for e in per_kernel if e["algorithmic_bytes"]]
+        if timed_sites:
+            dom = timed_sites[0]  # the largest share of the step among the sites with an algorithmic byte count
+            slot = dom["slot"]
+            roofline = dict(bound="hbm", achieved=dom["achieved_gbps"], peak=HBM_PEAK_GBS, unit="GB/s", frac=dom["frac"],
+                            peak_achievable=round(hbm_achievable, 1) if hbm_achievable else None,
+                            frac_achievable=dom["frac_achievable"],
+                            peak_achievable_is=("streaming-read GB/s measured in this process by mcl_read_bandwidth (the data-sheet "
+                                                "8 TB/s is `peak`)"),
+                            traffic=dom["traffic"],
+                            traffic_source=("static: %s (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE of this command in separate "
+                                            "passes, not measured in this run)" % pmc_source) if dom["traffic"] is not None else None,
+                            kernel=dom["kernel"], kernel_role=dom["role"], launches_per_step=dom["launches_per_step"],
+                            avg_us=dom["avg_us"], avg_us_with_event_pair=dom["avg_us_with_event_pair"],
+                            event_pair_overhead_us=round(overhead_us, 2), launches_timed=dom["launches_timed"],
+                            launches_in_timed_regions=int(round(dom["launches_per_step"] * n_steps_timed)), event_stride=prof_stride,
+                            algorithmic_bytes_per_launch=dom["algorithmic_bytes"],
+                            chosen_by="largest launches_per_step x avg_us of the step (per_kernel is sorted by it)",
+                            note=dom["bound"] if dom["bound"] != "hbm" else None,
+                            mfma=mfma_block(slot, dom["avg_us"] * 1e-3),
+                            per_kernel=[{k: v for k, v in e.items() if k != "slot"} for e in per_kernel],
+                            kernels_us_per_step=round(sum(e["us_per_step"] for e in per_kernel), 2))
 
-    final = ring[n_regions * args.steps - 1].cpu().numpy() if args.steps else None
     if rank == 0:
         its = args.steps / elapsed
-        S_X_tot, S_B_tot = 4.0 * N_tot * K, 4.0 * N_tot * r
-        swept = swept_now
-        bytes_iter = (S_X_tot + (1 + 4 * n_B) * S_B_tot) if swept else (2 * S_X_tot + (5 + 4 * n_B) * S_B_tot)
+        figures = {}
+        if args.full:
+            S_X_tot, S_B_tot = 4.0 * N_tot * K, 4.0 * N_tot * r
+            swept = swept_now
+            bytes_iter = (S_X_tot + (1 + 4 * n_B) * S_B_tot) if swept else (2 * S_X_tot + (5 + 4 * n_B) * S_B_tot)
+            figures = {
+                "algorithmic_bytes_per_iter": int(bytes_iter),
+                "hbm_gbps_algorithmic": round(bytes_iter * its / 1e9, 1),
+                "roofline": (dict(roofline, step_frac=round(bytes_iter / (1e-3 * 1e3 * elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 4),
+                                  step_frac_is="algorithmic_bytes_per_iter / ms_per_step / peak (whole step, all kernels and gaps)")
+                             if roofline else None),
+            }
         out = {
             "metric": "AO-ADMM outer-iters/sec", "value": round(its, 2), "unit": "outer-iters/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 6),
@@ -694,11 +768,7 @@ def main():
             "config": {"workload": cfg["desc"], "I": cfg["I"], "J": cfg["J"], "sum_J": N_tot, "K": K, "rank": r,
                        "inner_n_iter_max": 5, "diagnostics_every_iteration": True,
                        "sharding": f"{world} x contiguous slab ranges" if world > 1 else "single device"},
-            "algorithmic_bytes_per_iter": int(bytes_iter),
-            "hbm_gbps_algorithmic": round(bytes_iter * its / 1e9, 1),
-            "roofline": (dict(roofline, step_frac=round(bytes_iter / (1e-3 * 1e3 * elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 4),
-                              step_frac_is="algorithmic_bytes_per_iter / ms_per_step / peak (whole step, all kernels and gaps)")
-                         if roofline else None),
+            **figures,
             "timed_regions": n_regions, "region_ms": [round(1e3 * v, 4) for v in region_s], "region_stat": "median",
             "region_ms_stats": {"min": round(1e3 * float(np.min(region_s)), 4), "median": round(1e3 * elapsed, 4),
                                 "q25": round(1e3 * float(np.percentile(region_s, 25)), 4),
@@ -711,27 +781,28 @@ def main():
             out["collectives_per_step"] = round(coll_per_step, 2)
             out["collective_path"] = ("RCCL called directly on the engine's stream (matcouply_amd/_rccl.py)" if direct is not None
                                       else f"torch.distributed ({backend})")
-            out["replicated_C_bit_identical"] = c_identical
-        if final is not None:
-            xsq, inner, model = final[5], final[3], final[4]
-            out["final_rel_rec_error"] = round(float(np.sqrt(max(0.0, xsq - 2 * inner + model) / xsq)), 6)
-        t_leg = leg("roofline+checks", t_leg)
-        left = lambda: args.wall_budget - (time.perf_counter() - _T0)
-        if world == 1 and not args.no_api:
-            if left() > 0.5 * args.wall_budget:
-                out["api"] = api_block(cfg, X, row_ptr)
-            else:
-                out["api"] = {"skipped": f"{time.perf_counter() - _T0:.0f} s of the --wall-budget of {args.wall_budget:.0f} s were "
-                                         "used before this optional leg (wall_s names the slow leg)"}
-            t_leg = leg("api_block", t_leg)
-        if not args.no_cpu_baseline and world == 1:
-            # the CPU leg is part of the contract line: never skipped, but its sample shrinks with the time that is left
-            out["cpu_baseline"] = cpu_baseline(cfg, max(1.0, min(args.cpu_budget, 0.25 * left())))
-            t_leg = leg("cpu_baseline", t_leg)
-        elif world > 1:
-            # the CPU leg is timed on rank 0 at N = 1 only (task contract); the N > 1 lines point at it
-            out["cpu_baseline"] = {"value": None, "unit": "outer-iters/s", "cores": None, "kind": "port",
-                                   "sample": "not timed at N > 1: see the cpu_baseline of the N = 1 line of the same workload"}
+            if args.full:
+                out["replicated_C_bit_identical"] = c_identical
+        xsq, inner, model = final[5], final[3], final[4]
+        out["final_rel_rec_error"] = round(float(np.sqrt(max(0.0, xsq - 2 * inner + model) / xsq)), 6)
+        if args.full:
+            t_leg = leg("roofline+checks", t_leg)
+            left = lambda: args.wall_budget - (time.perf_counter() - _T0)
+            if world == 1 and not args.no_api:
+                if left() > 0.5 * args.wall_budget:
+                    out["api"] = api_block(cfg, X, row_ptr)
+                else:
+                    out["api"] = {"skipped": f"{time.perf_counter() - _T0:.0f} s of the --wall-budget of {args.wall_budget:.0f} s were "
+                                             "used before this optional leg (wall_s names the slow leg)"}
+                t_leg = leg("api_block", t_leg)
+            if not args.no_cpu_baseline and world == 1:
+                # the CPU leg is part of the --full line: never skipped, but its sample shrinks with the time that is left
+                out["cpu_baseline"] = cpu_baseline(cfg, max(1.0, min(args.cpu_budget, 0.25 * left())))
+                t_leg = leg("cpu_baseline", t_leg)
+            elif world > 1:
+                # the CPU leg is timed on rank 0 at N = 1 only; the N > 1 lines point at it
+                out["cpu_baseline"] = {"value": None, "unit": "outer-iters/s", "cores": None, "kind": "port",
+                                       "sample": "not timed at N > 1: see the cpu_baseline of the N = 1 line of the same workload"}
         WALL_S["total_until_print"] = round(time.perf_counter() - _T0, 3)
         out["wall_s"] = dict(WALL_S)
         print(json.dumps(out), flush=True)

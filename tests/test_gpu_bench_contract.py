@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -43,7 +44,7 @@ def test_roofline_names_the_dominant_kernel_of_config_4():
     """on the PARAFAC2 + L2-ball stack the dominant site is the chained row pass (six launches per iteration), not the
     X passes (two)"""
     out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--config", "c4", "--steps", "5",
-                          "--warmup", "2", "--regions", "3", "--no-api", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600)
+                          "--warmup", "2", "--regions", "3", "--no-api", "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     d = _last_json(out.stdout)
     _check_per_kernel(d)
@@ -54,7 +55,7 @@ def test_roofline_names_the_dominant_kernel_of_config_4():
 
 def test_single_rank_line():
     out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--config", "c2", "--steps", "6",
-                          "--warmup", "2", "--regions", "3", "--cpu-budget", "2"], capture_output=True, text=True, timeout=600)
+                          "--warmup", "2", "--regions", "3", "--cpu-budget", "2", "--full"], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     d = _last_json(out.stdout)
     assert all(k in d for k in REQUIRED), sorted(set(REQUIRED) - set(d))
@@ -91,6 +92,32 @@ def test_single_rank_line():
     assert bad.returncode != 0 and "WORLD_SIZE" in (bad.stderr + bad.stdout)
 
 
+def test_plain_run_times_its_steps_and_dumps_what_they_computed(tmp_path):
+    """without --full: ONE timed region of exactly --steps steps, the headline fields and none of the --full legs; with the
+    same arguments two runs start from the same seeded state, so what --dump-outputs writes agrees between them"""
+    dumps = []
+    for run in range(2):
+        out_dir = tmp_path / f"run{run}"
+        out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--config", "c2", "--steps", "7",
+                              "--warmup", "2", "--dump-outputs", str(out_dir)], capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-3000:]
+        d = _last_json(out.stdout)
+        assert d["metric"] == "AO-ADMM outer-iters/sec" and d["unit"] == "outer-iters/s" and d["higher_is_better"] is True
+        assert d["dtype"] == "f32" and d["steps"] == 7 and d["warmup"] == 2
+        assert d["timed_regions"] == 1 and len(d["region_ms"]) == 1 and abs(d["ms_per_step"] * 7 - d["region_ms"][0]) < 1e-3
+        assert abs(d["value"] - 1e3 / d["ms_per_step"]) / d["value"] < 1e-3
+        assert not {"roofline", "api", "cpu_baseline", "replicated_C_bit_identical"} & set(d), sorted(d)
+        assert not {"roofline+checks", "api_block", "cpu_baseline"} & set(d["wall_s"]) and "dump_outputs" in d["wall_s"]
+        files = sorted(out_dir.glob("*.npy"))
+        assert [f.stem for f in files] == ["A", "B", "C", "diagnostics"] and sum(f.stat().st_size for f in files) <= 64e6
+        dumped = {f.stem: np.load(f) for f in files}
+        assert dumped["A"].shape == (256, 8) and dumped["B"].shape == (256 * 256, 8) and dumped["C"].shape == (128, 8)
+        assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in dumped.values())
+        dumps.append(dumped)
+    for name, a in dumps[0].items():
+        np.testing.assert_allclose(dumps[1][name], a, rtol=1e-5, atol=1e-7, err_msg=name)
+
+
 @pytest.mark.parametrize("n", [2, 4])
 def test_gpus_2_without_a_launcher_spawns_its_own_ranks(n):
     """the driver's command form: `python bench.py --gpus N ...` with no torch.distributed.run around it;
@@ -99,7 +126,7 @@ def test_gpus_2_without_a_launcher_spawns_its_own_ranks(n):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(MCL_BENCH_SHARE_GPU="1", MCL_BENCH_BACKEND="gloo")
     out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", str(n), "--config", "c3_4th", "--steps", "4",
-                          "--warmup", "2", "--regions", "2", "--settle-ms", "20"], env=env, capture_output=True, text=True,
+                          "--warmup", "2", "--regions", "2", "--settle-ms", "20", "--full"], env=env, capture_output=True, text=True,
                          timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -119,12 +146,12 @@ def test_gpus_2_without_a_launcher_spawns_its_own_ranks(n):
 
 
 @pytest.mark.parametrize("config,n", [("c3_8th", 2), ("c4", 2), ("c4", 4)])
-def test_two_ranks_sharing_the_gpu(config, n):
+def test_two_ranks_sharing_the_gpu(config, n, tmp_path):
     env = dict(os.environ, MCL_BENCH_SHARE_GPU="1", MCL_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     port = str(29400 + (os.getpid() + len(config) + 7 * n) % 200)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
            "--master-port", port, os.path.join(REPO, "bench.py"), "--gpus", str(n), "--config", config, "--steps", "4",
-           "--warmup", "2", "--regions", "2", "--settle-ms", "20"]
+           "--warmup", "2", "--regions", "2", "--settle-ms", "20", "--full", "--dump-outputs", str(tmp_path)]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     d = _last_json(out.stdout)
@@ -132,3 +159,8 @@ def test_two_ranks_sharing_the_gpu(config, n):
     assert d["replicated_C_bit_identical"] is True
     assert d["collectives_per_step"] == (6.0 if config == "c4" else 1.0)  # [G | R] (+ PARAFAC2 per inner iteration)
     assert 0 < d["final_rel_rec_error"] < 1
+    # --dump-outputs gathers the sharded factors of every rank in row order
+    dumped = {name: np.load(tmp_path / f"{name}.npy") for name in ("A", "B", "C", "diagnostics")}
+    r = d["config"]["rank"]
+    assert dumped["A"].shape == (d["config"]["I"], r) and dumped["B"].shape == (d["config"]["sum_J"], r)
+    assert dumped["C"].shape == (d["config"]["K"], r) and all(np.isfinite(a).all() for a in dumped.values())

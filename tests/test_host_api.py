@@ -436,6 +436,26 @@ def test_bench_counts_the_cores_it_may_use():
     assert n <= len(os.sched_getaffinity(0))
 
 
+def test_bench_dump_outputs_stays_within_64_mb(tmp_path):
+    """bench.py --dump-outputs: arrays that fit are written whole; a larger factor is replaced by the same fixed sample of
+    its rows (kept in row order) on every run, and all files together stay within 64 MB"""
+    import bench
+
+    big = np.random.RandomState(1).rand(1 << 21, 32).astype(np.float32)  # 256 MiB
+    big[:, 0] = np.arange(len(big))  # each row names itself (exact in float32 below 2^24)
+    arrays = {"A": np.ones((1024, 32), np.float32), "B": big, "C": np.full((256, 32), 2.0, np.float32), "diagnostics": np.arange(32.0)}
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), arrays)
+        assert sum(f.stat().st_size for f in (tmp_path / run).iterdir()) <= 64e6
+    for name in ("A", "C", "diagnostics"):
+        assert np.array_equal(np.load(tmp_path / "a" / f"{name}.npy"), arrays[name])
+    B = np.load(tmp_path / "a" / "B.npy")
+    assert B.dtype == np.float32 and 0.9 * bench.DUMP_BYTES < B.nbytes <= bench.DUMP_BYTES and B.shape[1] == 32
+    assert np.array_equal(B, np.load(tmp_path / "b" / "B.npy"))
+    rows = B[:, 0].astype(np.int64)
+    assert np.all(np.diff(rows) > 0) and np.array_equal(big[rows], B)  # whole rows of the original, in row order
+
+
 # ---- plugin surface: docstring helpers and subclass routing ------------------------------------------------------
 def test_doc_utils_shim_inherits_docstrings():
     """the names user penalties import from the reference's matcouply._doc_utils (examples/plot_custom_penalty.py:213-231)"""

@@ -7,7 +7,7 @@
 cd /tmp; export TMPDIR=/tmp
 R=/root/repo; RND=$1; C=$2; S=${3:-20}; O=$R/gpurun_out/ev$RND/$C; mkdir -p $O
 W=${5:-3}  # c5: 30 - the unimodal regressions reach their steady-state cost (deep stacks) only after ~25 outer iterations
-B="python3 $R/bench.py --config $C --steps $S --warmup $W"
+B="python3 $R/bench.py --config $C --steps $S --warmup $W --full"
 $B > $O/bench.json 2> $O/bench.err || { tail -3 $O/bench.err; exit 1; }
 echo "bench: $(cut -c1-110 $O/bench.json)"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o t -- $B --regions 1 --no-cpu-baseline --no-api > $O/bench_traced.json 2> $O/trace.err || exit 1

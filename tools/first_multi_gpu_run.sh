@@ -21,7 +21,7 @@ run() {  # run <config> <n> <steps> <warmup> [env ...]
   local cfg=$1 n=$2 steps=$3 warm=$4; shift 4
   local tag="$OUT/${cfg}_n${n}"
   echo "== config $cfg on $n device(s)"
-  if ! env "$@" timeout -k 10 900 python3 bench.py --config "$cfg" --gpus "$n" --steps "$steps" --warmup "$warm" --no-api \
+  if ! env "$@" timeout -k 10 900 python3 bench.py --config "$cfg" --gpus "$n" --steps "$steps" --warmup "$warm" --no-api --full \
         > "$tag.json" 2> "$tag.err"; then
     echo "FAILED: $cfg at N=$n (stderr: $tag.err; the last '[bench] <leg>' line names the leg that hung)"
     echo "  isolate: MCL_NO_DIRECT_RCCL=1 (collectives through torch.distributed), MCL_RCCL_INIT_TIMEOUT_S=120 (slow ncclCommInitRank),"
