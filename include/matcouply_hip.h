@@ -34,6 +34,8 @@ typedef struct mcl_context mcl_context;
  *     mcl_options.inner_tol / exact_products, native GeneralizedL2 / UnitSimplex kinds (mcl_penalty_desc grew two fields),
  *     mcl_penalty_value, mcl_svd_init;
  * 410 mcl_condition_probe, mcl_condition_monitor, mcl_read_bandwidth (nothing else changed).
+ *     410 also gained, purely additively, mcl_set_problem_typed and mcl_svd_init_typed (16-bit X, enum mcl_x_type):
+ *     the version stays 410; a host detects the capability by the presence of the symbols.
  * A host MUST compare mcl_version() with the MCL_ABI_VERSION it was built against before any other call. */
 #define MCL_ABI_VERSION 410
 
@@ -102,6 +104,13 @@ int mcl_version(void);
 /* ---- problem definition (replaces the `matrices`, `rank` arguments of cmf_aoadmm, decomposition.py:662) */
 /* X: device [row_ptr[I], K]; row_ptr: HOST int64[I+1], non-decreasing, row_ptr[0] = 0. */
 int mcl_set_problem(mcl_context *ctx, const float *X, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank);
+/* Element type of X.  A 16-bit X stays 16-bit in device memory; every kernel converts its elements exactly to fp32 on
+ * load, so a run on 16-bit X gives bit for bit the results of the fp32 run on the upcast matrix. */
+enum mcl_x_type { MCL_X_F32 = 0, MCL_X_BF16 = 1, MCL_X_F16 = 2 };
+/* mcl_set_problem for X of element type x_type (mcl_x_type).  A 16-bit X must be 8-byte aligned (fp32: no requirement;
+ * the vectorised kernels take it when it is 16-byte aligned); the kernels pick the same variants as for fp32 X of the same
+ * shape.  mcl_set_problem(..) is mcl_set_problem_typed(.., MCL_X_F32, ..). */
+int mcl_set_problem_typed(mcl_context *ctx, const void *X, int32_t x_type, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank);
 int mcl_set_options(mcl_context *ctx, const mcl_options *opt);
 /* Factors of the CMF (decomposition.py:133,235,307): A [I, r], B packed [sum J_i, r], C [K, r]; updated in place. */
 int mcl_set_factors(mcl_context *ctx, float *A, float *B, float *C);
@@ -267,6 +276,9 @@ int mcl_cmf_to_packed(const float *A, const float *B, const float *C, const floa
 int64_t mcl_svd_init_workspace_bytes(const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank);
 int mcl_svd_init(const float *X, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank, int32_t threshold, float *B, float *C,
                  void *workspace, int64_t workspace_bytes, int32_t *info, void *hip_stream);
+/* mcl_svd_init for X of element type x_type (mcl_x_type); mcl_svd_init(..) is mcl_svd_init_typed(.., MCL_X_F32, ..) */
+int mcl_svd_init_typed(const void *X, int32_t x_type, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank, int32_t threshold,
+                       float *B, float *C, void *workspace, int64_t workspace_bytes, int32_t *info, void *hip_stream);
 const char *mcl_svd_init_last_error(void);
 
 /* ---- introspection for tests / profiling ------------------------------------------------------------- */

@@ -30,6 +30,18 @@ PROF_ROLE = {PROF_XC: "X C pass", PROF_XT: "X^T (B o a) pass", PROF_ROWS_FUSED: 
              PROF_A_FINISH: "A-phase finish", PROF_ROWS_CHAIN: "chained B row pass", PROF_UNIMODAL: "unimodal regressions",
              PROF_PF2: "PARAFAC2 per-slab algebra", PROF_DIAG: "diagnostics reduction", PROF_OTHER: "other launches"}
 VARIANT_EXACT_MODE = 100
+X_F32, X_BF16, X_F16 = 0, 1, 2  # enum mcl_x_type
+
+
+def x_type_of(dtype):
+    """enum mcl_x_type of a torch dtype of X (float32, bfloat16, float16); TypeError for any other"""
+    import torch
+
+    t = {torch.float32: X_F32, torch.bfloat16: X_BF16, torch.float16: X_F16}.get(dtype)
+    if t is None:
+        raise TypeError(f"X must be float32, bfloat16 or float16, not {dtype}")
+    return t
+
 # short names of the native kinds (descriptor dicts of bench.py / the test helpers -> enum mcl_penalty_kind)
 KIND = {"nn": PEN_NN, "box": PEN_BOX, "l1": PEN_L1, "l2ball": PEN_L2BALL, "unimodal": PEN_UNIMODAL,
         "parafac2": PEN_PARAFAC2, "tv": PEN_TV, "gl2": PEN_GL2, "simplex": PEN_SIMPLEX}
@@ -46,6 +58,7 @@ EXPORTED_SYMBOLS = [
     "mcl_internal_buffer", "mcl_kernel_variant", "mcl_profile_enable", "mcl_profile_set_stride", "mcl_profile_read", "mcl_profile_launches", "mcl_profile_overhead_us",
     "mcl_reload_switches", "mcl_active_switches", "mcl_record_event", "mcl_wait_event", "mcl_cmf_to_packed",
     "mcl_svd_init_workspace_bytes", "mcl_svd_init", "mcl_svd_init_last_error", "mcl_read_bandwidth",
+    "mcl_set_problem_typed", "mcl_svd_init_typed",
 ]
 
 
@@ -91,6 +104,7 @@ def load_library():
         "mcl_last_error": (ctypes.c_char_p, [P]),
         "mcl_version": (ctypes.c_int, []),
         "mcl_set_problem": (ctypes.c_int, [P, P, ctypes.POINTER(I64), I64, I64, I32]),
+        "mcl_set_problem_typed": (ctypes.c_int, [P, P, I32, ctypes.POINTER(I64), I64, I64, I32]),
         "mcl_set_options": (ctypes.c_int, [P, ctypes.POINTER(Options)]),
         "mcl_set_factors": (ctypes.c_int, [P, P, P, P]),
         "mcl_set_penalties": (ctypes.c_int, [P, I32, I32, ctypes.POINTER(PenaltyDesc)]),
@@ -143,6 +157,7 @@ def load_library():
         "mcl_cmf_to_packed": (ctypes.c_int, [P, P, P, P, P, I64, I64, I32, P, P]),
         "mcl_svd_init_workspace_bytes": (I64, [ctypes.POINTER(I64), I64, I64, I32]),
         "mcl_svd_init": (ctypes.c_int, [P, ctypes.POINTER(I64), I64, I64, I32, I32, P, P, P, I64, P, P]),
+        "mcl_svd_init_typed": (ctypes.c_int, [P, I32, ctypes.POINTER(I64), I64, I64, I32, I32, P, P, P, I64, P, P]),
         "mcl_svd_init_last_error": (ctypes.c_char_p, []),
         "mcl_read_bandwidth": (ctypes.c_int, [P, I64, I32, P, P, ctypes.POINTER(ctypes.c_double)]),
     }
@@ -203,14 +218,16 @@ def read_bandwidth(buf, repeats=10):
 
 
 def svd_init(X, row_ptr, rank, threshold=False):
-    """init="svd" / "threshold_svd" on the device (mcl_svd_init): X packed [sum J_i, K] float32 CUDA tensor -> (B packed
+    """init="svd" / "threshold_svd" on the device (mcl_svd_init_typed): X packed [sum J_i, K] float32 / bfloat16 / float16 CUDA
+    tensor -> (B packed
     [sum J_i, rank], C [K, rank], info int32 [I + 1]: subspace iterations per matrix, the stack last).  Singular vectors with
     the entry of largest magnitude positive (LAPACK's vectors up to sign)."""
     import torch
 
     lib = load_library()
-    if not (X.is_cuda and X.dtype == torch.float32 and X.is_contiguous()):
-        raise EngineError("X must be a contiguous float32 CUDA tensor")
+    xt = x_type_of(X.dtype)
+    if not (X.is_cuda and X.is_contiguous()):
+        raise EngineError("X must be a contiguous CUDA tensor")
     row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int64)
     I, K, N = len(row_ptr) - 1, int(X.shape[1]), int(X.shape[0])
     rp = row_ptr.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
@@ -224,8 +241,8 @@ def svd_init(X, row_ptr, rank, threshold=False):
     info = torch.zeros(I + 1, dtype=torch.int32, device=X.device)
     with torch.cuda.device(X.device):
         stream = torch.cuda.current_stream(X.device).cuda_stream
-        rc = lib.mcl_svd_init(X.data_ptr(), rp, I, K, int(rank), int(bool(threshold)), B.data_ptr(), C.data_ptr(), ws.data_ptr() + off,
-                              nbytes, info.data_ptr(), ctypes.c_void_p(stream))
+        rc = lib.mcl_svd_init_typed(X.data_ptr(), xt, rp, I, K, int(rank), int(bool(threshold)), B.data_ptr(), C.data_ptr(),
+                                    ws.data_ptr() + off, nbytes, info.data_ptr(), ctypes.c_void_p(stream))
     if rc != 0:
         raise EngineError(lib.mcl_svd_init_last_error().decode())
     return B, C, info
@@ -244,9 +261,12 @@ class NativeReg:
 class HipEngine:
     """Owns one `mcl_context` bound to torch's current HIP stream on `device`.
 
-    X: float32 CUDA tensor [sum J_i, K] (packed slabs), row_ptr: int64 array [I+1],
+    X: float32 / bfloat16 / float16 CUDA tensor [sum J_i, K] (packed slabs; a 16-bit X is read as such by every kernel),
+    row_ptr: int64 array [I+1],
     A/B/C: float32 CUDA tensors (updated in place), regs: [[NativeReg]*n0, [..]*n1, [..]*n2].
     """
+
+    supports_x16 = True  # takes a bfloat16 / float16 X as it is (a checker engine without the attribute gets X.float())
 
     def __init__(self, X, row_ptr, rank, A, B, C, regs, l2_penalty=(0.0, 0.0, 0.0), inner_n_iter_max=5,
                  feasibility_penalty_scale=1.0, constant_A=False, constant_B=False, exact_products=0, inner_tol=0.0):
@@ -256,7 +276,10 @@ class HipEngine:
         self.lib = load_library()
         if not torch.cuda.is_available():
             raise EngineError("no HIP device visible: matcouply_amd needs an MI355X (gfx950); there is no CPU fallback")
-        for name, t in (("X", X), ("A", A), ("B", B), ("C", C)):
+        self.x_type = x_type_of(X.dtype)
+        if not (X.is_cuda and X.is_contiguous()):
+            raise EngineError("X must be a contiguous CUDA tensor")
+        for name, t in (("A", A), ("B", B), ("C", C)):
             if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
                 raise EngineError(f"{name} must be a contiguous float32 CUDA tensor")
         self.device = X.device
@@ -272,8 +295,8 @@ class HipEngine:
             rc = self.lib.mcl_create(ctypes.byref(self._h), self.device.index or 0, ctypes.c_void_p(stream))
         if rc != 0:
             raise EngineError(self.lib.mcl_last_error(None).decode())
-        self._check(self.lib.mcl_set_problem(self._h, X.data_ptr(), self.row_ptr.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
-                                             self.I, self.K, self.r))
+        self._check(self.lib.mcl_set_problem_typed(self._h, X.data_ptr(), self.x_type,
+                                                   self.row_ptr.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), self.I, self.K, self.r))
         opt = Options()
         opt.feasibility_penalty_scale = float(feasibility_penalty_scale)
         for m in range(3):

@@ -8,6 +8,7 @@
 #include <utility>
 
 #include "mcl_internal.h"
+#include "xload.h"
 #include "rows_mfma.h"
 
 #define FULL_TILE 64
@@ -216,10 +217,8 @@ __global__ __launch_bounds__(256) void k_B_systems(const double *__restrict__ Ct
 // final fp64 roundings.  A wave owns 16 packed rows; per 16 columns of K: lane (i = l & 15, kk = l >> 4) holds
 // X[row0 + i][k0 + 4 kk .. + 3], step s of the fp64 MFMA pairs it with C[k0 + 4 kk + s][16 nb + (l & 15)]
 // (D: row = (l >> 4) + 4 reg, col = l & 15).  Only used when mode 1 has no penalty: a rare, accuracy-first path.
-template <int NB>
-__global__ __launch_bounds__(256) void k_contract_xc_f64(const float *__restrict__ X, const float *__restrict__ C, long N,
-                                                         int K, int r, double *__restrict__ XC64,
-                                                         float *__restrict__ XC32 = nullptr) {
+template <class XL, int NB>
+static __device__ __forceinline__ void k_contract_xc_f64_body(const typename XL::T *X, const float *C, long N, int K, int r, double *XC64, float *XC32) {
     typedef double f64x4 __attribute__((ext_vector_type(4)));
     const int lane = threadIdx.x & 63;
     const long row0 = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 16;
@@ -237,7 +236,7 @@ __global__ __launch_bounds__(256) void k_contract_xc_f64(const float *__restrict
             for (int s = 0; s < 4; ++s) {
                 const int k = k0 + 16 * h + 4 * kk + s;
                 const int kc = min(k, K - 1);  // unconditional loads at clamped indices, masked by a multiplication (no branch per load)
-                xv[h][s] = X[jx * K + kc] * ((k < K) ? 1.f : 0.f);
+                xv[h][s] = XL::ld1(X + jx * K + kc) * ((k < K) ? 1.f : 0.f);
 #pragma unroll
                 for (int nb = 0; nb < NB; ++nb) {
                     const int col = 16 * nb + i;
@@ -263,6 +262,19 @@ __global__ __launch_bounds__(256) void k_contract_xc_f64(const float *__restrict
                 if (XC32 != nullptr) XC32[j * r + col] = (float)acc[nb][v];  // exact-products mode: the image the row kernels read
             }
         }
+}
+template <int NB>
+__global__ __launch_bounds__(256) void k_contract_xc_f64(const float *__restrict__ X, const float *__restrict__ C, long N,
+                                                         int K, int r, double *__restrict__ XC64,
+                                                         float *__restrict__ XC32 = nullptr) {
+    k_contract_xc_f64_body<XF32, NB>(X, C, N, K, r, XC64, XC32);
+}
+// the 16-bit twin (xload.h): the same template arguments after the element type
+template <class XL, int NB>
+__global__ __launch_bounds__(256) void k_contract_xc_f64_h(const typename XL::T *__restrict__ X, const float *__restrict__ C, long N,
+                                                         int K, int r, double *__restrict__ XC64,
+                                                         float *__restrict__ XC32 = nullptr) {
+    k_contract_xc_f64_body<XL, NB>(X, C, N, K, r, XC64, XC32);
 }
 
 template <int RP>
@@ -1489,22 +1501,31 @@ __global__ __launch_bounds__(64) void k_A_e1(const float *__restrict__ rhsA, con
 // {A rows, B tiles, C tiles}; the next two blocks reduce the e1 columns; the last block writes the constants.
 // Every output entry is written by exactly one block (fixed summation order: deterministic).
 // ---------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_sumsq_partial(const float *__restrict__ x, long n, double *__restrict__ part) {
+template <class XL>
+static __device__ __forceinline__ void k_sumsq_partial_body(const typename XL::T *X, long n, double *part) {
     __shared__ double sm[4];
     double s = 0.0;
     const long stride = (long)gridDim.x * 256 * 4;
     for (long e = ((long)blockIdx.x * 256 + threadIdx.x) * 4; e < n; e += stride) {
         if (e + 3 < n) {
-            const float4 v = *reinterpret_cast<const float4 *>(x + e);
+            const mcl_xf32x4 v = XL::cvt(XL::template ld4<false>(X + e));
             s += (double)v.x * v.x + (double)v.y * v.y + (double)v.z * v.z + (double)v.w * v.w;
         } else {
-            for (long t = e; t < n; ++t) s += (double)x[t] * (double)x[t];
+            for (long t = e; t < n; ++t) s += (double)XL::ld1(X + t) * (double)XL::ld1(X + t);
         }
     }
     s = wave_sum(s);
     if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = s;
     __syncthreads();
     if (threadIdx.x == 0) part[blockIdx.x] = (sm[0] + sm[1]) + (sm[2] + sm[3]);
+}
+__global__ __launch_bounds__(256) void k_sumsq_partial(const float *__restrict__ X, long n, double *__restrict__ part) {
+    k_sumsq_partial_body<XF32>(X, n, part);
+}
+// the 16-bit twin (xload.h): the same template arguments after the element type
+template <class XL>
+__global__ __launch_bounds__(256) void k_sumsq_partial_h(const typename XL::T *__restrict__ X, long n, double *__restrict__ part) {
+    k_sumsq_partial_body<XL>(X, n, part);
 }
 
 __global__ __launch_bounds__(256) void k_sum_doubles(const double *__restrict__ part, int n, double *__restrict__ out) {
@@ -1806,32 +1827,42 @@ int mcl_launch_B_systems(mcl_context *c) {
 // exact-products mode (mcl_exact_mode): X C as fp64 sums of exact products, with its once-rounded fp32 image
 int mcl_launch_exact_xc(mcl_context *c) {
     ProfScope prof_(c, MCL_PROF_XC);
-    c->variant[MCL_PROF_XC] = "k_contract_xc_f64";
-    if (c->N == 0) return 0;
+    if (c->N == 0) {
+        c->variant[MCL_PROF_XC] = "k_contract_xc_f64";
+        return 0;
+    }
     const dim3 g((unsigned)(((c->N + 15) / 16 + 3) / 4));
+    return mcl_x_dispatch(c->x_type, [&](auto xl) {
+    using XL = decltype(xl);
+    const typename XL::T *X = mcl_x<XL>(c);
+    c->variant[MCL_PROF_XC] = std::string("k_contract_xc_f64") + mcl_x_kname<XL>() + (std::is_same_v<XL, XF32> ? "" : std::string("<") + XL::name + ">");
     if (c->NB == 1)
-        hipLaunchKernelGGL(k_contract_xc_f64<1>, g, dim3(256), 0, c->stream, c->X, c->C, (long)c->N, (int)c->K, c->r, c->XC64, c->XC);
+        hipLaunchKernelGGL((MCL_XKERNEL(k_contract_xc_f64, 1)), g, dim3(256), 0, c->stream, X, c->C, (long)c->N, (int)c->K, c->r, c->XC64, c->XC);
     else if (c->NB == 2)
-        hipLaunchKernelGGL(k_contract_xc_f64<2>, g, dim3(256), 0, c->stream, c->X, c->C, (long)c->N, (int)c->K, c->r, c->XC64, c->XC);
+        hipLaunchKernelGGL((MCL_XKERNEL(k_contract_xc_f64, 2)), g, dim3(256), 0, c->stream, X, c->C, (long)c->N, (int)c->K, c->r, c->XC64, c->XC);
     else
-        hipLaunchKernelGGL(k_contract_xc_f64<4>, g, dim3(256), 0, c->stream, c->X, c->C, (long)c->N, (int)c->K, c->r, c->XC64, c->XC);
+        hipLaunchKernelGGL((MCL_XKERNEL(k_contract_xc_f64, 4)), g, dim3(256), 0, c->stream, X, c->C, (long)c->N, (int)c->K, c->r, c->XC64, c->XC);
     MCL_CHECK_HIP(c, hipGetLastError());
     return 0;
+    });
 }
 
 int mcl_launch_B_solve_f64(mcl_context *c) {
     ProfScope prof_(c, MCL_PROF_ROWS_FUSED);
     c->variant[MCL_PROF_ROWS_FUSED] = "k_contract_xc_f64 + k_B_solve_f64";
     if (c->tilesB.n_tiles == 0) return 0;
-    {  // X C in fp64 (one inner iteration per phase for a penalty-free mode: computed right here)
+    mcl_x_dispatch(c->x_type, [&](auto xl) {  // X C in fp64 (one inner iteration per phase for a penalty-free mode: computed right here)
+        using XL = decltype(xl);
+        const typename XL::T *X = mcl_x<XL>(c);
         const dim3 g((unsigned)(((c->N + 15) / 16 + 3) / 4));
         if (c->NB == 1)
-            hipLaunchKernelGGL(k_contract_xc_f64<1>, g, dim3(256), 0, c->stream, c->X, c->C, (long)c->N, (int)c->K, c->r, c->XC64);
+            hipLaunchKernelGGL((MCL_XKERNEL(k_contract_xc_f64, 1)), g, dim3(256), 0, c->stream, X, c->C, (long)c->N, (int)c->K, c->r, c->XC64, nullptr);
         else if (c->NB == 2)
-            hipLaunchKernelGGL(k_contract_xc_f64<2>, g, dim3(256), 0, c->stream, c->X, c->C, (long)c->N, (int)c->K, c->r, c->XC64);
+            hipLaunchKernelGGL((MCL_XKERNEL(k_contract_xc_f64, 2)), g, dim3(256), 0, c->stream, X, c->C, (long)c->N, (int)c->K, c->r, c->XC64, nullptr);
         else
-            hipLaunchKernelGGL(k_contract_xc_f64<4>, g, dim3(256), 0, c->stream, c->X, c->C, (long)c->N, (int)c->K, c->r, c->XC64);
-    }
+            hipLaunchKernelGGL((MCL_XKERNEL(k_contract_xc_f64, 4)), g, dim3(256), 0, c->stream, X, c->C, (long)c->N, (int)c->K, c->r, c->XC64, nullptr);
+        return 0;
+    });
     dim3 grid((unsigned)((c->tilesB.n_tiles + 3) / 4)), block(256);
     DISPATCH_RP_T(c, k_B_solve_f64, grid, block, c->tilesB.slab, c->tilesB.row0, c->tilesB.nrows, c->tilesB.n_tiles, c->XC64,
                   c->A, c->LinvB64, c->r, c->B, c->gate_active);
@@ -2269,7 +2300,11 @@ int mcl_launch_x_sq(mcl_context *c) {
     ProfScope prof_(c, MCL_PROF_OTHER);
     const long n = (long)c->N * c->K;
     const int nb = 1024;
-    hipLaunchKernelGGL(k_sumsq_partial, dim3(nb), dim3(256), 0, c->stream, c->X, n, c->xsq_part);
+    mcl_x_dispatch(c->x_type, [&](auto xl) {
+        using XL = decltype(xl);
+        hipLaunchKernelGGL((MCL_XKERNEL0(k_sumsq_partial)), dim3(nb), dim3(256), 0, c->stream, mcl_x<XL>(c), n, c->xsq_part);
+        return 0;
+    });
     hipLaunchKernelGGL(k_sum_doubles, dim3(1), dim3(256), 0, c->stream, c->xsq_part, nb, c->x_sq);
     MCL_CHECK_HIP(c, hipGetLastError());
     return 0;

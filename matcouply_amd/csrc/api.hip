@@ -480,7 +480,15 @@ void mcl_destroy(mcl_context *ctx) {
 }
 
 int mcl_set_problem(mcl_context *c, const float *X, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank) {
+    return mcl_set_problem_typed(c, X, MCL_X_F32, row_ptr, I, K, rank);
+}
+
+int mcl_set_problem_typed(mcl_context *c, const void *X, int32_t x_type, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank) {
     if (!c) return 1;
+    if (x_type != MCL_X_F32 && x_type != MCL_X_BF16 && x_type != MCL_X_F16)
+        return fail(c, "mcl_set_problem_typed: unknown x_type " + std::to_string(x_type) + " (MCL_X_F32 = 0, MCL_X_BF16 = 1, MCL_X_F16 = 2)");
+    if (x_type != MCL_X_F32 && (reinterpret_cast<uintptr_t>(X) & 7) != 0)
+        return fail(c, "mcl_set_problem_typed: a 16-bit X must be 8-byte aligned");
     if (I < 0 || K < 1) return fail(c, "mcl_set_problem: need I >= 0 and K >= 1");
     if (rank < 1 || rank > MCL_MAX_RANK) return fail(c, "mcl_set_problem: rank must be in [1, 64]");
     if (int rc = settle_deferred(c)) return rc;
@@ -492,6 +500,7 @@ int mcl_set_problem(mcl_context *c, const float *X, const int64_t *row_ptr, int6
     if (N >= (int64_t(1) << 31) - 64) return fail(c, "mcl_set_problem: more than 2^31 packed rows are not supported");
     if (N > 0 && !X) return fail(c, "mcl_set_problem: X is NULL");
     c->X = X;
+    c->x_type = x_type;
     c->row_ptr.assign(row_ptr, row_ptr + I + 1);
     c->I = I, c->K = K, c->N = N, c->r = rank;
     c->max_slab_rows = 0;

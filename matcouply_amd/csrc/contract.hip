@@ -15,6 +15,7 @@
 #include <type_traits>
 
 #include "mcl_internal.h"
+#include "xload.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef double f64x4 __attribute__((ext_vector_type(4)));
@@ -38,13 +39,8 @@ static __device__ __forceinline__ f32x4 zero4() { return f32x4{0.f, 0.f, 0.f, 0.
 // ---------------------------------------------------------------------------------------------------------
 // MODE 0: R slice of blockIdx.y, and G in the blocks with blockIdx.y == 0.  Rank > 32 (NB = 4) has no registers for both
 // accumulator sets with their fp64 shadows: MODE 1 (R only) and MODE 2 (G only, one launch with gridDim.y = 1, X untouched).
-template <int KB, int NB, int VEC, int DEPTH, int MODE, bool XNT = false>  // XNT: non-temporal loads of X (X >> last-level cache)
-__global__ __launch_bounds__(256) void k_contract_xt(const float *__restrict__ X, const float *__restrict__ B,
-                                                     const float *__restrict__ A, const int *__restrict__ seg_slab,
-                                                     const int *__restrict__ seg_row0, const int *__restrict__ seg_rows,
-                                                     const int *__restrict__ wave_seg_ptr, int n_waves, int K, int r,
-                                                     double *__restrict__ part, int part_stride, int dbg, int n_slices,
-                                                     int n_rowblocks) {
+template <class XL, int KB, int NB, int VEC, int DEPTH, int MODE, bool XNT>
+static __device__ __forceinline__ void k_contract_xt_body(const typename XL::T *X, const float *B, const float *A, const int *seg_slab, const int *seg_row0, const int *seg_rows, const int *wave_seg_ptr, int n_waves, int K, int r, double *part, int part_stride, int dbg, int n_slices, int n_rowblocks) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int rsub = lane >> 4, c16 = lane & 15;
     // XCD-aware mapping (round 3).  The K-slices of one row range all need the same rows of B (and a_i); with the row
@@ -134,20 +130,19 @@ __global__ __launch_bounds__(256) void k_contract_xt(const float *__restrict__ X
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb) a_val[nb] = bok[nb] ? A[(long)slab * r + bcol[nb]] : 0.f;
 
-        f32x4 fx[DEPTH][KB];
+        xraw_t<XL, VEC == 4> fx[DEPTH][KB];
         float fb[DEPTH][NB], fa[DEPTH][NB];
         auto load = [&](int d, int g) {
             const int rl = 4 * g + rsub;
             const long j = row0 + min(rl, nrows - 1);
 #pragma unroll
             for (int kb = 0; kb < (DO_R ? KB : 0); ++kb) {
-                if (VEC == 4) {
-                    fx[d][kb] = XNT ? __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(X + j * K + kcol[kb]))
-                                    : *reinterpret_cast<const f32x4 *>(X + j * K + kcol[kb]);
+                if constexpr (VEC == 4) {
+                    fx[d][kb] = XL::template ld4<XNT>(X + j * K + kcol[kb]);
                 } else {
                     f32x4 v;
 #pragma unroll
-                    for (int m = 0; m < 4; ++m) v[m] = X[j * K + min(kcol[kb] + m, K - 1)];
+                    for (int m = 0; m < 4; ++m) v[m] = XL::ld1(X + j * K + min(kcol[kb] + m, K - 1));
                     fx[d][kb] = v;
                 }
             }
@@ -170,7 +165,7 @@ __global__ __launch_bounds__(256) void k_contract_xt(const float *__restrict__ X
                 // MFMAs and the counted vmcnt waits drop from 12..15 to 8..12: 6 % slower at K = 1024, measured)
                 if (DO_R && (dbg & 1)) {  // timing experiment: loads only
 #pragma unroll
-                    for (int kb = 0; kb < KB; ++kb) acc[kb][0][0] += fx[d][kb] * ba[0];
+                    for (int kb = 0; kb < KB; ++kb) acc[kb][0][0] += xcvt<XL, VEC == 4>(fx[d][kb]) * ba[0];
                     load(d, g + DEPTH + d);
                     continue;
                 }
@@ -180,7 +175,7 @@ __global__ __launch_bounds__(256) void k_contract_xt(const float *__restrict__ X
 #pragma unroll
                         for (int m = 0; m < 4; ++m)
 #pragma unroll
-                            for (int nb = 0; nb < NB; ++nb) acc[kb][m][nb] = MFMA16(fx[d][kb][m], ba[nb], acc[kb][m][nb]);
+                            for (int nb = 0; nb < NB; ++nb) acc[kb][m][nb] = MFMA16((xcvt<XL, VEC == 4>(fx[d][kb])[m]), ba[nb], acc[kb][m][nb]);
                 }
                 if (MODE != 1 && doG) {
 #pragma unroll
@@ -240,6 +235,25 @@ __global__ __launch_bounds__(256) void k_contract_xt(const float *__restrict__ X
         }
     }
 }
+template <int KB, int NB, int VEC, int DEPTH, int MODE, bool XNT = false>  // XNT: non-temporal loads of X (X >> last-level cache)
+__global__ __launch_bounds__(256) void k_contract_xt(const float *__restrict__ X, const float *__restrict__ B,
+                                                     const float *__restrict__ A, const int *__restrict__ seg_slab,
+                                                     const int *__restrict__ seg_row0, const int *__restrict__ seg_rows,
+                                                     const int *__restrict__ wave_seg_ptr, int n_waves, int K, int r,
+                                                     double *__restrict__ part, int part_stride, int dbg, int n_slices,
+                                                     int n_rowblocks) {
+    k_contract_xt_body<XF32, KB, NB, VEC, DEPTH, MODE, XNT>(X, B, A, seg_slab, seg_row0, seg_rows, wave_seg_ptr, n_waves, K, r, part, part_stride, dbg, n_slices, n_rowblocks);
+}
+// the 16-bit twin (xload.h): the same template arguments after the element type
+template <class XL, int KB, int NB, int VEC, int DEPTH, int MODE, bool XNT = false>
+__global__ __launch_bounds__(256) void k_contract_xt_h(const typename XL::T *__restrict__ X, const float *__restrict__ B,
+                                                     const float *__restrict__ A, const int *__restrict__ seg_slab,
+                                                     const int *__restrict__ seg_row0, const int *__restrict__ seg_rows,
+                                                     const int *__restrict__ wave_seg_ptr, int n_waves, int K, int r,
+                                                     double *__restrict__ part, int part_stride, int dbg, int n_slices,
+                                                     int n_rowblocks) {
+    k_contract_xt_body<XL, KB, NB, VEC, DEPTH, MODE, XNT>(X, B, A, seg_slab, seg_row0, seg_rows, wave_seg_ptr, n_waves, K, r, part, part_stride, dbg, n_slices, n_rowblocks);
+}
 
 // GR[e] = sum_p part[p][e]; fixed summation order (deterministic, identical on every rank for identical input)
 __global__ __launch_bounds__(256) void k_reduce_partials(const double *__restrict__ part, int n_part, int E,
@@ -295,10 +309,8 @@ __global__ void k_build_cfrag(const float *__restrict__ C, int K, int r, int KC,
 // KCT in {2, 4}: K <= 64*KCT, C fragments live in registers.  KCT == 0: runtime chunk count (multiple of 4, the
 // host pads Cfrag with zeros), fragments re-read from the L1/L2-resident Cfrag buffer each chunk.
 // ---------------------------------------------------------------------------------------------------------
-template <int NB, int VEC, int KCT>
-__global__ __launch_bounds__(256) void k_contract_xc(const float *__restrict__ X, const float *__restrict__ Cfrag,
-                                                     float *__restrict__ XC, long N, int K, int r, int KCrt,
-                                                     long blocks_per_wave, long n_blocks16, int dbg) {
+template <class XL, int NB, int VEC, int KCT>
+static __device__ __forceinline__ void k_contract_xc_body(const typename XL::T *X, const float *Cfrag, float *XC, long N, int K, int r, int KCrt, long blocks_per_wave, long n_blocks16, int dbg) {
     __shared__ float lds_all[4][16 * 64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int q = lane >> 4, i16 = lane & 15;
@@ -323,7 +335,7 @@ __global__ __launch_bounds__(256) void k_contract_xc(const float *__restrict__ X
                         *reinterpret_cast<const f32x4 *>(Cfrag + ((((long)kc * 4 + kq) * NB + nb) * 64 + lane) * 4);
     }
 
-    f32x4 xr[4][4];
+    xraw_t<XL, VEC == 4> xr[4][4];
     // stage the 16 x 64 chunk (blk, kc) into ring slot `slot`
     auto issue = [&](int slot, long blk, int kc) {
         const long bc = min(blk, b1 - 1);
@@ -332,12 +344,12 @@ __global__ __launch_bounds__(256) void k_contract_xc(const float *__restrict__ X
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             const long j = min(bc * 16 + 4 * t + q, N - 1);
-            if (VEC == 4) {
-                xr[slot][t] = *reinterpret_cast<const f32x4 *>(X + j * K + col);
+            if constexpr (VEC == 4) {
+                xr[slot][t] = XL::template ld4<false>(X + j * K + col);
             } else {
                 f32x4 v;
 #pragma unroll
-                for (int m = 0; m < 4; ++m) v[m] = X[j * K + min(col + m, K - 1)];
+                for (int m = 0; m < 4; ++m) v[m] = XL::ld1(X + j * K + min(col + m, K - 1));
                 xr[slot][t] = v;
             }
         }
@@ -351,12 +363,12 @@ __global__ __launch_bounds__(256) void k_contract_xc(const float *__restrict__ X
         f32x4 fr[4];
         if (dbg & 2) {  // timing experiment: no LDS staging (wrong results)
 #pragma unroll
-            for (int kq = 0; kq < 4; ++kq) fr[kq] = xr[slot][kq];
+            for (int kq = 0; kq < 4; ++kq) fr[kq] = xcvt<XL, VEC == 4>(xr[slot][kq]);
         } else {
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
                 const int row = 4 * t + q;
-                *reinterpret_cast<f32x4 *>(L + row * 64 + ((i16 ^ row) << 2)) = xr[slot][t];
+                *reinterpret_cast<f32x4 *>(L + row * 64 + ((i16 ^ row) << 2)) = xcvt<XL, VEC == 4>(xr[slot][t]);
             }
 #pragma unroll
             for (int kq = 0; kq < 4; ++kq)
@@ -427,6 +439,19 @@ __global__ __launch_bounds__(256) void k_contract_xc(const float *__restrict__ X
         }
     }
 }
+template <int NB, int VEC, int KCT>
+__global__ __launch_bounds__(256) void k_contract_xc(const float *__restrict__ X, const float *__restrict__ Cfrag,
+                                                     float *__restrict__ XC, long N, int K, int r, int KCrt,
+                                                     long blocks_per_wave, long n_blocks16, int dbg) {
+    k_contract_xc_body<XF32, NB, VEC, KCT>(X, Cfrag, XC, N, K, r, KCrt, blocks_per_wave, n_blocks16, dbg);
+}
+// the 16-bit twin (xload.h): the same template arguments after the element type
+template <class XL, int NB, int VEC, int KCT>
+__global__ __launch_bounds__(256) void k_contract_xc_h(const typename XL::T *__restrict__ X, const float *__restrict__ Cfrag,
+                                                     float *__restrict__ XC, long N, int K, int r, int KCrt,
+                                                     long blocks_per_wave, long n_blocks16, int dbg) {
+    k_contract_xc_body<XL, NB, VEC, KCT>(X, Cfrag, XC, N, K, r, KCrt, blocks_per_wave, n_blocks16, dbg);
+}
 
 // ---------------------------------------------------------------------------------------------------------
 // k_contract_xc_row : XC = X C for K % 256 == 0, optionally FUSED with the per-slab A-phase reductions.
@@ -443,13 +468,8 @@ __global__ __launch_bounds__(256) void k_contract_xc(const float *__restrict__ X
 // k_slab_gram pass (a 2 S_B re-read and a launch).
 // CREG: K == 256 and NB == 1: the 64 C-fragment registers stay resident.
 // ---------------------------------------------------------------------------------------------------------
-template <int NB, bool CREG, int GRAM, bool XNT = false>
-__global__ __launch_bounds__(256) void k_contract_xc_row(const float *__restrict__ X, const float *__restrict__ Cfrag,
-                                                         float *__restrict__ XC, const float *__restrict__ B,
-                                                         const int *__restrict__ seg_row0,
-                                                         const int *__restrict__ seg_rows,
-                                                         const int *__restrict__ wave_seg_ptr, int n_waves, int K, int r,
-                                                         double *__restrict__ seg_rhs, double *__restrict__ seg_btb) {
+template <class XL, int NB, bool CREG, int GRAM, bool XNT>
+static __device__ __forceinline__ void k_contract_xc_row_body(const typename XL::T *X, const float *Cfrag, float *XC, const float *B, const int *seg_row0, const int *seg_rows, const int *wave_seg_ptr, int n_waves, int K, int r, double *seg_rhs, double *seg_btb) {
     extern __shared__ float lds_dyn[];  // 4 waves x 16 rows x 256 floats
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int q = lane >> 4, i16 = lane & 15;
@@ -474,7 +494,7 @@ __global__ __launch_bounds__(256) void k_contract_xc_row(const float *__restrict
                         *reinterpret_cast<const f32x4 *>(Cfrag + ((((long)kc * 4 + kq) * NB + nb) * 64 + lane) * 4);
     }
 
-    f32x4 xr[16];
+    typename XL::raw xr[16];
     float bnx[NB][4];  // B block (rows 4q+v, column 16nb+i16) of the block whose X loads are in flight
     int bcolc[NB];
 #pragma unroll
@@ -484,8 +504,7 @@ __global__ __launch_bounds__(256) void k_contract_xc_row(const float *__restrict
 #pragma unroll
         for (int t = 0; t < 16; ++t) {
             const long j = row0 + min(16 * blk + t, nrows - 1);
-            xr[t] = XNT ? __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(X + j * K + 256 * sc + 4 * lane))
-                        : *reinterpret_cast<const f32x4 *>(X + j * K + 256 * sc + 4 * lane);
+            xr[t] = XL::template ld4<XNT>(X + j * K + 256 * sc + 4 * lane);
         }
         if (GRAM && sc == 0) {  // unconditional clamped loads; masked at use
 #pragma unroll
@@ -561,7 +580,7 @@ __global__ __launch_bounds__(256) void k_contract_xc_row(const float *__restrict
                 }
                 // registers -> LDS: row t, logical 16-B slot = lane, physical slot = lane ^ t
 #pragma unroll
-                for (int t = 0; t < 16; ++t) *reinterpret_cast<f32x4 *>(L + t * 256 + ((lane ^ t) << 2)) = xr[t];
+                for (int t = 0; t < 16; ++t) *reinterpret_cast<f32x4 *>(L + t * 256 + ((lane ^ t) << 2)) = XL::cvt(xr[t]);
                 // prefetch the next super-chunk (possibly the first one of the next segment)
                 if (sc + 1 < SC) issue(row0, nrows, blk, sc + 1);
                 else if (blk + 1 < nblk) issue(row0, nrows, blk + 1, 0);
@@ -658,6 +677,25 @@ __global__ __launch_bounds__(256) void k_contract_xc_row(const float *__restrict
         nrows = nnrows;
     }
 }
+template <int NB, bool CREG, int GRAM, bool XNT = false>
+__global__ __launch_bounds__(256) void k_contract_xc_row(const float *__restrict__ X, const float *__restrict__ Cfrag,
+                                                         float *__restrict__ XC, const float *__restrict__ B,
+                                                         const int *__restrict__ seg_row0,
+                                                         const int *__restrict__ seg_rows,
+                                                         const int *__restrict__ wave_seg_ptr, int n_waves, int K, int r,
+                                                         double *__restrict__ seg_rhs, double *__restrict__ seg_btb) {
+    k_contract_xc_row_body<XF32, NB, CREG, GRAM, XNT>(X, Cfrag, XC, B, seg_row0, seg_rows, wave_seg_ptr, n_waves, K, r, seg_rhs, seg_btb);
+}
+// the 16-bit twin (xload.h): the same template arguments after the element type
+template <class XL, int NB, bool CREG, int GRAM, bool XNT = false>
+__global__ __launch_bounds__(256) void k_contract_xc_row_h(const typename XL::T *__restrict__ X, const float *__restrict__ Cfrag,
+                                                         float *__restrict__ XC, const float *__restrict__ B,
+                                                         const int *__restrict__ seg_row0,
+                                                         const int *__restrict__ seg_rows,
+                                                         const int *__restrict__ wave_seg_ptr, int n_waves, int K, int r,
+                                                         double *__restrict__ seg_rhs, double *__restrict__ seg_btb) {
+    k_contract_xc_row_body<XL, NB, CREG, GRAM, XNT>(X, Cfrag, XC, B, seg_row0, seg_rows, wave_seg_ptr, n_waves, K, r, seg_rhs, seg_btb);
+}
 
 // ---------------------------------------------------------------------------------------------------------
 // k_contract_xc_256 : the K = 256, rank <= 16 case of k_contract_xc_row (C fragments resident in 64 registers) with TWO
@@ -668,14 +706,8 @@ __global__ __launch_bounds__(256) void k_contract_xc_row(const float *__restrict
 // The flat walk: `cur` is the block being multiplied, `pre` the one being requested (two blocks ahead); past the wave's last
 // block `pre` keeps pointing at the last valid rows (unconditional clamped loads, nothing stored).
 // ---------------------------------------------------------------------------------------------------------
-template <int GRAM, int D, bool XNT = false>
-__global__ __launch_bounds__(256) void k_contract_xc_256(const float *__restrict__ X, const float *__restrict__ Cfrag,
-                                                         float *__restrict__ XC, const float *__restrict__ B,
-                                                         const int *__restrict__ seg_row0,
-                                                         const int *__restrict__ seg_rows,
-                                                         const int *__restrict__ wave_seg_ptr, int n_waves, int r,
-                                                         double *__restrict__ seg_rhs,
-                                                         double *__restrict__ seg_btb) {
+template <class XL, int GRAM, int D, bool XNT>
+static __device__ __forceinline__ void k_contract_xc_256_body(const typename XL::T *X, const float *Cfrag, float *XC, const float *B, const int *seg_row0, const int *seg_rows, const int *wave_seg_ptr, int n_waves, int r, double *seg_rhs, double *seg_btb) {
     extern __shared__ float lds_dyn[];  // 4 waves x 16 rows x 256 floats
     constexpr int K = 256;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -716,15 +748,14 @@ __global__ __launch_bounds__(256) void k_contract_xc_256(const float *__restrict
     int total = 0;
     for (int sg = s0; sg < s1; ++sg) total += (__builtin_amdgcn_readfirstlane(seg_rows[sg]) + 15) >> 4;
 
-    f32x4 xr[D][16];
+    typename XL::raw xr[D][16];
     float bnx[D][4];
     auto issue = [&](auto dc, const Cursor &c) {
         constexpr int d = decltype(dc)::value;
 #pragma unroll
         for (int t = 0; t < 16; ++t) {
             const long j = c.row0 + min(16 * c.blk + t, c.nrows - 1);
-            xr[d][t] = XNT ? __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(X + j * K + 4 * lane))
-                           : *reinterpret_cast<const f32x4 *>(X + j * K + 4 * lane);
+            xr[d][t] = XL::template ld4<XNT>(X + j * K + 4 * lane);
         }
         if (GRAM) {
 #pragma unroll
@@ -764,7 +795,7 @@ __global__ __launch_bounds__(256) void k_contract_xc_256(const float *__restrict
             for (int v = 0; v < 4; ++v) bcur[v] = bnx[d][v];
         }
 #pragma unroll
-        for (int t = 0; t < 16; ++t) *reinterpret_cast<f32x4 *>(L + t * 256 + ((lane ^ t) << 2)) = xr[d][t];
+        for (int t = 0; t < 16; ++t) *reinterpret_cast<f32x4 *>(L + t * 256 + ((lane ^ t) << 2)) = XL::cvt(xr[d][t]);
         issue(dc, pre);  // the slot is free again: its next block (two ahead) goes out now
         advance(pre);
         // EIGHT fp32 accumulation chains per output (32 columns = 8 MFMAs each; round 2: four of 16), summed as a tree in
@@ -832,6 +863,27 @@ __global__ __launch_bounds__(256) void k_contract_xc_256(const float *__restrict
         if (D > 1) body(std::integral_constant<int, (D > 1 ? 1 : 0)>{}, b + 1 < total);
         if (D > 2) body(std::integral_constant<int, (D > 2 ? 2 : 0)>{}, b + 2 < total);
     }
+}
+template <int GRAM, int D, bool XNT = false>
+__global__ __launch_bounds__(256) void k_contract_xc_256(const float *__restrict__ X, const float *__restrict__ Cfrag,
+                                                         float *__restrict__ XC, const float *__restrict__ B,
+                                                         const int *__restrict__ seg_row0,
+                                                         const int *__restrict__ seg_rows,
+                                                         const int *__restrict__ wave_seg_ptr, int n_waves, int r,
+                                                         double *__restrict__ seg_rhs,
+                                                         double *__restrict__ seg_btb) {
+    k_contract_xc_256_body<XF32, GRAM, D, XNT>(X, Cfrag, XC, B, seg_row0, seg_rows, wave_seg_ptr, n_waves, r, seg_rhs, seg_btb);
+}
+// the 16-bit twin (xload.h): the same template arguments after the element type
+template <class XL, int GRAM, int D, bool XNT = false>
+__global__ __launch_bounds__(256) void k_contract_xc_256_h(const typename XL::T *__restrict__ X, const float *__restrict__ Cfrag,
+                                                         float *__restrict__ XC, const float *__restrict__ B,
+                                                         const int *__restrict__ seg_row0,
+                                                         const int *__restrict__ seg_rows,
+                                                         const int *__restrict__ wave_seg_ptr, int n_waves, int r,
+                                                         double *__restrict__ seg_rhs,
+                                                         double *__restrict__ seg_btb) {
+    k_contract_xc_256_body<XL, GRAM, D, XNT>(X, Cfrag, XC, B, seg_row0, seg_rows, wave_seg_ptr, n_waves, r, seg_rhs, seg_btb);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -928,7 +980,7 @@ static inline int xt_KB(const mcl_context *c) {
 // measured best, one 256-thread block per CU)
 int mcl_contract_n_partials(const mcl_context *c) { return std::max(1, (c->n_seg_waves + 3) / 4); }
 
-template <int KB, int NB>
+template <class XL, int KB, int NB>
 static int launch_xt(mcl_context *c) {
     const int nb = mcl_contract_n_partials(c);
     const int E = (int)(c->K * c->r + c->r * c->r);
@@ -939,14 +991,14 @@ static int launch_xt(mcl_context *c) {
     }
     const int n_slices = (int)((c->K + 64 * KB - 1) / (64 * KB));
     dim3 grid((unsigned)(((nb + 7) / 8) * 8 * n_slices));  // 1-D: (row range mod 8 = XCD, slice, row range div 8), see the kernel
-    const bool vec = (c->K % 4 == 0) && ((reinterpret_cast<uintptr_t>(c->X) & 15) == 0);
+    const bool vec = (c->K % 4 == 0) && mcl_x_vec_aligned(c);
     ProfScope prof(c, MCL_PROF_XT);
     int dbg = 0, depth = 4;
     dbg = c->sw.xt_dbg;
     if (c->sw.xt_depth > 0) depth = c->sw.xt_depth;
     constexpr int RMODE = (NB == 4) ? 1 : 0;
 #define MCL_XT_(VEC_, DEPTH_, MODE_, GRID_, NT_)                                                                      \
-    hipLaunchKernelGGL((k_contract_xt<KB, NB, VEC_, DEPTH_, MODE_, NT_>), GRID_, dim3(256), 0, c->stream, c->X, c->B, c->A, \
+    hipLaunchKernelGGL((MCL_XKERNEL(k_contract_xt, KB, NB, VEC_, DEPTH_, MODE_, NT_)), GRID_, dim3(256), 0, c->stream, mcl_x<XL>(c), c->B, c->A, \
                        c->segs.slab, c->segs.row0, c->segs.nrows, c->wave_seg_ptr, c->n_seg_waves, (int)c->K, c->r, c->partials, \
                        E, dbg, ((GRID_).x / (((nb + 7) / 8) * 8)), nb)
 #define MCL_XT(VEC_, DEPTH_, MODE_, GRID_)                                                                            \
@@ -965,7 +1017,7 @@ static int launch_xt(mcl_context *c) {
 #undef MCL_XT_
     c->n_part = nb;
     char buf[96];
-    snprintf(buf, sizeof buf, "k_contract_xt<KB=%d,NB=%d,VEC=%d>", KB, NB, vec ? 4 : 1);
+    snprintf(buf, sizeof buf, "k_contract_xt%s<%sKB=%d,NB=%d,VEC=%d>", mcl_x_kname<XL>(), mcl_x_targ<XL>(), KB, NB, vec ? 4 : 1);
     c->variant[MCL_PROF_XT] = buf;
     MCL_CHECK_HIP(c, hipGetLastError());
     return 0;
@@ -973,17 +1025,20 @@ static int launch_xt(mcl_context *c) {
 
 int mcl_launch_contract_xt(mcl_context *c) {
     const int KB = xt_KB(c);
-    switch (c->NB) {
-        case 1:
-            if (KB == 4) return launch_xt<4, 1>(c);
-            if (KB == 2) return launch_xt<2, 1>(c);
-            return launch_xt<1, 1>(c);
-        case 2:
-            if (KB >= 2) return launch_xt<2, 2>(c);
-            return launch_xt<1, 2>(c);
-        default:
-            return launch_xt<1, 4>(c);
-    }
+    return mcl_x_dispatch(c->x_type, [&](auto xl) {
+        using XL = decltype(xl);
+        switch (c->NB) {
+            case 1:
+                if (KB == 4) return launch_xt<XL, 4, 1>(c);
+                if (KB == 2) return launch_xt<XL, 2, 1>(c);
+                return launch_xt<XL, 1, 1>(c);
+            case 2:
+                if (KB >= 2) return launch_xt<XL, 2, 2>(c);
+                return launch_xt<XL, 1, 2>(c);
+            default:
+                return launch_xt<XL, 1, 4>(c);
+        }
+    });
 }
 
 int mcl_launch_reduce_partials(mcl_context *c) {
@@ -1008,7 +1063,7 @@ int mcl_launch_build_cfrag(mcl_context *c) {
     return 0;
 }
 
-template <int NB>
+template <class XL, int NB>
 static int launch_xc(mcl_context *c) {
     const int KC = xc_KC(c);
     const long nblk = (c->N + 15) / 16;
@@ -1021,7 +1076,7 @@ static int launch_xc(mcl_context *c) {
     const long waves = (nblk + bpw - 1) / bpw;
     const unsigned grid = (unsigned)((waves + 3) / 4);
     if (grid == 0) return 0;
-    const bool vec = (c->K % 4 == 0) && ((reinterpret_cast<uintptr_t>(c->X) & 15) == 0);
+    const bool vec = (c->K % 4 == 0) && mcl_x_vec_aligned(c);
     ProfScope prof(c, MCL_PROF_XC);
     int kct = 0;
     mcl_xc_chunks(c, &kct);
@@ -1034,7 +1089,7 @@ static int launch_xc(mcl_context *c) {
         int gram = !c->xc_with_gram ? 0 : (c->regs[0].n == 0 ? 2 : 1);
         if (NB == 4 && gram == 2) gram = 0;  // rank > 32 has no registers for the fp64 Gram tiles: k_slab_gram follows
 #define MCL_XCR_(CREG_, GRAM_, NT_)                                                                                  \
-    hipLaunchKernelGGL((k_contract_xc_row<NB, CREG_, GRAM_, NT_>), dim3(g), dim3(256), sm, c->stream, c->X, c->Cfrag, \
+    hipLaunchKernelGGL((MCL_XKERNEL(k_contract_xc_row, NB, CREG_, GRAM_, NT_)), dim3(g), dim3(256), sm, c->stream, mcl_x<XL>(c), c->Cfrag, \
                        c->XC, c->B, c->segs.row0, c->segs.nrows, c->wave_seg_ptr, c->n_seg_waves, (int)c->K, c->r, c->seg_rhs, \
                        c->seg_btb)
 #define MCL_XCR(CREG_, GRAM_)                                                                                        \
@@ -1046,7 +1101,7 @@ static int launch_xc(mcl_context *c) {
             // K % 512 == 0 with the fragment image of C resident in LDS and four X tiles in flight per wave (xclds.hip)
             c->xc_did_gram = gram != 0;
             char bufl[96];
-            snprintf(bufl, sizeof bufl, "k_contract_xc_lds<NB=%d,GRAM=%d>", NB, gram);
+            snprintf(bufl, sizeof bufl, "k_contract_xc_lds%s<%sNB=%d,GRAM=%d>", mcl_x_kname<XL>(), mcl_x_targ<XL>(), NB, gram);
             c->variant[MCL_PROF_XC] = bufl;
             MCL_CHECK_HIP(c, hipGetLastError());
             return 0;
@@ -1055,7 +1110,7 @@ static int launch_xc(mcl_context *c) {
             if constexpr (NB == 1) {  // resident C fragments: K = 256, rank <= 16 only
                 if (creg && !c->sw.xc_depth1) {  // two blocks of X in flight per wave
 #define MCL_XC256_(GRAM_, NT_)                                                                                        \
-    hipLaunchKernelGGL((k_contract_xc_256<GRAM_, 2, NT_>), dim3(g), dim3(256), sm, c->stream, c->X, c->Cfrag, c->XC, c->B, \
+    hipLaunchKernelGGL((MCL_XKERNEL(k_contract_xc_256, GRAM_, 2, NT_)), dim3(g), dim3(256), sm, c->stream, mcl_x<XL>(c), c->Cfrag, c->XC, c->B, \
                        c->segs.row0, c->segs.nrows, c->wave_seg_ptr, c->n_seg_waves, c->r, c->seg_rhs, c->seg_btb)
 #define MCL_XC256(GRAM_)                                                                                              \
     do {                                                                                                              \
@@ -1087,15 +1142,17 @@ static int launch_xc(mcl_context *c) {
 #undef MCL_XCR_
         c->xc_did_gram = gram != 0;
         char buf[96];
-        if (creg && !c->sw.xc_depth1) snprintf(buf, sizeof buf, "k_contract_xc_256<DEPTH=2,GRAM=%d>", gram);
-        else snprintf(buf, sizeof buf, "k_contract_xc_row<NB=%d,CREG=%d,GRAM=%d>", NB, creg ? 1 : 0, gram);
+        if (creg && !c->sw.xc_depth1)
+            snprintf(buf, sizeof buf, "k_contract_xc_256%s<%sDEPTH=2,GRAM=%d>", mcl_x_kname<XL>(), mcl_x_targ<XL>(), gram);
+        else
+            snprintf(buf, sizeof buf, "k_contract_xc_row%s<%sNB=%d,CREG=%d,GRAM=%d>", mcl_x_kname<XL>(), mcl_x_targ<XL>(), NB, creg ? 1 : 0, gram);
         c->variant[MCL_PROF_XC] = buf;
         MCL_CHECK_HIP(c, hipGetLastError());
         return 0;
     }
     c->xc_did_gram = false;
 #define MCL_XC(NB_, VEC_, KCT_)                                                                                     \
-    hipLaunchKernelGGL((k_contract_xc<NB_, VEC_, KCT_>), dim3(grid), dim3(256), 0, c->stream, c->X, c->Cfrag, c->XC, \
+    hipLaunchKernelGGL((MCL_XKERNEL(k_contract_xc, NB_, VEC_, KCT_)), dim3(grid), dim3(256), 0, c->stream, mcl_x<XL>(c), c->Cfrag, c->XC, \
                        (long)c->N, (int)c->K, c->r, KC, bpw, nblk, dbg)
     if (vec) {
         if (kct == 4) MCL_XC(NB, 4, 4);
@@ -1108,16 +1165,19 @@ static int launch_xc(mcl_context *c) {
     }
 #undef MCL_XC
     char buf[96];
-    snprintf(buf, sizeof buf, "k_contract_xc<NB=%d,VEC=%d,KCT=%d>", NB, vec ? 4 : 1, kct);
+    snprintf(buf, sizeof buf, "k_contract_xc%s<%sNB=%d,VEC=%d,KCT=%d>", mcl_x_kname<XL>(), mcl_x_targ<XL>(), NB, vec ? 4 : 1, kct);
     c->variant[MCL_PROF_XC] = buf;
     MCL_CHECK_HIP(c, hipGetLastError());
     return 0;
 }
 
 int mcl_launch_contract_xc(mcl_context *c) {
-    if (c->NB == 1) return launch_xc<1>(c);
-    if (c->NB == 2) return launch_xc<2>(c);
-    return launch_xc<4>(c);
+    return mcl_x_dispatch(c->x_type, [&](auto xl) {
+        using XL = decltype(xl);
+        if (c->NB == 1) return launch_xc<XL, 1>(c);
+        if (c->NB == 2) return launch_xc<XL, 2>(c);
+        return launch_xc<XL, 4>(c);
+    });
 }
 
 int mcl_launch_slab_gram(mcl_context *c) {
@@ -1172,10 +1232,8 @@ bool mcl_exact_mode(const mcl_context *c) {
 // B[kk][j = i] = (b a)[row + kk][16 nb + i]; (b a) is an exact product of two fp32 values, the MFMA rounds each fp64 multiply-add
 // once.  D: lane l, register v = D[(l >> 4) + 4 v][l & 15].  Every output is a sum over the rows in ascending order
 // (k_exact_gr_reduce adds the chunks in ascending order): deterministic, and the same on every rank layout of the same rows.
-template <int NB>
-__global__ __launch_bounds__(64) void k_exact_gr(const float *__restrict__ X, const float *__restrict__ B,
-                                                 const float *__restrict__ A, const int *__restrict__ slab_of_row, long N, int K,
-                                                 int r, double *__restrict__ part) {
+template <class XL, int NB>
+static __device__ __forceinline__ void k_exact_gr_body(const typename XL::T *X, const float *B, const float *A, const int *slab_of_row, long N, int K, int r, double *part) {
     const int lane = threadIdx.x, i = lane & 15, kk = lane >> 4;
     const int kblocks = (K + 15) / 16;
     const long c0 = (long)blockIdx.y * 256, c1 = min(c0 + 256, N);
@@ -1200,7 +1258,7 @@ __global__ __launch_bounds__(64) void k_exact_gr(const float *__restrict__ X, co
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const long row = g + 4 * u + kk;
-                x[u] = (double)X[min(row, c1 - 1) * K + min(k, K - 1)] * ((row < c1 && k < K) ? 1.0 : 0.0);
+                x[u] = (double)XL::ld1(X + min(row, c1 - 1) * K + min(k, K - 1)) * ((row < c1 && k < K) ? 1.0 : 0.0);
 #pragma unroll
                 for (int nb = 0; nb < NB; ++nb) w[u][nb] = ba(row, 16 * nb + i);
             }
@@ -1247,6 +1305,19 @@ __global__ __launch_bounds__(64) void k_exact_gr(const float *__restrict__ X, co
                 }
     }
 }
+template <int NB>
+__global__ __launch_bounds__(64) void k_exact_gr(const float *__restrict__ X, const float *__restrict__ B,
+                                                 const float *__restrict__ A, const int *__restrict__ slab_of_row, long N, int K,
+                                                 int r, double *__restrict__ part) {
+    k_exact_gr_body<XF32, NB>(X, B, A, slab_of_row, N, K, r, part);
+}
+// the 16-bit twin (xload.h): the same template arguments after the element type
+template <class XL, int NB>
+__global__ __launch_bounds__(64) void k_exact_gr_h(const typename XL::T *__restrict__ X, const float *__restrict__ B,
+                                                 const float *__restrict__ A, const int *__restrict__ slab_of_row, long N, int K,
+                                                 int r, double *__restrict__ part) {
+    k_exact_gr_body<XL, NB>(X, B, A, slab_of_row, N, K, r, part);
+}
 
 __global__ __launch_bounds__(256) void k_exact_gr_reduce(const double *__restrict__ part, int n_chunks, long E,
                                                          double *__restrict__ GR) {
@@ -1273,13 +1344,19 @@ int mcl_launch_exact_gr(mcl_context *c) {
     const dim3 grid((unsigned)(kblocks + 1), (unsigned)n_chunks);
     double *part = n_chunks == 1 ? c->GR : c->exact_part;  // one chunk (<= 256 rows): its sums ARE [G | R], no second launch
     ProfScope prof(c, MCL_PROF_XT);  // the exact-products form of the X^T pass (and its reduction)
-    c->variant[MCL_PROF_XT] = "k_exact_gr (+ k_exact_gr_reduce)";
-    if (c->NB == 1)
-        hipLaunchKernelGGL(k_exact_gr<1>, grid, dim3(64), 0, c->stream, c->X, c->B, c->A, c->slab_of_row, (long)c->N, (int)c->K, c->r, part);
-    else if (c->NB == 2)
-        hipLaunchKernelGGL(k_exact_gr<2>, grid, dim3(64), 0, c->stream, c->X, c->B, c->A, c->slab_of_row, (long)c->N, (int)c->K, c->r, part);
-    else
-        hipLaunchKernelGGL(k_exact_gr<4>, grid, dim3(64), 0, c->stream, c->X, c->B, c->A, c->slab_of_row, (long)c->N, (int)c->K, c->r, part);
+    mcl_x_dispatch(c->x_type, [&](auto xl) {
+        using XL = decltype(xl);
+        c->variant[MCL_PROF_XT] = std::string("k_exact_gr") + mcl_x_kname<XL>() + (std::is_same_v<XL, XF32> ? "" : std::string("<") +
+                                  XL::name + ">") + " (+ k_exact_gr_reduce)";
+        const typename XL::T *X = mcl_x<XL>(c);
+        if (c->NB == 1)
+            hipLaunchKernelGGL((MCL_XKERNEL(k_exact_gr, 1)), grid, dim3(64), 0, c->stream, X, c->B, c->A, c->slab_of_row, (long)c->N, (int)c->K, c->r, part);
+        else if (c->NB == 2)
+            hipLaunchKernelGGL((MCL_XKERNEL(k_exact_gr, 2)), grid, dim3(64), 0, c->stream, X, c->B, c->A, c->slab_of_row, (long)c->N, (int)c->K, c->r, part);
+        else
+            hipLaunchKernelGGL((MCL_XKERNEL(k_exact_gr, 4)), grid, dim3(64), 0, c->stream, X, c->B, c->A, c->slab_of_row, (long)c->N, (int)c->K, c->r, part);
+        return 0;
+    });
     if (n_chunks > 1)
         hipLaunchKernelGGL(k_exact_gr_reduce, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, c->stream, c->exact_part, n_chunks, E, c->GR);
     MCL_CHECK_HIP(c, hipGetLastError());

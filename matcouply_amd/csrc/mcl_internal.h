@@ -102,7 +102,8 @@ struct mcl_context {
     std::string failed_why;
 
     // problem
-    const float *X = nullptr;
+    const void *X = nullptr;  // x_type elements (MCL_X_*): launch sites reach it through mcl_x<XL>(c) (xload.h)
+    int x_type = 0;
     std::vector<int64_t> row_ptr;  // host
     int64_t I = 0, K = 0, N = 0;
     int64_t max_slab_rows = 0;  // longest matrix (rows)

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "mcl_internal.h"
+#include "xload.h"
 
 namespace {
 
@@ -29,8 +30,8 @@ static std::string g_svd_error;
 inline int svd_m(int64_t K, int rank) { return (int)std::min<int64_t>(K, rank + SVD_OVERSAMPLE); }
 
 // G_b = X_b^T X_b (fp64 sums of exact products of the stored fp32 values), 32 x 32 output tile per workgroup
-__global__ __launch_bounds__(256) void k_svd_gram(const float *__restrict__ X, const int *__restrict__ ext, int b0, int K,
-                                                  double *__restrict__ G) {
+template <class XL>
+static __device__ __forceinline__ void k_svd_gram_body(const typename XL::T *X, const int *ext, int b0, int K, double *G) {
     __shared__ float As[32][33], Bs[32][33];
     const int b = blockIdx.z, slab = b0 + b;
     const long s0 = ext[slab];
@@ -43,8 +44,8 @@ __global__ __launch_bounds__(256) void k_svd_gram(const float *__restrict__ X, c
         for (int e = threadIdx.x; e < 32 * 32; e += 256) {
             const int jj = e >> 5, cc = e & 31;
             const bool okj = j0 + jj < n;
-            As[jj][cc] = (okj && a0 + cc < K) ? X[(s0 + j0 + jj) * K + a0 + cc] : 0.f;
-            Bs[jj][cc] = (okj && c0 + cc < K) ? X[(s0 + j0 + jj) * K + c0 + cc] : 0.f;
+            As[jj][cc] = (okj && a0 + cc < K) ? XL::ld1(X + (s0 + j0 + jj) * K + a0 + cc) : 0.f;
+            Bs[jj][cc] = (okj && c0 + cc < K) ? XL::ld1(X + (s0 + j0 + jj) * K + c0 + cc) : 0.f;
         }
         __syncthreads();
 #pragma unroll 8
@@ -63,6 +64,16 @@ __global__ __launch_bounds__(256) void k_svd_gram(const float *__restrict__ X, c
             const int a = a0 + 2 * ty + u, c = c0 + 2 * tx + v;
             if (a < K && c < K) Gb[(long)a * K + c] = acc[u][v];
         }
+}
+__global__ __launch_bounds__(256) void k_svd_gram(const float *__restrict__ X, const int *__restrict__ ext, int b0, int K,
+                                                  double *__restrict__ G) {
+    k_svd_gram_body<XF32>(X, ext, b0, K, G);
+}
+// the 16-bit twin (xload.h): the same template arguments after the element type
+template <class XL>
+__global__ __launch_bounds__(256) void k_svd_gram_h(const typename XL::T *__restrict__ X, const int *__restrict__ ext, int b0, int K,
+                                                  double *__restrict__ G) {
+    k_svd_gram_body<XL>(X, ext, b0, K, G);
 }
 
 // Gstack += sum of the batch's Gram matrices, slabs in ascending order
@@ -248,9 +259,8 @@ __global__ __launch_bounds__(256) void k_svd_subspace(const double *__restrict__
 }
 
 // B_b = X_b V_b with unit columns, the entry of largest magnitude of every column positive (threshold: clipped at 0)
-__global__ __launch_bounds__(256) void k_svd_left(const float *__restrict__ X, const int *__restrict__ ext, int b0, int K, int m, int r,
-                                                  const double *__restrict__ Qall, double *__restrict__ Uws, long uws0, int threshold,
-                                                  float *__restrict__ B) {
+template <class XL>
+static __device__ __forceinline__ void k_svd_left_body(const typename XL::T *X, const int *ext, int b0, int K, int m, int r, const double *Qall, double *Uws, long uws0, int threshold, float *B) {
     __shared__ double red[256];
     __shared__ double red2[256];
     __shared__ double scale_sh[MCL_MAX_RANK];
@@ -263,7 +273,7 @@ __global__ __launch_bounds__(256) void k_svd_left(const float *__restrict__ X, c
         const long j = e / r;
         const int c = (int)(e - j * r);
         double s = 0.0;
-        for (int k = 0; k < K; ++k) s = fma((double)X[(s0 + j) * K + k], V[(long)k * m + c], s);
+        for (int k = 0; k < K; ++k) s = fma((double)XL::ld1(X + (s0 + j) * K + k), V[(long)k * m + c], s);
         U[e] = s;
     }
     __syncthreads();
@@ -303,6 +313,18 @@ __global__ __launch_bounds__(256) void k_svd_left(const float *__restrict__ X, c
         if (threshold) v = fmax(v, 0.0);
         B[(s0 + j) * r + c] = (float)v;
     }
+}
+__global__ __launch_bounds__(256) void k_svd_left(const float *__restrict__ X, const int *__restrict__ ext, int b0, int K, int m, int r,
+                                                  const double *__restrict__ Qall, double *__restrict__ Uws, long uws0, int threshold,
+                                                  float *__restrict__ B) {
+    k_svd_left_body<XF32>(X, ext, b0, K, m, r, Qall, Uws, uws0, threshold, B);
+}
+// the 16-bit twin (xload.h): the same template arguments after the element type
+template <class XL>
+__global__ __launch_bounds__(256) void k_svd_left_h(const typename XL::T *__restrict__ X, const int *__restrict__ ext, int b0, int K, int m, int r,
+                                                  const double *__restrict__ Qall, double *__restrict__ Uws, long uws0, int threshold,
+                                                  float *__restrict__ B) {
+    k_svd_left_body<XL>(X, ext, b0, K, m, r, Qall, Uws, uws0, threshold, B);
 }
 
 // C = the stack's Ritz vectors, the entry of largest magnitude of every column positive (threshold: clipped at 0)
@@ -371,8 +393,11 @@ int64_t mcl_svd_init_workspace_bytes(const int64_t *row_ptr, int64_t I, int64_t 
     return svd_plan(I, K, rank, max_batch_rows_of(row_ptr, I, p0.BS)).total;
 }
 
-int mcl_svd_init(const float *X, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank, int32_t threshold, float *B, float *C,
-                 void *workspace, int64_t workspace_bytes, int32_t *info, void *hip_stream) {
+}  // extern "C"
+
+template <class XL>
+static int svd_init(const typename XL::T *X, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank, int32_t threshold, float *B,
+                    float *C, void *workspace, int64_t workspace_bytes, int32_t *info, void *hip_stream) {
     auto fail = [](const std::string &msg) {
         g_svd_error = msg;
         return 1;
@@ -409,12 +434,12 @@ int mcl_svd_init(const float *X, const int64_t *row_ptr, int64_t I, int64_t K, i
     const long KK = (long)K * K;
     for (int64_t b0 = 0; b0 < I; b0 += p.BS) {
         const int nb = (int)std::min<int64_t>(p.BS, I - b0);
-        hipLaunchKernelGGL(k_svd_gram, dim3((unsigned)tiles, (unsigned)tiles, (unsigned)nb), dim3(256), 0, s, X, (const int *)ext, (int)b0,
+        hipLaunchKernelGGL((MCL_XKERNEL0(k_svd_gram)), dim3((unsigned)tiles, (unsigned)tiles, (unsigned)nb), dim3(256), 0, s, X, (const int *)ext, (int)b0,
                            (int)K, G);
         hipLaunchKernelGGL(k_svd_add, dim3((unsigned)((KK + 255) / 256)), dim3(256), 0, s, (const double *)G, nb, KK, Gstack, b0 == 0 ? 1 : 0);
         hipLaunchKernelGGL(k_svd_subspace, dim3((unsigned)nb), dim3(256), sm, s, (const double *)G, (int)K, m, (int)rank, Q, Y, theta, info,
                            (int)b0);
-        hipLaunchKernelGGL(k_svd_left, dim3((unsigned)nb), dim3(256), 0, s, X, (const int *)ext, (int)b0, (int)K, m, (int)rank,
+        hipLaunchKernelGGL((MCL_XKERNEL0(k_svd_left)), dim3((unsigned)nb), dim3(256), 0, s, X, (const int *)ext, (int)b0, (int)K, m, (int)rank,
                            (const double *)Q, U, (long)row_ptr[b0], (int)threshold, B);
     }
     hipLaunchKernelGGL(k_svd_subspace, dim3(1), dim3(256), sm, s, (const double *)Gstack, (int)K, m, (int)rank, Q, Y, theta, info, (int)I);
@@ -422,6 +447,26 @@ int mcl_svd_init(const float *X, const int64_t *row_ptr, int64_t I, int64_t K, i
     SVD_HIP(hipGetLastError());
 #undef SVD_HIP
     return 0;
+}
+
+extern "C" {
+
+int mcl_svd_init(const float *X, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank, int32_t threshold, float *B, float *C,
+                 void *workspace, int64_t workspace_bytes, int32_t *info, void *hip_stream) {
+    return svd_init<XF32>(X, row_ptr, I, K, rank, threshold, B, C, workspace, workspace_bytes, info, hip_stream);
+}
+
+int mcl_svd_init_typed(const void *X, int32_t x_type, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank, int32_t threshold,
+                       float *B, float *C, void *workspace, int64_t workspace_bytes, int32_t *info, void *hip_stream) {
+    if (x_type != MCL_X_F32 && x_type != MCL_X_BF16 && x_type != MCL_X_F16) {
+        g_svd_error = "mcl_svd_init_typed: unknown x_type " + std::to_string(x_type) + " (MCL_X_F32 = 0, MCL_X_BF16 = 1, MCL_X_F16 = 2)";
+        return 1;
+    }
+    return mcl_x_dispatch(x_type, [&](auto xl) {
+        using XL = decltype(xl);
+        return svd_init<XL>(static_cast<const typename XL::T *>(X), row_ptr, I, K, rank, threshold, B, C, workspace, workspace_bytes,
+                            info, hip_stream);
+    });
 }
 
 }  // extern "C"

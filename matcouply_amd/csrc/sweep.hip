@@ -23,6 +23,7 @@
 
 #include "mcl_internal.h"
 #include "rows_mfma.h"
+#include "xload.h"
 
 // ---------------------------------------------------------------------------------------------------------
 // lane naming: (q = l>>4, i16 = l&15).  Two register layouts of a 16 x 16 block of rows x columns occur:
@@ -52,23 +53,24 @@ static __device__ __forceinline__ long uniform_off(long v) {
 // DBG: the MCL_SWEEP_DBG experiments (phase elimination, per-section cycle counters: tools/run_dbg.sh, sweep_cycles.py)
 // are compiled into a second instantiation of the config-2/3 variants only; the production kernels carry none of it
 // (the counters alone cost 12 registers in kernels that sit at the 512-register limit).
-template <int KS, int NB, int NREG, int DEPTH, int NW, bool VEC, bool DBG = false, bool GRP = false, bool XNT = false>
-__global__ __launch_bounds__(64 * NW) void k_sweep(const float *__restrict__ X, const float *__restrict__ Cfrag,
-                                               const float *__restrict__ A, const float *__restrict__ rhoB,
-                                               const float *__restrict__ LinvB, float *__restrict__ Bout, RegSet regs,
-                                               const int *__restrict__ bs_slab, const int *__restrict__ bs_row0,
-                                               const int *__restrict__ bs_nrows, const int *__restrict__ wave_bseg_ptr, int n_waves,
-                                               int K, int r, int inner, float *__restrict__ Mpart,
-                                               double *__restrict__ part_btb, float *__restrict__ GRpart,
-                                               double *__restrict__ diag_block, int dbg_rt,
-                                               long long *__restrict__ cyc_out, const int *__restrict__ bs_part) {
+// XL: the element type of X (xload.h); k_sweep (fp32) and k_sweep_h (16-bit) below share this body.
+template <class XL, int KS, int NB, int NREG, int DEPTH, int NW, bool VEC, bool DBG, bool GRP, bool XNT>
+static __device__ __forceinline__ void sweep_body(const typename XL::T *X, const float *Cfrag,
+                                               const float *A, const float *rhoB,
+                                               const float *LinvB, float *Bout, RegSet regs,
+                                               const int *bs_slab, const int *bs_row0,
+                                               const int *bs_nrows, const int *wave_bseg_ptr, int n_waves,
+                                               int K, int r, int inner, float *Mpart,
+                                               double *part_btb, float *GRpart,
+                                               double *diag_block, int dbg_rt,
+                                               long long *cyc_out, const int *bs_part) {
     MCL_GATE(regs.gate);
     const int dbg = DBG ? dbg_rt : 0;
     // KS = 0: the half-width form for K <= 128 (config 2) - tile rows of 128 floats, a wave load / LDS store covers TWO
     // rows (lanes 0..31 row 2t, lanes 32..63 row 2t + 1): half the MFMAs, LDS traffic and partial bytes of the 256-wide form
     constexpr bool HALF = KS == 0;
     constexpr int KSA = HALF ? 1 : KS;           // 256-column super-chunks (array extents)
-    constexpr int XL = HALF ? 8 : 16;            // wave loads per super-chunk of a 16-row block
+    constexpr int XLD = HALF ? 8 : 16;           // wave loads per super-chunk of a 16-row block
     constexpr int KW = HALF ? 128 : 256 * KS;    // floats per tile row: K rounded up (K % 4 == 0, K <= KW)
     constexpr int KC = KW / 64;                  // 64-column chunks
     constexpr int W = 16 * NB;
@@ -205,7 +207,7 @@ __global__ __launch_bounds__(64 * NW) void k_sweep(const float *__restrict__ X, 
             unsigned xcol[KSA];
 #pragma unroll
             for (int sc = 0; sc < KSA; ++sc) xcol[sc] = (unsigned)min(256 * sc + 4 * (HALF ? (lane & 31) : lane), K - 4);
-            f32x4 xr[DEPTH][KSA][XL];
+            typename XL::raw xr[DEPTH][KSA][XLD];
             f32x4 zs[DEPTH][NR][NB], us[DEPTH][NR][NB];  // aux / dual rows of the slot's block, updated IN PLACE
             // Stage block `blk` of this wave into ring slot d.  Every load is unconditional (rows clamped into the
             // wave's range, scalar arithmetic): a branch around loads makes the compiler's counted s_waitcnt vmcnt(N)
@@ -214,7 +216,7 @@ __global__ __launch_bounds__(64 * NW) void k_sweep(const float *__restrict__ X, 
             // non-temporal hint, so the stream does not evict B / aux / dual (100 MB at config 3), the partials and the C image
             // from the cache between the kernels of an iteration (config 3: k_sweep 161 -> 137 us on the same box).  Problems
             // that fit the cache (per-rank shards, config 2) keep ordinary loads: with the hint they ran 3-5 % slower
-            auto ldx = [](const f32x4 *p) -> f32x4 { return XNT ? __builtin_nontemporal_load(p) : *p; };
+            auto ldx = [](const typename XL::T *p) { return XL::template ld4<XNT>(p); };
             auto issue_x = [&](auto dc, int blk) {  // 16 rows x K columns, one 1 KB row segment per wave load
                 constexpr int d = decltype(dc)::value;
                 // scalar addressing: ONE 64-bit product per block, then a 32-bit row offset per row (row clamped into
@@ -226,17 +228,16 @@ __global__ __launch_bounds__(64 * NW) void k_sweep(const float *__restrict__ X, 
                 if (HALF) {
                     // two rows per load: the upper half-wave adds one row (K floats) unless that row lies past the end
 #pragma unroll
-                    for (int t = 0; t < XL; ++t) {
+                    for (int t = 0; t < XLD; ++t) {
                         const unsigned up = (2 * t + 1 <= tmax) ? (unsigned)K : 0u;  // wave-uniform
-                        xr[d][0][t] = ldx(reinterpret_cast<const f32x4 *>(X + uniform_off(blk_off + (long)(min(2 * t, tmax) * K)) +
-                                                                          (xcol[0] + (hi ? up : 0u))));
+                        xr[d][0][t] = ldx(X + uniform_off(blk_off + (long)(min(2 * t, tmax) * K)) + (xcol[0] + (hi ? up : 0u)));
                     }
                 } else {
 #pragma unroll
                     for (int sc = 0; sc < KSA; ++sc)
 #pragma unroll
                         for (int t = 0; t < 16; ++t)
-                            xr[d][sc][t] = ldx(reinterpret_cast<const f32x4 *>(X + uniform_off(blk_off + (long)(min(t, tmax) * K)) + xcol[sc]));
+                            xr[d][sc][t] = ldx(X + uniform_off(blk_off + (long)(min(t, tmax) * K)) + xcol[sc]);
                 }
             };
             // aux / dual rows go straight into the registers the inner loop works on.  They are issued AFTER the slot's
@@ -288,14 +289,14 @@ __global__ __launch_bounds__(64 * NW) void k_sweep(const float *__restrict__ X, 
                 // ---- registers -> LDS tile (row t, 16-B slot 64 sc + lane, physical slot XORed with the row)
                 if (HALF) {
 #pragma unroll
-                    for (int t = 0; t < XL; ++t)
-                        *reinterpret_cast<f32x4 *>(L + 2 * t * KW + wr_hi + (wl ^ ((2 * t) << 2))) = xr[d][0][t];
+                    for (int t = 0; t < XLD; ++t)
+                        *reinterpret_cast<f32x4 *>(L + 2 * t * KW + wr_hi + (wl ^ ((2 * t) << 2))) = XL::cvt(xr[d][0][t]);
                 } else {
 #pragma unroll
                     for (int sc = 0; sc < KSA; ++sc)
 #pragma unroll
                         for (int t = 0; t < 16; ++t)
-                            *reinterpret_cast<f32x4 *>(L + t * KW + 256 * sc + wr_hi + (wl ^ (t << 2))) = xr[d][sc][t];
+                            *reinterpret_cast<f32x4 *>(L + t * KW + 256 * sc + wr_hi + (wl ^ (t << 2))) = XL::cvt(xr[d][sc][t]);
                 }
                 f32x4(&z)[NR][NB] = zs[d];
                 f32x4(&u)[NR][NB] = us[d];
@@ -681,6 +682,28 @@ __global__ __launch_bounds__(64 * NW) void k_sweep(const float *__restrict__ X, 
     }
 }
 
+#define MCL_SWEEP_PARAMS                                                                                                  \
+    const float *__restrict__ Cfrag, const float *__restrict__ A, const float *__restrict__ rhoB,                        \
+        const float *__restrict__ LinvB, float *__restrict__ Bout, RegSet regs, const int *__restrict__ bs_slab,          \
+        const int *__restrict__ bs_row0, const int *__restrict__ bs_nrows, const int *__restrict__ wave_bseg_ptr,         \
+        int n_waves, int K, int r, int inner, float *__restrict__ Mpart, double *__restrict__ part_btb,                  \
+        float *__restrict__ GRpart, double *__restrict__ diag_block, int dbg_rt, long long *__restrict__ cyc_out,         \
+        const int *__restrict__ bs_part
+#define MCL_SWEEP_ARGS                                                                                                    \
+    Cfrag, A, rhoB, LinvB, Bout, regs, bs_slab, bs_row0, bs_nrows, wave_bseg_ptr, n_waves, K, r, inner, Mpart, part_btb, \
+        GRpart, diag_block, dbg_rt, cyc_out, bs_part
+template <int KS, int NB, int NREG, int DEPTH, int NW, bool VEC, bool DBG = false, bool GRP = false, bool XNT = false>
+__global__ __launch_bounds__(64 * NW) void k_sweep(const float *__restrict__ X, MCL_SWEEP_PARAMS) {
+    sweep_body<XF32, KS, NB, NREG, DEPTH, NW, VEC, DBG, GRP, XNT>(X, MCL_SWEEP_ARGS);
+}
+// the 16-bit twin (XBF16 / XF16): the same template arguments after the element type
+template <class XL, int KS, int NB, int NREG, int DEPTH, int NW, bool VEC, bool DBG = false, bool GRP = false, bool XNT = false>
+__global__ __launch_bounds__(64 * NW) void k_sweep_h(const typename XL::T *__restrict__ X, MCL_SWEEP_PARAMS) {
+    sweep_body<XL, KS, NB, NREG, DEPTH, NW, VEC, DBG, GRP, XNT>(X, MCL_SWEEP_ARGS);
+}
+#undef MCL_SWEEP_PARAMS
+#undef MCL_SWEEP_ARGS
+
 // ---------------------------------------------------------------------------------------------------------
 // [G | R] = sum over the sweep's per-bseg a-weighted partials (decomposition.py:312-318).  Thread e walks the partials in fragment
 // order (coalesced) and scatters its sum to the row-major [G | R] image.  Fixed summation order (16 interleaved groups
@@ -871,20 +894,21 @@ bool mcl_sweep_eligible(const mcl_context *c) {
     if (c->regs[1].n == 0 || c->regs[1].n > 2 || !mcl_mode_is_row_separable(c, 1)) return false;  // n = 0: fp64 solve
     if (c->opt.inner_n_iter_max <= 0) return false;
     if (c->opt.inner_tol > 0.0) return false;  // the inner stopping test needs a launch per inner iteration
-    if (reinterpret_cast<uintptr_t>(c->X) & 15) return false;
+    if (!mcl_x_vec_aligned(c)) return false;
     return true;
 }
 
 static inline int sweep_MS(const mcl_context *c) { return mcl_sweep_KC(c) * 64 * 16 * c->NB; }
 
-template <int KS, int NB, int NREG, int NW, int DEPTH, bool VEC>
+template <class XL, int KS, int NB, int NREG, int NW, int DEPTH, bool VEC>
 static int launch_sweep_v(mcl_context *c) {
+    constexpr bool F32 = std::is_same_v<XL, XF32>;
     const int n = c->bsegs.n_tiles;
     const int n_waves = c->n_bseg_waves;  // <= 1024 = one per SIMD (the register file and the LDS tiles allow one or two)
     const int grid = (n_waves + NW - 1) / NW;
     constexpr int KWH = KS == 0 ? 128 : 256 * KS;
     const size_t sm = sizeof(float) * (size_t)(NW * 16 * KWH + KWH * 16 * NB);  // up to the full 160 KB
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_sweep<KS, NB, NREG, DEPTH, NW, VEC>),
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(MCL_XKERNEL(k_sweep, KS, NB, NREG, DEPTH, NW, VEC, false, false, false)),
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm) != hipSuccess) {
         (void)hipGetLastError();
         return -1;  // caller falls back to the two-pass path
@@ -893,13 +917,14 @@ static int launch_sweep_v(mcl_context *c) {
     // tables (mcl_diagnostics_deferred) may still be waiting for the coming C-phase reduction kernel
     c->diagB_parity ^= 1;
     c->diagB_tile = c->diagB_bufs[c->diagB_parity];
+    const typename XL::T *X = mcl_x<XL>(c);
 #define MCL_SWEEP_LAUNCH(DBG_, GRP_, NT_)                                                                              \
-    hipLaunchKernelGGL((k_sweep<KS, NB, NREG, DEPTH, NW, VEC, DBG_, GRP_, NT_>), dim3(grid), dim3(64 * NW), sm, c->stream, c->X,    \
-                       c->CfragS, c->A, c->rhoB, c->LinvB, c->B, c->regs[1], c->bsegs.slab, c->bsegs.row0, c->bsegs.nrows, \
-                       c->wave_bseg_ptr, n_waves, (int)c->K, c->r, c->opt.inner_n_iter_max, c->Mpart, c->part_btb, c->GRpart, c->diagB_tile, \
-                       c->sw.sweep_dbg, c->sweep_cycles, c->bseg_part)
+    hipLaunchKernelGGL((MCL_XKERNEL(k_sweep, KS, NB, NREG, DEPTH, NW, VEC, DBG_, GRP_, NT_)), dim3(grid), dim3(64 * NW), sm,    \
+                       c->stream, X, c->CfragS, c->A, c->rhoB, c->LinvB, c->B, c->regs[1], c->bsegs.slab, c->bsegs.row0,      \
+                       c->bsegs.nrows, c->wave_bseg_ptr, n_waves, (int)c->K, c->r, c->opt.inner_n_iter_max, c->Mpart,         \
+                       c->part_btb, c->GRpart, c->diagB_tile, c->sw.sweep_dbg, c->sweep_cycles, c->bseg_part)
     bool launched = false;
-    if constexpr (KS == 1 && NB == 1 && VEC) {  // the instrumented twin exists for the config-2/3 variants only
+    if constexpr (F32 && KS == 1 && NB == 1 && VEC) {  // the instrumented twin exists for the fp32 config-2/3 variants only
         if (c->sw.sweep_dbg != 0 && c->n_parts == n) {  // (the twin has no grouped flush: a plan with grouped partials keeps GRP)
             if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_sweep<KS, NB, NREG, DEPTH, NW, VEC, true>),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm) == hipSuccess) {
@@ -910,7 +935,7 @@ static int launch_sweep_v(mcl_context *c) {
     }
     if constexpr (KS <= 1 && NB == 1) {  // the instantiations with the grouped flush (mcl_set_problem only groups for them)
         if (!launched && c->n_parts < n) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_sweep<KS, NB, NREG, DEPTH, NW, VEC, false, true>),
+            if (hipFuncSetAttribute(reinterpret_cast<const void *>(MCL_XKERNEL(k_sweep, KS, NB, NREG, DEPTH, NW, VEC, false, true, false)),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm) != hipSuccess) {
                 (void)hipGetLastError();
                 return -1;
@@ -925,7 +950,7 @@ static int launch_sweep_v(mcl_context *c) {
             return 1;
         }
         if (c->x_streams) {  // X does not fit the last-level cache: non-temporal loads of X
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_sweep<KS, NB, NREG, DEPTH, NW, VEC, false, false, true>),
+            if (hipFuncSetAttribute(reinterpret_cast<const void *>(MCL_XKERNEL(k_sweep, KS, NB, NREG, DEPTH, NW, VEC, false, false, true)),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm) != hipSuccess) {
                 (void)hipGetLastError();
                 return -1;
@@ -940,7 +965,8 @@ static int launch_sweep_v(mcl_context *c) {
     c->diag_rows[1] = grid;
     c->n_grpart = c->n_parts;  // one partial per bseg, or per group of four bsegs of a slab
     char buf[96];
-    snprintf(buf, sizeof buf, "k_sweep<KS=%d,NB=%d,NREG=%d,DEPTH=%d,NW=%d,VEC=%d>", KS, NB, NREG, DEPTH, NW, VEC ? 4 : 1);
+    snprintf(buf, sizeof buf, "k_sweep%s<%sKS=%d,NB=%d,NREG=%d,DEPTH=%d,NW=%d,VEC=%d>", mcl_x_kname<XL>(), mcl_x_targ<XL>(), KS, NB,
+             NREG, DEPTH, NW, VEC ? 4 : 1);
     c->variant[MCL_PROF_SWEEP] = buf;
     return 0;
 }
@@ -951,8 +977,11 @@ static int launch_sweep_w(mcl_context *c) {
     auto al = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
     bool vec = (c->r % 4 == 0) && al(c->B);
     for (int k = 0; k < c->regs[1].n; ++k) vec = vec && al(c->regs[1].aux[k]) && al(c->regs[1].dual[k]);
-    if (vec) return launch_sweep_v<KS, NB, NREG, NW, DEPTH, true>(c);
-    return launch_sweep_v<KS, NB, NREG, NW, DEPTH, false>(c);
+    return mcl_x_dispatch(c->x_type, [&](auto xl) {
+        using XL = decltype(xl);
+        if (vec) return launch_sweep_v<XL, KS, NB, NREG, NW, DEPTH, true>(c);
+        return launch_sweep_v<XL, KS, NB, NREG, NW, DEPTH, false>(c);
+    });
 }
 
 template <int KS, int NB, int NREG>

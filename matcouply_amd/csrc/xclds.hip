@@ -16,6 +16,7 @@
 // ascending in K), summed pairwise at the end of a 16-row block; the fused reductions (GRAM) word for word.  Same segment /
 // wave tables.  Reference: decomposition.py:147-158 (X_i C, diag(B_i^T X_i C), B_i^T B_i) and :242.
 #include "mcl_internal.h"
+#include "xload.h"
 
 typedef float xf32x4 __attribute__((ext_vector_type(4)));
 typedef double xf64x4 __attribute__((ext_vector_type(4)));
@@ -30,12 +31,8 @@ struct TileCursor {
     int nrows, nblk, blk, hs;
 };
 
-template <int NB, int GRAM, bool XNT, int DEPTH>
-__global__ __launch_bounds__(256) void k_contract_xc_lds(const float *__restrict__ X, const float *__restrict__ Cfrag,
-                                                         float *__restrict__ XC, const float *__restrict__ B,
-                                                         const int *__restrict__ seg_row0, const int *__restrict__ seg_rows,
-                                                         const int *__restrict__ wave_seg_ptr, int n_waves, int K, int r,
-                                                         double *__restrict__ seg_rhs, double *__restrict__ seg_btb) {
+template <class XL, int NB, int GRAM, bool XNT, int DEPTH>
+static __device__ __forceinline__ void k_contract_xc_lds_body(const typename XL::T *X, const float *Cfrag, float *XC, const float *B, const int *seg_row0, const int *seg_rows, const int *wave_seg_ptr, int n_waves, int K, int r, double *seg_rhs, double *seg_btb) {
     extern __shared__ float lds_dyn[];  // fragment image of C, then 4 waves x 16 rows x 128 floats
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int q = lane >> 4, i16 = lane & 15;
@@ -55,7 +52,7 @@ __global__ __launch_bounds__(256) void k_contract_xc_lds(const float *__restrict
     const int TPB = K >> 7;  // tiles per 16-row block (a multiple of DEPTH)
 
     // ---- the prefetch side: four tiles in registers
-    xf32x4 xr[DEPTH][8];
+    typename XL::raw xr[DEPTH][8];
     float bnx[NB][4];  // rows 4q + v, column 16 nb + i16 of B for the block the prefetch cursor is in
     int bcolc[NB];
 #pragma unroll
@@ -77,12 +74,11 @@ __global__ __launch_bounds__(256) void k_contract_xc_lds(const float *__restrict
         }
     };
     const int half = lane >> 5, slot = lane & 31;
-    auto issue = [&](const TileCursor &c, xf32x4 (&dst)[8]) {
+    auto issue = [&](const TileCursor &c, typename XL::raw (&dst)[8]) {
 #pragma unroll
         for (int t = 0; t < 8; ++t) {
             const long j = c.row0 + min(16 * c.blk + 2 * t + half, c.nrows - 1);
-            const xf32x4 *p = reinterpret_cast<const xf32x4 *>(X + j * K + 128 * c.hs + 4 * slot);
-            dst[t] = XNT ? __builtin_nontemporal_load(p) : *p;
+            dst[t] = XL::template ld4<XNT>(X + j * K + 128 * c.hs + 4 * slot);
         }
     };
     auto issue_b = [&](const TileCursor &c) {
@@ -150,7 +146,7 @@ __global__ __launch_bounds__(256) void k_contract_xc_lds(const float *__restrict
 #pragma unroll
             for (int t = 0; t < 8; ++t) {
                 const int R = 2 * t + half;
-                *reinterpret_cast<xf32x4 *>(L + R * 128 + ((slot ^ (R & 15)) << 2)) = xr[s][t];
+                *reinterpret_cast<xf32x4 *>(L + R * 128 + ((slot ^ (R & 15)) << 2)) = XL::cvt(xr[s][t]);
             }
             // the slot is free: the tile DEPTH ahead (once per round with the rows of B of its block: a fixed number of loads)
             if (s == 0) issue_b(pc);
@@ -249,14 +245,32 @@ __global__ __launch_bounds__(256) void k_contract_xc_lds(const float *__restrict
         if (cc.sg + 1 < s1) seg_of(cc, cc.sg + 1);
     }
 }
+template <int NB, int GRAM, bool XNT, int DEPTH>
+__global__ __launch_bounds__(256) void k_contract_xc_lds(const float *__restrict__ X, const float *__restrict__ Cfrag,
+                                                         float *__restrict__ XC, const float *__restrict__ B,
+                                                         const int *__restrict__ seg_row0, const int *__restrict__ seg_rows,
+                                                         const int *__restrict__ wave_seg_ptr, int n_waves, int K, int r,
+                                                         double *__restrict__ seg_rhs, double *__restrict__ seg_btb) {
+    k_contract_xc_lds_body<XF32, NB, GRAM, XNT, DEPTH>(X, Cfrag, XC, B, seg_row0, seg_rows, wave_seg_ptr, n_waves, K, r, seg_rhs, seg_btb);
+}
+// the 16-bit twin (xload.h): the same template arguments after the element type
+template <class XL, int NB, int GRAM, bool XNT, int DEPTH>
+__global__ __launch_bounds__(256) void k_contract_xc_lds_h(const typename XL::T *__restrict__ X, const float *__restrict__ Cfrag,
+                                                         float *__restrict__ XC, const float *__restrict__ B,
+                                                         const int *__restrict__ seg_row0, const int *__restrict__ seg_rows,
+                                                         const int *__restrict__ wave_seg_ptr, int n_waves, int K, int r,
+                                                         double *__restrict__ seg_rhs, double *__restrict__ seg_btb) {
+    k_contract_xc_lds_body<XL, NB, GRAM, XNT, DEPTH>(X, Cfrag, XC, B, seg_row0, seg_rows, wave_seg_ptr, n_waves, K, r, seg_rhs, seg_btb);
+}
 
 }  // namespace
 
 // Launches the LDS-resident-C form of the X C pass when the shape allows it; returns 1 when launched, 0 otherwise.
 // gram: 0 X C only, 1 fused per-segment reductions in fp32 chains, 2 in fp64.  MCL_XC_LDS_DEPTH=4 / 8 overrides the ring depth.
-int mcl_try_contract_xc_lds(mcl_context *c, int gram) {
+template <class XL>
+static int try_xc_lds(mcl_context *c, int gram) {
     if (c->sw.no_xc_lds || c->NB > 2 || (c->K % 512) != 0 || (c->K % 4) != 0) return 0;
-    if ((reinterpret_cast<uintptr_t>(c->X) & 15) != 0) return 0;
+    if (!mcl_x_vec_aligned(c)) return 0;
     const size_t cf_bytes = (size_t)(c->K >> 6) * 4 * c->NB * 256 * sizeof(float);
     const size_t sm = cf_bytes + sizeof(float) * 4 * 16 * 128;
     if (sm > 160 * 1024) return 0;
@@ -268,21 +282,27 @@ int mcl_try_contract_xc_lds(mcl_context *c, int gram) {
     // config 5: with four the pass no longer waits for bytes in flight
     int depth = 4;
     if (c->sw.xc_lds_depth == 4 || c->sw.xc_lds_depth == 8) depth = (c->K % (128 * c->sw.xc_lds_depth) == 0) ? c->sw.xc_lds_depth : depth;
+    constexpr bool F32 = std::is_same_v<XL, XF32>;  // (the depth-8 experiment has no 16-bit twin)
 #define MCL_XCL__(NB_, GRAM_, NT_, D_)                                                                                    \
     do {                                                                                                                  \
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_contract_xc_lds<NB_, GRAM_, NT_, D_>),                    \
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(MCL_XKERNEL(k_contract_xc_lds, NB_, GRAM_, NT_, D_)),       \
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm) != hipSuccess) {                      \
             (void)hipGetLastError();                                                                                      \
             return 0;                                                                                                     \
         }                                                                                                                 \
-        hipLaunchKernelGGL((k_contract_xc_lds<NB_, GRAM_, NT_, D_>), dim3(g), dim3(256), sm, c->stream, c->X, c->Cfrag,     \
+        hipLaunchKernelGGL((MCL_XKERNEL(k_contract_xc_lds, NB_, GRAM_, NT_, D_)), dim3(g), dim3(256), sm, c->stream,          \
+                           mcl_x<XL>(c), c->Cfrag,                                                                        \
                            c->XC, c->B, c->segs.row0, c->segs.nrows, c->wave_seg_ptr, c->n_seg_waves, (int)c->K, c->r,      \
                            c->seg_rhs, c->seg_btb);                                                                       \
     } while (0)
 #define MCL_XCL_(NB_, GRAM_, NT_)                                \
     do {                                                         \
-        if (depth == 8) MCL_XCL__(NB_, GRAM_, NT_, 8);           \
-        else MCL_XCL__(NB_, GRAM_, NT_, 4);                      \
+        if constexpr (F32) {                                     \
+            if (depth == 8) MCL_XCL__(NB_, GRAM_, NT_, 8);       \
+            else MCL_XCL__(NB_, GRAM_, NT_, 4);                  \
+        } else {                                                 \
+            MCL_XCL__(NB_, GRAM_, NT_, 4);                       \
+        }                                                        \
     } while (0)
 #define MCL_XCL(NB_, GRAM_)                                      \
     do {                                                         \
@@ -302,4 +322,8 @@ int mcl_try_contract_xc_lds(mcl_context *c, int gram) {
 #undef MCL_XCL_
 #undef MCL_XCL__
     return hipGetLastError() == hipSuccess ? 1 : 0;
+}
+
+int mcl_try_contract_xc_lds(mcl_context *c, int gram) {
+    return mcl_x_dispatch(c->x_type, [&](auto xl) { return try_xc_lds<decltype(xl)>(c, gram); });
 }

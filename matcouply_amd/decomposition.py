@@ -88,8 +88,8 @@ def partition_slabs(n_rows, world_size, contiguous=True):
 
 
 class PackedMatrices:
-    """The I coupled matrices already packed along rows in device memory: X [sum J_i, K] float32 (torch CUDA
-    tensor) + row_ptr [I+1].  Behaves like the list of the I matrices (len / iteration / indexing give views),
+    """The I coupled matrices already packed along rows in device memory: X [sum J_i, K] float32, bfloat16 or float16
+    (contiguous torch CUDA tensor; a 16-bit X stays 16-bit, every kernel reads it as such) + row_ptr [I+1].  Behaves like the list of the I matrices (len / iteration / indexing give views),
     and lets callers that keep their data in HBM skip the host-side packing."""
 
     def __init__(self, X, row_ptr):
@@ -182,7 +182,8 @@ def initialize_cmf(matrices, rank, init, svd_fun, random_state=None, init_params
 
         if svd_fun is None:
             svd_fun = get_svd("truncated_svd")
-        mats = [np.asarray(to_numpy(m), dtype=np.float64) for m in matrices]
+        mats = [np.asarray(to_numpy(m.float() if is_torch(m) and m.dtype == torch.bfloat16 else m), dtype=np.float64)
+                for m in matrices]  # (NumPy has no bfloat16: exact upcast first)
         A = np.ones((len(mats), rank))
         B_is = [svd_fun(m, n_eigenvecs=rank)[0] for m in mats]
         C = svd_fun(np.concatenate(mats, 0), n_eigenvecs=rank)[2].T
@@ -509,12 +510,36 @@ def _to_dev(x, device):
     return torch.as_tensor(np.ascontiguousarray(np.asarray(x)), device=device).to(_dtype()).contiguous()
 
 
-def _pack(matrices, device):
-    """-> (X [N, K] float32 on device, row_ptr int64 [I+1])"""
+def _x16_dtype(mats):
+    """the torch dtype of a homogeneous list of 16-bit matrices (torch bfloat16 / float16 tensors, NumPy float16 arrays), else
+    None: mixed lists and every other input are packed in float32"""
+    def dt(m):
+        if is_torch(m):
+            return m.dtype if m.dtype in (torch.bfloat16, torch.float16) else None
+        return torch.float16 if isinstance(m, np.ndarray) and m.dtype == np.float16 else None
+
+    d = [dt(m) for m in mats]
+    return d[0] if d and d[0] is not None and all(x == d[0] for x in d) else None
+
+
+def _upcast_x16(matrices):
+    """the matrices with 16-bit X upcast (exactly) to float32: for a substituted checker engine without `supports_x16`"""
     if isinstance(matrices, PackedMatrices):
         X = matrices.X
-        if not (is_torch(X) and X.is_cuda and X.dtype == torch.float32 and X.is_contiguous()):
-            raise TypeError("PackedMatrices.X must be a contiguous float32 CUDA tensor")
+        return PackedMatrices(X.float(), matrices.row_ptr) if is_torch(X) and X.dtype in (torch.bfloat16, torch.float16) else matrices
+    return [m.float() if is_torch(m) and m.dtype in (torch.bfloat16, torch.float16) else m for m in matrices]
+
+
+def _pack(matrices, device):
+    """-> (X [N, K] on device, row_ptr int64 [I+1]).  X is float32, or bfloat16 / float16 for a PackedMatrices of that dtype and
+    for a homogeneous list of 16-bit matrices (_x16_dtype: packed at two bytes per element, no float32 copy)."""
+    if isinstance(matrices, PackedMatrices):
+        X = matrices.X
+        if not (is_torch(X) and X.dtype in (torch.float32, torch.bfloat16, torch.float16)):
+            raise TypeError("PackedMatrices.X must be a float32, bfloat16 or float16 torch tensor, not "
+                            f"{getattr(X, 'dtype', type(X).__name__)}")
+        if not (X.is_cuda and X.is_contiguous()):
+            raise TypeError("PackedMatrices.X must be a contiguous CUDA tensor")
         return X, matrices.row_ptr
     mats = list(matrices)
     K = shape(mats[0])[1]
@@ -523,6 +548,12 @@ def _pack(matrices, device):
             raise ValueError("All matrices must be second order tensors with the same number of columns")
     rows = [shape(m)[0] for m in mats]
     row_ptr = np.concatenate([[0], np.cumsum(rows)]).astype(np.int64)
+    x16 = _x16_dtype(mats)
+    if x16 is not None:  # one packed 16-bit copy on the device (CPU matrices are uploaded at two bytes per element)
+        X = torch.empty((int(row_ptr[-1]), K), dtype=x16, device=device)
+        for i, m in enumerate(mats):
+            X[row_ptr[i]: row_ptr[i + 1]] = m.detach() if is_torch(m) else torch.from_numpy(np.ascontiguousarray(m))
+        return X, row_ptr
     if all(is_torch(m) for m in mats):
         X = torch.cat([m.detach().to(device=device, dtype=torch.float32) for m in mats], 0).contiguous()
     else:
@@ -733,7 +764,9 @@ def cmf_aoadmm(
     sub = _test_engine_factory()
     factory = sub or _default_engine_factory
     device = _device() if sub is None else getattr(sub, "device", torch.device("cpu"))
-    X, row_ptr = _pack(matrices, device) if sub is None else sub.pack(matrices)
+    # a checker engine without `supports_x16` is handed the exact float32 image of a 16-bit X
+    X, row_ptr = _pack(matrices, device) if sub is None else sub.pack(
+        matrices if getattr(sub, "supports_x16", False) else _upcast_x16(matrices))
     out = _Out(matrices)
     _, (A0, B0_is, C0) = cmf
     A, B, C = _to_dev(A0, device), _pack_rows(B0_is, device), _to_dev(C0, device)

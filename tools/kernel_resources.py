@@ -22,7 +22,7 @@ BASELINE = os.path.join(REPO, "profiles", "kernel_resources.json")
 READELF = "/opt/rocm/lib/llvm/bin/llvm-readelf"
 MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
 # the kernels the iteration time of the BASELINE configurations is made of: held to the committed baseline
-HOT = [r"^k_sweep<", r"^k_contract_x", r"^k_rows_finish_solve_stats<", r"^k_rows_finish_fused<", r"^k_rows_solve_stats<",
+HOT = [r"^k_sweep<", r"^k_sweep_h<", r"^k_contract_x", r"^k_rows_finish_solve_stats<", r"^k_rows_finish_fused<", r"^k_rows_solve_stats<",
        r"^k_pf2_algebra_ns<", r"^k_slab_unimodal_v4<", r"^k_rows_fused<", r"^k_reduce_frag", r"^k_A_finish_rows", r"^k_C_finish_multi",
        r"k_rows_chain_(first|mid|last)<"]
 
