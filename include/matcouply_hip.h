@@ -281,6 +281,22 @@ int mcl_svd_init_typed(const void *X, int32_t x_type, const int64_t *row_ptr, in
                        float *B, float *C, void *workspace, int64_t workspace_bytes, int32_t *info, void *hip_stream);
 const char *mcl_svd_init_last_error(void);
 
+/* ---- before the solver: init="parafac_als" / "cp_als", "parafac_hals" / "cp_hals" (decomposition.py:55-75) ------------------ */
+/* CP-ALS (method MCL_ALS_CP) or CP-HALS (MCL_ALS_CP_HALS) on the zero-padded tensor [I, max J_i, K] for data resident in HBM.
+ * Start: C = the C of mcl_svd_init, B = the leading eigenvectors of sum_i X~_i X~_i^T (entry of largest magnitude positive;
+ * HALS: both clipped at 0), A = 1.  Sweeps over the modes A, B, C; stop after sweep t >= 1 when |e_{t-1} - e_t| < tol (tol = 0:
+ * exactly n_iter_max sweeps).  Outputs A [I, rank], B packed [N, rank] (B_i = B[:J_i]), C [K, rank], errors fp64[n_iter_max]
+ * (relative reconstruction error after every sweep; may be NULL), info int32[1] = sweeps used.  Stateless; X, A, B, C, errors,
+ * info, workspace: device pointers; row_ptr: HOST int64[I+1].  Needs rank <= min(max J_i, K), K <= 2048, max J_i <= 2048,
+ * rank <= 64.  Deterministic (fixed reduction orders).  Synchronises the stream at the start, once per sweep when tol > 0 and at
+ * the end. */
+enum mcl_als_method { MCL_ALS_CP = 0, MCL_ALS_CP_HALS = 1 };
+int64_t mcl_als_init_workspace_bytes(const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank);
+int mcl_als_init_typed(const void *X, int32_t x_type, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank, int32_t method,
+                       int32_t n_iter_max, double tol, float *A, float *B, float *C, double *errors, int32_t *info, void *workspace,
+                       int64_t workspace_bytes, void *hip_stream);
+const char *mcl_als_init_last_error(void);
+
 /* ---- introspection for tests / profiling ------------------------------------------------------------- */
 /* device pointers to internal by-products / planner tables (the int32 tables: read the bits) */
 enum mcl_buffer_id {

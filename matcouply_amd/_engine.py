@@ -59,6 +59,7 @@ EXPORTED_SYMBOLS = [
     "mcl_reload_switches", "mcl_active_switches", "mcl_record_event", "mcl_wait_event", "mcl_cmf_to_packed",
     "mcl_svd_init_workspace_bytes", "mcl_svd_init", "mcl_svd_init_last_error", "mcl_read_bandwidth",
     "mcl_set_problem_typed", "mcl_svd_init_typed",
+    "mcl_als_init_workspace_bytes", "mcl_als_init_typed", "mcl_als_init_last_error",
 ]
 
 
@@ -159,6 +160,10 @@ def load_library():
         "mcl_svd_init": (ctypes.c_int, [P, ctypes.POINTER(I64), I64, I64, I32, I32, P, P, P, I64, P, P]),
         "mcl_svd_init_typed": (ctypes.c_int, [P, I32, ctypes.POINTER(I64), I64, I64, I32, I32, P, P, P, I64, P, P]),
         "mcl_svd_init_last_error": (ctypes.c_char_p, []),
+        "mcl_als_init_workspace_bytes": (I64, [ctypes.POINTER(I64), I64, I64, I32]),
+        "mcl_als_init_typed": (ctypes.c_int, [P, I32, ctypes.POINTER(I64), I64, I64, I32, I32, I32, ctypes.c_double, P, P, P, P, P, P,
+                                              I64, P]),
+        "mcl_als_init_last_error": (ctypes.c_char_p, []),
         "mcl_read_bandwidth": (ctypes.c_int, [P, I64, I32, P, P, ctypes.POINTER(ctypes.c_double)]),
     }
     for name, (res, args) in sig.items():
@@ -246,6 +251,43 @@ def svd_init(X, row_ptr, rank, threshold=False):
     if rc != 0:
         raise EngineError(lib.mcl_svd_init_last_error().decode())
     return B, C, info
+
+
+ALS_CP, ALS_CP_HALS = 0, 1  # enum mcl_als_method
+
+
+def als_init(X, row_ptr, rank, method, n_iter_max, tol):
+    """init="parafac_als" / "parafac_hals" on the device (mcl_als_init_typed): CP-ALS (method ALS_CP) or CP-HALS (ALS_CP_HALS)
+    on the zero-padded tensor.  X packed [sum J_i, K] float32 / bfloat16 / float16 CUDA tensor -> (A [I, rank], B packed
+    [sum J_i, rank] (B_i = B[:J_i] of the padded factor), C [K, rank], errors float64 [sweeps used]: the relative
+    reconstruction error after every sweep)."""
+    import torch
+
+    lib = load_library()
+    xt = x_type_of(X.dtype)
+    if not (X.is_cuda and X.is_contiguous()):
+        raise EngineError("X must be a contiguous CUDA tensor")
+    row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int64)
+    I, K, N = len(row_ptr) - 1, int(X.shape[1]), int(X.shape[0])
+    rp = row_ptr.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+    nbytes = lib.mcl_als_init_workspace_bytes(rp, I, K, int(rank))
+    if nbytes < 0:
+        raise EngineError("mcl_als_init_workspace_bytes: bad arguments")
+    ws = torch.empty(int(nbytes) + 256, dtype=torch.uint8, device=X.device)
+    off = (-ws.data_ptr()) % 256
+    A = torch.empty((I, int(rank)), dtype=torch.float32, device=X.device)
+    B = torch.empty((N, int(rank)), dtype=torch.float32, device=X.device)
+    C = torch.empty((K, int(rank)), dtype=torch.float32, device=X.device)
+    errors = torch.zeros(max(int(n_iter_max), 1), dtype=torch.float64, device=X.device)
+    info = torch.zeros(1, dtype=torch.int32, device=X.device)
+    with torch.cuda.device(X.device):
+        stream = torch.cuda.current_stream(X.device).cuda_stream
+        rc = lib.mcl_als_init_typed(X.data_ptr(), xt, rp, I, K, int(rank), int(method), int(n_iter_max), float(tol), A.data_ptr(),
+                                    B.data_ptr(), C.data_ptr(), errors.data_ptr(), info.data_ptr(), ws.data_ptr() + off, nbytes,
+                                    ctypes.c_void_p(stream))
+    if rc != 0:
+        raise EngineError(lib.mcl_als_init_last_error().decode())
+    return A, B, C, errors[: int(info.item())]
 
 
 class NativeReg:

@@ -1,0 +1,868 @@
+// init="parafac_als" / "cp_als" and "parafac_hals" / "cp_hals" (decomposition.py:55-75) for data resident in HBM: CP-ALS or
+// CP-HALS on the zero-padded tensor X~ [I, Jmax, K] (row j >= J_i of slab i is a zero the model fits), deterministic start.
+//
+// Factors A [I, r], B [Jmax, r], C [K, r] are kept in fp64; B_i = B[:J_i] is what the caller receives.  Per sweep, modes A, B, C:
+//     pass 1 (X):  XC = X C on the fp32 MFMA (C as fp32 fragments); epilogue: M_A partial per segment = sum_rows XC o B[j]
+//     A <- update(M_A, G_A = B^T B o C^T C)
+//     M_B = sum_i X~_i C diag(a_i) from the XC rows (no X traffic), slab groups then a fixed-order sum
+//     B <- update(M_B, G_B = A^T A o C^T C)
+//     pass 2 (X):  M_C = sum_i X_i^T (B[:J_i] diag(a_i)) on the fp32 MFMA, fp64 partials per row chunk, fixed-order sum
+//     C <- update(M_C, G_C = A^T A o B^T B);  e_t = sqrt(max(0, |X|^2 - 2 <M_C, C> + 1^T (A^T A o B^T B o C^T C) 1)) / |X|
+// update: ALS  F = M_F G_F^-1 (in-place Gauss-Jordan of the SPD r x r matrix; not positive definite: the pseudo-inverse from a
+//         Jacobi eigen-decomposition, eigenvalues <= 1e-12 lam_max dropped);
+//         HALS for q = 0..r-1: F[:,q] <- max(0, F[:,q] + (M_F[:,q] - F G_F[:,q]) / G_F[q,q])  (skipped where G_F[q,q] = 0).
+// M_C needs the A and B of the same sweep, so two reads of X per sweep is the floor.  Every reduction has a fixed order and no
+// float atomics are used: two runs are bitwise equal.
+// Start: C0 = the C of mcl_svd_init (the stack's right singular vectors), B0 = the leading eigenvectors of the padded-row Gram
+// matrix sum_i X~_i X~_i^T (Jmax x Jmax, fp64), both with the entry of largest magnitude positive (HALS: clipped at 0); A0 = 1.
+#include <algorithm>
+#include <cmath>
+#include <string>
+#include <vector>
+
+#include "mcl_internal.h"
+#include "rows_mfma.h"
+#include "symeig_lds.h"
+#include "xload.h"
+
+namespace {
+
+static std::string g_als_error;
+constexpr int ALS_SEG = 64;          // rows of one slab per segment (one wave of pass 1)
+constexpr int ALS_TARGET_WG = 1024;  // workgroups of pass 2 (row chunks x 64-column blocks)
+enum { OP_LOAD = 0, OP_ALS = 1, OP_HALS = 2 };
+
+inline int als_nb(int r) { return r <= 16 ? 1 : r <= 32 ? 2 : 4; }
+
+// sum of a double over the 16 lanes of a DPP row (lanes with the same l >> 4); the total in every lane of the row
+static __device__ __forceinline__ double row16_sum(double v) {
+    v += dpp_mov_f64<0xB1>(v);
+    v += dpp_mov_f64<0x4E>(v);
+    v += dpp_mov_f64<0x141>(v);
+    v += dpp_mov_f64<0x140>(v);
+    return v;
+}
+
+// four consecutive elements of X as fp32, zero past column K (VEC: K % 4 == 0 and an aligned base)
+template <class XL, bool VEC>
+static __device__ __forceinline__ f32x4 als_ld4(const typename XL::T *p, int col, int K) {
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (VEC) {
+        if (col < K) v = XL::cvt(XL::template ld4<false>(p));
+    } else {
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (col + q < K) v[q] = XL::ld1(p + q);
+    }
+    return v;
+}
+
+// ---- pass 1: XC = X C, M_A partials ---------------------------------------------------------------------------------------
+// One wave per segment (<= 64 rows of one slab; seg = {slab, first packed row, rows, first row within the slab}), walking
+// 64-column chunks H and, inside each, its 4 row blocks rb of 16 rows:
+//   global -> registers: lane (rr = l >> 4, cc = l & 15), t < 4: X[16 rb + 4 t + rr][64 H + 4 cc .. +3]  (256-B row segments)
+//   registers -> LDS   : wave-private 16 x 64 fp32 tile, 16-B slot index XORed with the row (conflict-free)
+//   LDS -> fragments   : lane (row16 = l & 15, g = l >> 4), h < 4: X[16 rb + row16][64 H + 16 h + 4 g .. +3]
+//   MFMA on the transposed problem (rows_mfma.h) with Cfrag[4H + h][hp][lane][kq] = C[64H + 16h + 4g + kq][16hp + (l & 15)]:
+//   accumulator (rb, hp), lane l, reg v = XC[16 rb + row16][16 hp + 4 g + v].
+// The next step's global loads are in flight while the current tile is multiplied (rows clamped into the segment, columns
+// past K zero).  LDS operations of one wave complete in order, so the tile needs no barrier.
+template <class XL, int NB, bool VEC>
+static __device__ __forceinline__ void k_als_xc_body(const typename XL::T *X, const int4 *segs, int nseg, int K, int r, const float *Cfrag,
+                                                     const double *B64, float *XC, double *Pa) {
+    __shared__ f32x4 tiles[4][16 * 16];
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, seg = blockIdx.x * 4 + w;
+    if (seg >= nseg) return;  // whole waves; no barrier below
+    f32x4 *T = tiles[w];
+    const int4 sg = segs[seg];
+    const int row0 = sg.y, n = sg.z, j0 = sg.w;
+    const int row16 = lane & 15, g = lane >> 4, rr = lane >> 4, cc = lane & 15;
+    f32x4 acc[4][NB];
+#pragma unroll
+    for (int rb = 0; rb < 4; ++rb)
+#pragma unroll
+        for (int hp = 0; hp < NB; ++hp) acc[rb][hp] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int KC = (K + 63) >> 6;
+    f32x4 xn[4];
+    auto load = [&](int H, int rb) {
+        const int col = 64 * H + 4 * cc;
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+            xn[t] = als_ld4<XL, VEC>(X + (long)(row0 + min(16 * rb + 4 * t + rr, n - 1)) * K + col, col, K);
+    };
+    load(0, 0);
+    for (int H = 0; H < KC; ++H) {
+        f32x4 cf[4][NB];
+#pragma unroll
+        for (int h = 0; h < 4; ++h)
+#pragma unroll
+            for (int hp = 0; hp < NB; ++hp)
+                cf[h][hp] = *reinterpret_cast<const f32x4 *>(Cfrag + (((long)(4 * H + h) * NB + hp) * 64 + lane) * 4);
+#pragma unroll
+        for (int rb = 0; rb < 4; ++rb) {
+#pragma unroll
+            for (int t = 0; t < 4; ++t) T[(4 * t + rr) * 16 + (cc ^ (4 * t + rr))] = xn[t];
+            if (rb < 3) load(H, rb + 1);
+            else if (H + 1 < KC) load(H + 1, 0);
+            f32x4 x[4];
+#pragma unroll
+            for (int h = 0; h < 4; ++h) x[h] = T[row16 * 16 + ((4 * h + g) ^ row16)];
+#pragma unroll
+            for (int h = 0; h < 4; ++h)
+#pragma unroll
+                for (int hp = 0; hp < NB; ++hp)
+#pragma unroll
+                    for (int kq = 0; kq < 4; ++kq) acc[rb][hp] = MFMA16(cf[h][hp][kq], x[h][kq], acc[rb][hp]);
+        }
+    }
+    double pa[NB][4];
+#pragma unroll
+    for (int hp = 0; hp < NB; ++hp)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) pa[hp][v] = 0.0;
+#pragma unroll
+    for (int rb = 0; rb < 4; ++rb) {
+        const int loc = 16 * rb + row16;
+        if (loc >= n) continue;
+#pragma unroll
+        for (int hp = 0; hp < NB; ++hp)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                const int q = 16 * hp + 4 * g + v;
+                if (q < r) {
+                    XC[(long)(row0 + loc) * r + q] = acc[rb][hp][v];
+                    pa[hp][v] = fma((double)acc[rb][hp][v], B64[(long)(j0 + loc) * r + q], pa[hp][v]);
+                }
+            }
+    }
+#pragma unroll
+    for (int hp = 0; hp < NB; ++hp)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const double s = row16_sum(pa[hp][v]);
+            const int q = 16 * hp + 4 * g + v;
+            if (row16 == 0 && q < r) Pa[(long)seg * r + q] = s;
+        }
+}
+template <int NB, bool VEC>
+__global__ __launch_bounds__(256) void k_als_xc(const float *__restrict__ X, const int4 *__restrict__ segs, int nseg, int K, int r,
+                                                const float *__restrict__ Cfrag, const double *__restrict__ B64, float *__restrict__ XC,
+                                                double *__restrict__ Pa) {
+    k_als_xc_body<XF32, NB, VEC>(X, segs, nseg, K, r, Cfrag, B64, XC, Pa);
+}
+// the 16-bit twin (xload.h): the same template arguments after the element type
+template <class XL, int NB, bool VEC>
+__global__ __launch_bounds__(256) void k_als_xc_h(const typename XL::T *__restrict__ X, const int4 *__restrict__ segs, int nseg, int K, int r,
+                                                  const float *__restrict__ Cfrag, const double *__restrict__ B64, float *__restrict__ XC,
+                                                  double *__restrict__ Pa) {
+    k_als_xc_body<XL, NB, VEC>(X, segs, nseg, K, r, Cfrag, B64, XC, Pa);
+}
+
+// ---- pass 2: M_C partials = sum over the rows of a chunk of X^T (B[j] o a_i) ----------------------------------------------------
+// Workgroup (chunk c = consecutive segments, 64-column block kb); wave w takes the 4-row groups w, w + 4, w + 8, w + 12 of every
+// segment.  Lane (rsub = l >> 4, c16 = l & 15) loads X[row0 + 4 gi + rsub][64 kb + 4 c16 .. +3]; MFMA (m, nb): A = component m
+// (output row i = c16 <-> k = 64 kb + 4 i + m), B = W[row][16 nb + c16], reduction index = the 4 rows of the group.
+// Accumulator (m, nb), lane l, reg v = R[64 kb + 4 (4 (l >> 4) + v) + m][16 nb + (l & 15)].  The four waves are summed in fp64 in a
+// fixed order and written as the chunk's partial Pc[c][k][q].
+template <class XL, int NB, bool VEC>
+static __device__ __forceinline__ void k_als_xtw_body(const typename XL::T *X, const int4 *segs, const int *chunk_seg, int K, int r,
+                                                      const double *A64, const double *B64, double *Pc) {
+    __shared__ float red[3][NB * 16][64];
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int rsub = lane >> 4, c16 = lane & 15;
+    const int c = blockIdx.x, kb = blockIdx.y, col = 64 * kb + 4 * c16;
+    f32x4 acc[4][NB];
+#pragma unroll
+    for (int m = 0; m < 4; ++m)
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) acc[m][nb] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int s_beg = chunk_seg[c], s_end = chunk_seg[c + 1];
+    // the next segment's X rows and B / a values are in flight while the current one is multiplied (loads unconditional:
+    // rows clamped into the segment, invalid rows and columns get a zero weight)
+    f32x4 xn[4];
+    double bn[4][NB], an[NB];
+    int nn = 0;
+    auto load = [&](int s) {
+        const int4 sg = segs[s];
+        const int row0 = sg.y, j0 = sg.w;
+        nn = sg.z;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int loc = min(4 * (w + 4 * u) + rsub, nn - 1);
+            xn[u] = als_ld4<XL, VEC>(X + (long)(row0 + loc) * K + col, col, K);
+#pragma unroll
+            for (int nb = 0; nb < NB; ++nb) bn[u][nb] = B64[(long)(j0 + loc) * r + min(16 * nb + c16, r - 1)];
+        }
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) an[nb] = A64[(long)sg.x * r + min(16 * nb + c16, r - 1)];
+    };
+    if (s_beg < s_end) load(s_beg);
+    for (int s = s_beg; s < s_end; ++s) {
+        f32x4 x[4];
+        float wv[4][NB];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const bool ok = 4 * (w + 4 * u) + rsub < nn;
+            x[u] = xn[u];
+#pragma unroll
+            for (int nb = 0; nb < NB; ++nb) wv[u][nb] = (ok && 16 * nb + c16 < r) ? (float)(bn[u][nb] * an[nb]) : 0.f;
+        }
+        if (s + 1 < s_end) load(s + 1);
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int m = 0; m < 4; ++m)
+#pragma unroll
+                for (int nb = 0; nb < NB; ++nb) acc[m][nb] = MFMA16(x[u][m], wv[u][nb], acc[m][nb]);
+    }
+    if (w > 0)
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+#pragma unroll
+            for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+                for (int v = 0; v < 4; ++v) red[w - 1][(m * NB + nb) * 4 + v][lane] = acc[m][nb][v];
+    __syncthreads();
+    if (w > 0) return;
+#pragma unroll
+    for (int m = 0; m < 4; ++m)
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                const int e = (m * NB + nb) * 4 + v;
+                const double s = ((double)acc[m][nb][v] + (double)red[0][e][lane]) + ((double)red[1][e][lane] + (double)red[2][e][lane]);
+                const int k = 64 * kb + 4 * (4 * (lane >> 4) + v) + m, q = 16 * nb + (lane & 15);
+                if (k < K && q < r) Pc[((long)c * K + k) * r + q] = s;
+            }
+}
+template <int NB, bool VEC>
+__global__ __launch_bounds__(256) void k_als_xtw(const float *__restrict__ X, const int4 *__restrict__ segs, const int *__restrict__ chunk_seg,
+                                                 int K, int r, const double *__restrict__ A64, const double *__restrict__ B64,
+                                                 double *__restrict__ Pc) {
+    k_als_xtw_body<XF32, NB, VEC>(X, segs, chunk_seg, K, r, A64, B64, Pc);
+}
+// the 16-bit twin (xload.h): the same template arguments after the element type
+template <class XL, int NB, bool VEC>
+__global__ __launch_bounds__(256) void k_als_xtw_h(const typename XL::T *__restrict__ X, const int4 *__restrict__ segs,
+                                                   const int *__restrict__ chunk_seg, int K, int r, const double *__restrict__ A64,
+                                                   const double *__restrict__ B64, double *__restrict__ Pc) {
+    k_als_xtw_body<XL, NB, VEC>(X, segs, chunk_seg, K, r, A64, B64, Pc);
+}
+
+// ---- start: the padded-row Gram matrix P = sum_i X~_i X~_i^T [Jmax, Jmax] (fp64 sums of exact products) ----------------------
+// 32 x 32 output tile per workgroup, upper triangle of tiles (mirrored); slabs in ascending order, then columns.
+template <class XL>
+static __device__ __forceinline__ void k_als_rowgram_body(const typename XL::T *X, const int *ext, int I, int K, int Jm, double *P) {
+    if (blockIdx.y < blockIdx.x) return;
+    __shared__ float As[32][33], Bs[32][33];
+    const int a0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
+    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+    double acc[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
+    for (int i = 0; i < I; ++i) {
+        const long s0 = ext[i];
+        const int n = ext[i + 1] - ext[i];
+        if (n <= a0) continue;  // (c0 >= a0) the slab has no row in the tile's first range
+        for (int k0 = 0; k0 < K; k0 += 32) {
+            __syncthreads();
+            for (int e = threadIdx.x; e < 32 * 32; e += 256) {
+                const int jj = e >> 5, kk = e & 31;
+                const bool okk = k0 + kk < K;
+                As[kk][jj] = (okk && a0 + jj < n) ? XL::ld1(X + (s0 + a0 + jj) * K + k0 + kk) : 0.f;
+                Bs[kk][jj] = (okk && c0 + jj < n) ? XL::ld1(X + (s0 + c0 + jj) * K + k0 + kk) : 0.f;
+            }
+            __syncthreads();
+#pragma unroll 8
+            for (int kk = 0; kk < 32; ++kk) {
+                const double a_0 = (double)As[kk][2 * ty], a_1 = (double)As[kk][2 * ty + 1];
+                const double b_0 = (double)Bs[kk][2 * tx], b_1 = (double)Bs[kk][2 * tx + 1];
+                acc[0][0] = fma(a_0, b_0, acc[0][0]), acc[0][1] = fma(a_0, b_1, acc[0][1]);
+                acc[1][0] = fma(a_1, b_0, acc[1][0]), acc[1][1] = fma(a_1, b_1, acc[1][1]);
+            }
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+        for (int v = 0; v < 2; ++v) {
+            const int a = a0 + 2 * ty + u, c = c0 + 2 * tx + v;
+            if (a < Jm && c < Jm) P[(long)a * Jm + c] = acc[u][v], P[(long)c * Jm + a] = acc[u][v];
+        }
+}
+__global__ __launch_bounds__(256) void k_als_rowgram(const float *__restrict__ X, const int *__restrict__ ext, int I, int K, int Jm,
+                                                     double *__restrict__ P) {
+    k_als_rowgram_body<XF32>(X, ext, I, K, Jm, P);
+}
+// the 16-bit twin (xload.h): the same template arguments after the element type
+template <class XL>
+__global__ __launch_bounds__(256) void k_als_rowgram_h(const typename XL::T *__restrict__ X, const int *__restrict__ ext, int I, int K,
+                                                       int Jm, double *__restrict__ P) {
+    k_als_rowgram_body<XL>(X, ext, I, K, Jm, P);
+}
+
+// |X|^2 = trace(P), in row order
+__global__ void k_als_trace(const double *__restrict__ P, int Jm, double *__restrict__ nx2) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    double s = 0.0;
+    for (int j = 0; j < Jm; ++j) s += P[(long)j * Jm + j];
+    *nx2 = s;
+}
+
+// M_B partials: Pb[g][j][q] = sum over the slabs i of group g (ascending) with J_i > j of a_i[q] XC[row of (i, j)][q]
+__global__ __launch_bounds__(256) void k_als_mb(const float *__restrict__ XC, const double *__restrict__ A64, const int *__restrict__ ext,
+                                                const int *__restrict__ bgrp, int ngrp, int Jm, int r, double *__restrict__ Pb) {
+    const long e = (long)blockIdx.x * 256 + threadIdx.x, E = (long)Jm * r;
+    if (e >= E * ngrp) return;
+    const int gidx = (int)(e / E);
+    const int rem = (int)(e - (long)gidx * E), j = rem / r, q = rem - j * r;
+    double s = 0.0;
+#pragma unroll 8
+    for (int i = bgrp[gidx]; i < bgrp[gidx + 1]; ++i) {  // (rows past J_i: a clamped load, weight 0)
+        const int s0 = ext[i], n = ext[i + 1] - s0;
+        const double a = n > j ? A64[(long)i * r + q] : 0.0;
+        s = fma(a, (double)XC[(n > 0 ? (long)s0 + min(j, n - 1) : 0L) * r + q], s);
+    }
+    Pb[e] = s;
+}
+
+// M_A[i][q] = sum of the partials of the segments of slab i, in segment order
+__global__ __launch_bounds__(256) void k_als_segsum(const double *__restrict__ Pa, const int *__restrict__ slab_seg, int I, int r,
+                                                    double *__restrict__ Ma) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= I * r) return;
+    const int i = e / r, q = e - i * r;
+    double s = 0.0;
+    for (int g = slab_seg[i]; g < slab_seg[i + 1]; ++g) s += Pa[(long)g * r + q];
+    Ma[e] = s;
+}
+
+// out[e] = sum_p part[p][e].  64 elements per workgroup; thread quarter w sums the parts p = w (mod 4) in ascending order, the
+// quarters are combined as (s0 + s1) + (s2 + s3)
+__global__ __launch_bounds__(256) void k_als_reduce(const double *__restrict__ part, int np, long E, double *__restrict__ out) {
+    __shared__ double red[4][64];
+    const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+    const long e = (long)blockIdx.x * 64 + l;
+    double s = 0.0;
+    if (e < E) {
+#pragma unroll 8
+        for (int p = w; p < np; p += 4) s += part[(long)p * E + e];
+    }
+    red[w][l] = s;
+    __syncthreads();
+    if (w == 0 && e < E) out[e] = (red[0][l] + red[1][l]) + (red[2][l] + red[3][l]);
+}
+
+// ---- the row update of one mode (one thread per row of F, 64 rows per workgroup) -------------------------------------------------
+// op LOAD: F = the fp32 start (NULL: ones); ALS: F = M Ginv; HALS: one pass over the columns.  Then every workgroup writes its
+// partial Gram matrix sum_rows F^T F (fp64, rows in order); mode C also its part of <M_C, C> and the fp32 fragments of C.
+struct AlsUpd {
+    int mode, op, n, r, NB;
+    const double *M;      // [n, r]
+    const float *F32;     // LOAD
+    const double *Gm;     // [r, r]: G^-1 (ALS) or G (HALS)
+    double *F64, *Gp, *Ep;
+    float *Cfrag;
+};
+
+template <int RMAX>
+__global__ __launch_bounds__(64) void k_als_update(AlsUpd u) {
+    __shared__ double buf[64 * (RMAX + 1)];  // G (r x r) during the update, then the rows (64 x (RMAX + 1)) for the Gram partial
+    __shared__ double ep[64];
+    const int tid = threadIdx.x, row = blockIdx.x * 64 + tid, r = u.r;
+    const bool ok = row < u.n;
+    double *Gs = buf;
+    if (u.op != OP_LOAD)
+        for (int e = tid; e < r * r; e += 64) Gs[e] = u.Gm[e];
+    __syncthreads();
+    double m[RMAX], f[RMAX];
+#pragma unroll
+    for (int q = 0; q < RMAX; ++q) m[q] = 0.0, f[q] = 0.0;
+    if (ok && u.op != OP_LOAD)
+#pragma unroll
+        for (int q = 0; q < RMAX; ++q)
+            if (q < r) m[q] = u.M[(long)row * r + q];
+    if (ok) {
+        if (u.op == OP_LOAD) {
+#pragma unroll
+            for (int q = 0; q < RMAX; ++q)
+                if (q < r) f[q] = u.F32 ? (double)u.F32[(long)row * r + q] : 1.0;
+        } else if (u.op == OP_ALS) {
+#pragma unroll
+            for (int q = 0; q < RMAX; ++q) {
+                double s = 0.0;
+#pragma unroll
+                for (int p = 0; p < RMAX; ++p)
+                    if (p < r && q < r) s = fma(m[p], Gs[p * r + q], s);
+                f[q] = s;
+            }
+        } else {
+#pragma unroll
+            for (int q = 0; q < RMAX; ++q)
+                if (q < r) f[q] = u.F64[(long)row * r + q];
+#pragma unroll
+            for (int q = 0; q < RMAX; ++q) {
+                if (q >= r) continue;
+                const double gqq = Gs[q * r + q];
+                if (gqq == 0.0) continue;
+                double s = m[q];
+#pragma unroll
+                for (int p = 0; p < RMAX; ++p)
+                    if (p < r) s = fma(-f[p], Gs[p * r + q], s);
+                f[q] = fmax(0.0, f[q] + s / gqq);
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < RMAX; ++q)
+            if (q < r) u.F64[(long)row * r + q] = f[q];
+        if (u.mode == 2) {
+            const int h = row >> 4, g = (row >> 2) & 3, kq = row & 3;
+#pragma unroll
+            for (int q = 0; q < RMAX; ++q)
+                if (q < r) u.Cfrag[(((long)h * u.NB + (q >> 4)) * 64 + g * 16 + (q & 15)) * 4 + kq] = (float)f[q];
+        }
+    }
+    __syncthreads();  // (G is no longer read)
+    double(*Fs)[RMAX + 1] = reinterpret_cast<double(*)[RMAX + 1]>(buf);
+#pragma unroll
+    for (int q = 0; q < RMAX; ++q) Fs[tid][q] = f[q];
+    if (u.mode == 2) {
+        double d = 0.0;
+#pragma unroll
+        for (int q = 0; q < RMAX; ++q) d = fma(m[q], f[q], d);
+        ep[tid] = d;
+    }
+    __syncthreads();
+    if (u.mode == 2 && tid == 0) {
+        double d = 0.0;
+#pragma unroll 16
+        for (int t = 0; t < 64; ++t) d += ep[t];
+        u.Ep[blockIdx.x] = d;
+    }
+    for (int e = tid; e < r * r; e += 64) {
+        const int a = e / r, c = e - a * r;
+        double s = 0.0;
+#pragma unroll 16
+        for (int t = 0; t < 64; ++t) s = fma(Fs[t][a], Fs[t][c], s);
+        u.Gp[(long)blockIdx.x * r * r + e] = s;
+    }
+}
+
+// ---- r x r work between the updates (one workgroup) ------------------------------------------------------------------------
+// prev >= 0: Gram[prev] = the sum of the partial Gram matrices of the factor just updated.  t >= 0 (after mode C): the error
+// e_t.  next >= 0: G_next = the Hadamard product of the other two Gram matrices; ALS: its inverse (pseudo-inverse when it is
+// not positive definite), HALS: G itself, into Gm.
+struct AlsPrep {
+    int prev, nprev, next, method, t, r, nEp;
+    const double *Gp;
+    double *Gram;  // [3][r * r]
+    double *Gm;
+    const double *Ep, *nx2;
+    double *ews, *errors;
+};
+
+__global__ __launch_bounds__(256) void k_als_prep(AlsPrep p) {
+    extern __shared__ double sm[];
+    const int r = p.r, rr = r * r, tid = threadIdx.x;
+    double *S = sm, *W = S + rr, *cs = W + rr;
+    __shared__ int fail_sh;
+    if (p.prev >= 0)
+        for (int e = tid; e < rr; e += 256) {
+            double s = 0.0;
+            for (int w = 0; w < p.nprev; ++w) s += p.Gp[(long)w * rr + e];
+            p.Gram[p.prev * rr + e] = s;
+        }
+    __threadfence_block();
+    __syncthreads();
+    if (p.t >= 0) {  // 1^T (A^T A o B^T B o C^T C) 1 and <M_C, C>: per-thread sums in index order, then a fixed tree
+        __shared__ double fit_sh[256], dot_sh[256];
+        double fit = 0.0, d = 0.0;
+        for (int e = tid; e < rr; e += 256) fit += p.Gram[e] * p.Gram[rr + e] * p.Gram[2 * rr + e];
+        for (int w = tid; w < p.nEp; w += 256) d += p.Ep[w];
+        fit_sh[tid] = fit, dot_sh[tid] = d;
+        __syncthreads();
+        for (int o = 128; o > 0; o >>= 1) {
+            if (tid < o) fit_sh[tid] += fit_sh[tid + o], dot_sh[tid] += dot_sh[tid + o];
+            __syncthreads();
+        }
+        if (tid == 0) {
+            const double nx2 = *p.nx2;
+            const double err = nx2 > 0.0 ? sqrt(fmax(0.0, nx2 - 2.0 * dot_sh[0] + fit_sh[0])) / sqrt(nx2) : 0.0;
+            p.ews[0] = err;
+            if (p.errors) p.errors[p.t] = err;
+        }
+    }
+    if (p.next < 0) return;
+    const int o1 = p.next == 0 ? 1 : 0, o2 = p.next == 2 ? 1 : 2;
+    for (int e = tid; e < rr; e += 256) S[e] = p.Gram[o1 * rr + e] * p.Gram[o2 * rr + e];
+    if (tid == 0) fail_sh = 0;
+    __syncthreads();
+    if (p.method == 1) {
+        for (int e = tid; e < rr; e += 256) p.Gm[e] = S[e];
+        return;
+    }
+    // in-place Gauss-Jordan without pivoting (SPD: every pivot is positive), in the first wave only: its LDS operations complete
+    // in order, so the two phases of a pivot need no workgroup barrier
+    if (tid < 64)
+        for (int q = 0; q < r; ++q) {
+            const double piv = S[q * r + q];
+            if (!(piv > 0.0) || !isfinite(piv)) {
+                if (tid == 0) fail_sh = 1;
+                break;
+            }
+            const double d = 1.0 / piv;
+            for (int e = tid; e < rr; e += 64) {
+                const int a = e / r, c = e - a * r;
+                if (a != q && c != q) S[e] = fma(-S[a * r + q] * d, S[q * r + c], S[e]);
+            }
+            __builtin_amdgcn_wave_barrier();
+            for (int e = tid; e < 2 * r; e += 64) {
+                const int k = e < r ? e : e - r;
+                if (k == q) {
+                    if (e == q) S[q * r + q] = d;
+                } else if (e < r) {
+                    S[q * r + k] *= d;
+                } else {
+                    S[k * r + q] *= -d;
+                }
+            }
+            __builtin_amdgcn_wave_barrier();
+        }
+    __syncthreads();
+    if (fail_sh) {  // pseudo-inverse: G = W diag(lam) W^T, 1 / lam for lam > 1e-12 lam_max
+        for (int e = tid; e < rr; e += 256) S[e] = p.Gram[o1 * rr + e] * p.Gram[o2 * rr + e];
+        __syncthreads();
+        jacobi_lds(S, W, cs, r);
+        double lmax = 0.0;
+        for (int k = 0; k < r; ++k) lmax = fmax(lmax, S[k * r + k]);
+        for (int e = tid; e < rr; e += 256) {
+            const int a = e / r, c = e - a * r;
+            double s = 0.0;
+            for (int k = 0; k < r; ++k) {
+                const double l = S[k * r + k];
+                if (l > 1e-12 * lmax) s += W[a * r + k] * W[c * r + k] / l;
+            }
+            p.Gm[e] = s;
+        }
+        return;
+    }
+    for (int e = tid; e < rr; e += 256) p.Gm[e] = S[e];
+}
+
+// outputs in fp32: A, B packed along the rows of X (B_i = B[:J_i]), C
+__global__ __launch_bounds__(256) void k_als_out(const double *__restrict__ A64, const double *__restrict__ B64, const double *__restrict__ C64,
+                                                 const int *__restrict__ ext, int I, int N, int K, int r, float *__restrict__ A,
+                                                 float *__restrict__ B, float *__restrict__ C) {
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (blockIdx.y == 0) {
+        if (e >= (long)N * r) return;
+        const int row = (int)(e / r), q = (int)(e - (long)row * r);
+        int lo = 0, hi = I;  // the slab of the row: ext[lo] <= row < ext[lo + 1]
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (ext[mid] <= row) lo = mid;
+            else hi = mid;
+        }
+        B[e] = (float)B64[(long)(row - ext[lo]) * r + q];
+    } else if (blockIdx.y == 1) {
+        if (e < (long)I * r) A[e] = (float)A64[e];
+    } else {
+        if (e < (long)K * r) C[e] = (float)C64[e];
+    }
+}
+
+struct AlsPlan {
+    int64_t N, Jm;
+    int nseg, nchunk, nkb, ngrp, NB, KH, wgA, wgB, wgC;
+    int64_t off_segs, off_slab_seg, off_chunk_seg, off_ext, off_bgrp, off_A, off_B, off_C, off_Cfrag, off_XC, off_Pa, off_Pb, off_Mb,
+        off_Pc, off_Mc, off_Ma, off_Gp, off_Ep, off_Gram, off_Gm, off_small, off_info, off_scratch;
+    int64_t svd_ws, gv_ws, scratch, total;
+};
+
+AlsPlan als_plan(const int64_t *row_ptr, int64_t I, int64_t K, int rank) {
+    AlsPlan p{};
+    p.N = row_ptr[I];
+    p.Jm = 0;
+    int64_t nseg = 0;
+    for (int64_t i = 0; i < I; ++i) {
+        const int64_t J = row_ptr[i + 1] - row_ptr[i];
+        p.Jm = std::max(p.Jm, J);
+        nseg += (J + ALS_SEG - 1) / ALS_SEG;
+    }
+    const int64_t r = rank;
+    p.nseg = (int)nseg;
+    p.nkb = (int)((K + 63) / 64);
+    p.nchunk = (int)std::max<int64_t>(1, std::min<int64_t>(nseg, ALS_TARGET_WG / p.nkb));
+    p.ngrp = (int)std::max<int64_t>(1, std::min<int64_t>(I, (262144 + p.Jm * r - 1) / std::max<int64_t>(p.Jm * r, 1)));
+    p.NB = als_nb(rank);
+    p.KH = 4 * (int)((K + 63) / 64);  // 16-row blocks of the C fragments, whole 64-column chunks (zero past K)
+    p.wgA = (int)((I + 63) / 64), p.wgB = (int)((p.Jm + 63) / 64), p.wgC = (int)((K + 63) / 64);
+    const int wgmax = std::max(p.wgA, std::max(p.wgB, p.wgC));
+    int64_t off = 0;
+    auto take = [&](int64_t bytes) {
+        const int64_t o = off;
+        off = (off + std::max<int64_t>(bytes, 1) + 255) & ~int64_t(255);
+        return o;
+    };
+    p.off_segs = take(std::max<int64_t>(nseg, 1) * 16);
+    p.off_slab_seg = take((I + 1) * 4);
+    p.off_chunk_seg = take((int64_t)(p.nchunk + 1) * 4);
+    p.off_ext = take((I + 1) * 4);
+    p.off_bgrp = take((int64_t)(p.ngrp + 1) * 4);
+    p.off_A = take(I * r * 8);
+    p.off_B = take(p.Jm * r * 8);
+    p.off_C = take(K * r * 8);
+    p.off_Cfrag = take((int64_t)p.KH * p.NB * 64 * 4 * 4);
+    p.off_XC = take(p.N * r * 4);
+    p.off_Pa = take(std::max<int64_t>(nseg, 1) * r * 8);
+    p.off_Pb = take((int64_t)p.ngrp * p.Jm * r * 8);
+    p.off_Mb = take(p.Jm * r * 8);
+    p.off_Pc = take((int64_t)p.nchunk * K * r * 8);
+    p.off_Mc = take(K * r * 8);
+    p.off_Ma = take(I * r * 8);
+    p.off_Gp = take((int64_t)3 * wgmax * r * r * 8);
+    p.off_Ep = take((int64_t)p.wgC * 8);
+    p.off_Gram = take(3 * r * r * 8);
+    p.off_Gm = take(r * r * 8);
+    p.off_small = take(4 * 8);  // |X|^2, e_t
+    p.off_info = take((I + 2) * 4);
+    p.off_scratch = off;
+    // the start: mcl_svd_init's workspace + C0 (fp32), then P [Jmax, Jmax] + the subspace iteration's + B0 (fp32)
+    p.svd_ws = (mcl_svd_stack_workspace_bytes(row_ptr, I, K, rank) + 255) & ~int64_t(255);
+    p.gv_ws = (mcl_gram_vectors_workspace_bytes(p.Jm, rank) + 255) & ~int64_t(255);
+    const int64_t s1 = p.svd_ws + ((K * r * 4 + 255) & ~int64_t(255));
+    const int64_t s2 = ((p.Jm * p.Jm * 8 + 255) & ~int64_t(255)) + p.gv_ws + ((p.Jm * r * 4 + 255) & ~int64_t(255));
+    p.scratch = std::max(s1, s2);
+    p.total = off + p.scratch;
+    return p;
+}
+
+template <int RMAX>
+void launch_update(const AlsUpd &u, hipStream_t s) {
+    hipLaunchKernelGGL(k_als_update<RMAX>, dim3((unsigned)((u.n + 63) / 64)), dim3(64), 0, s, u);
+}
+
+void update(AlsUpd u, hipStream_t s) {
+    if (u.r <= 16) launch_update<16>(u, s);
+    else if (u.r <= 32) launch_update<32>(u, s);
+    else launch_update<64>(u, s);
+}
+
+template <class XL, int NB, bool VEC>
+void launch_passes(bool second, const typename XL::T *X, const AlsPlan &p, const int4 *segs, const int *chunk_seg, int K, int r,
+                   const float *Cfrag, const double *A64, const double *B64, float *XC, double *Pa, double *Pc, hipStream_t s) {
+    if (!second)
+        hipLaunchKernelGGL((MCL_XKERNEL(k_als_xc, NB, VEC)), dim3((unsigned)((p.nseg + 3) / 4)), dim3(256), 0, s, X, segs, p.nseg, K, r, Cfrag,
+                           B64, XC, Pa);
+    else
+        hipLaunchKernelGGL((MCL_XKERNEL(k_als_xtw, NB, VEC)), dim3((unsigned)p.nchunk, (unsigned)p.nkb), dim3(256), 0, s, X, segs, chunk_seg, K,
+                           r, A64, B64, Pc);
+}
+
+template <class XL, int NB>
+void passes_nb(bool second, bool vec, const typename XL::T *X, const AlsPlan &p, const int4 *segs, const int *chunk_seg, int K, int r,
+               const float *Cfrag, const double *A64, const double *B64, float *XC, double *Pa, double *Pc, hipStream_t s) {
+    if (vec) launch_passes<XL, NB, true>(second, X, p, segs, chunk_seg, K, r, Cfrag, A64, B64, XC, Pa, Pc, s);
+    else launch_passes<XL, NB, false>(second, X, p, segs, chunk_seg, K, r, Cfrag, A64, B64, XC, Pa, Pc, s);
+}
+
+template <class XL>
+int als_init(const typename XL::T *X, int32_t x_type, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank, int32_t method,
+             int32_t n_iter_max, double tol, float *A, float *B, float *C, double *errors, int32_t *info, void *workspace,
+             int64_t workspace_bytes, void *hip_stream) {
+    auto fail = [](const std::string &msg) {
+        g_als_error = msg;
+        return 1;
+    };
+    const AlsPlan p = als_plan(row_ptr, I, K, rank);
+    if (workspace_bytes < p.total) return fail("mcl_als_init: workspace too small (mcl_als_init_workspace_bytes)");
+    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail("mcl_als_init: workspace must be 256-byte aligned");
+    hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+    char *ws = static_cast<char *>(workspace);
+    auto at = [&](int64_t off) { return static_cast<void *>(ws + off); };
+    int4 *segs = static_cast<int4 *>(at(p.off_segs));
+    int *slab_seg = static_cast<int *>(at(p.off_slab_seg)), *chunk_seg = static_cast<int *>(at(p.off_chunk_seg));
+    int *ext = static_cast<int *>(at(p.off_ext)), *bgrp = static_cast<int *>(at(p.off_bgrp));
+    double *A64 = static_cast<double *>(at(p.off_A)), *B64 = static_cast<double *>(at(p.off_B)), *C64 = static_cast<double *>(at(p.off_C));
+    float *Cfrag = static_cast<float *>(at(p.off_Cfrag)), *XC = static_cast<float *>(at(p.off_XC));
+    double *Pa = static_cast<double *>(at(p.off_Pa)), *Pb = static_cast<double *>(at(p.off_Pb)), *Mb = static_cast<double *>(at(p.off_Mb));
+    double *Pc = static_cast<double *>(at(p.off_Pc)), *Mc = static_cast<double *>(at(p.off_Mc)), *Ma = static_cast<double *>(at(p.off_Ma));
+    double *Gp = static_cast<double *>(at(p.off_Gp)), *Ep = static_cast<double *>(at(p.off_Ep));
+    double *Gram = static_cast<double *>(at(p.off_Gram)), *Gm = static_cast<double *>(at(p.off_Gm));
+    double *nx2 = static_cast<double *>(at(p.off_small)), *ews = nx2 + 1;
+    int *sinfo = static_cast<int *>(at(p.off_info));
+    char *scr = ws + p.off_scratch;
+    const int r = rank, Jm = (int)p.Jm, N = (int)p.N;
+    const int wgmax = std::max(p.wgA, std::max(p.wgB, p.wgC));
+    double *GpM[3] = {Gp, Gp + (int64_t)wgmax * r * r, Gp + (int64_t)2 * wgmax * r * r};
+    const int nwg[3] = {p.wgA, p.wgB, p.wgC};
+
+    // host-built tables: segments, per-slab segment ranges, row chunks of pass 2, slab groups of M_B
+    std::vector<int4> h_segs;
+    std::vector<int> h_slab_seg(1, 0), h_ext((size_t)I + 1), h_chunk((size_t)p.nchunk + 1), h_bgrp((size_t)p.ngrp + 1);
+    for (int64_t i = 0; i < I; ++i) {
+        const int J = (int)(row_ptr[i + 1] - row_ptr[i]);
+        for (int j0 = 0; j0 < J; j0 += ALS_SEG) h_segs.push_back(int4{(int)i, (int)row_ptr[i] + j0, std::min(ALS_SEG, J - j0), j0});
+        h_slab_seg.push_back((int)h_segs.size());
+    }
+    if (h_segs.empty()) h_segs.push_back(int4{0, 0, 0, 0});
+    for (int64_t i = 0; i <= I; ++i) h_ext[(size_t)i] = (int)row_ptr[i];
+    for (int c = 0; c <= p.nchunk; ++c) h_chunk[(size_t)c] = (int)((int64_t)p.nseg * c / p.nchunk);
+    for (int g = 0; g <= p.ngrp; ++g) h_bgrp[(size_t)g] = (int)(I * g / p.ngrp);
+#define ALS_HIP(expr)                                                                   \
+    do {                                                                                \
+        const hipError_t e_ = (expr);                                                   \
+        if (e_ != hipSuccess) return fail(std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+    ALS_HIP(hipMemcpyAsync(segs, h_segs.data(), sizeof(int4) * h_segs.size(), hipMemcpyHostToDevice, s));
+    ALS_HIP(hipMemcpyAsync(slab_seg, h_slab_seg.data(), sizeof(int) * h_slab_seg.size(), hipMemcpyHostToDevice, s));
+    ALS_HIP(hipMemcpyAsync(ext, h_ext.data(), sizeof(int) * h_ext.size(), hipMemcpyHostToDevice, s));
+    ALS_HIP(hipMemcpyAsync(chunk_seg, h_chunk.data(), sizeof(int) * h_chunk.size(), hipMemcpyHostToDevice, s));
+    ALS_HIP(hipMemcpyAsync(bgrp, h_bgrp.data(), sizeof(int) * h_bgrp.size(), hipMemcpyHostToDevice, s));
+    ALS_HIP(hipMemsetAsync(Cfrag, 0, (size_t)p.KH * p.NB * 64 * 4 * 4, s));
+    ALS_HIP(hipStreamSynchronize(s));  // (the tables are locals)
+
+    const int hals = method == MCL_ALS_CP_HALS;
+    // ---- start.  C0: the C of mcl_svd_init
+    float *C32 = reinterpret_cast<float *>(scr + p.svd_ws);
+    std::string err;
+    if (mcl_svd_stack_right(X, x_type, row_ptr, I, K, rank, hals, C32, scr, p.svd_ws, sinfo, s, err)) return fail(err);
+    AlsUpd u{};
+    u.r = r, u.NB = p.NB, u.op = OP_LOAD;
+    u.mode = 2, u.n = (int)K, u.F32 = C32, u.F64 = C64, u.Gp = GpM[2], u.Ep = Ep, u.Cfrag = Cfrag;
+    update(u, s);
+    // B0: the leading eigenvectors of the padded-row Gram matrix
+    double *P = reinterpret_cast<double *>(scr);
+    char *gv = scr + ((p.Jm * p.Jm * 8 + 255) & ~int64_t(255));
+    float *B32 = reinterpret_cast<float *>(gv + p.gv_ws);
+    const unsigned tj = (unsigned)((Jm + 31) / 32);
+    hipLaunchKernelGGL((MCL_XKERNEL0(k_als_rowgram)), dim3(tj, tj), dim3(256), 0, s, X, (const int *)ext, (int)I, (int)K, Jm, P);
+    hipLaunchKernelGGL(k_als_trace, dim3(1), dim3(64), 0, s, (const double *)P, Jm, nx2);
+    if (mcl_gram_vectors(P, p.Jm, rank, hals, B32, gv, sinfo, (int)I + 1, s, err)) return fail(err);
+    u.mode = 1, u.n = Jm, u.F32 = B32, u.F64 = B64, u.Gp = GpM[1];
+    update(u, s);
+    u.mode = 0, u.n = (int)I, u.F32 = nullptr, u.F64 = A64, u.Gp = GpM[0];  // A0 = 1
+    update(u, s);
+
+    const int rr = r * r;
+    const size_t psm = sizeof(double) * (size_t)(2 * rr + 2 * (r / 2 + 2)) + 64;
+    ALS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_als_prep), hipFuncAttributeMaxDynamicSharedMemorySize, (int)psm));
+    auto prep = [&](int prev, int next, int t) {
+        AlsPrep q{};
+        q.prev = prev, q.nprev = prev >= 0 ? nwg[prev] : 0, q.next = next, q.method = hals, q.t = t, q.r = r, q.nEp = p.wgC;
+        q.Gp = prev >= 0 ? GpM[prev] : nullptr, q.Gram = Gram, q.Gm = Gm, q.Ep = Ep, q.nx2 = nx2, q.ews = ews, q.errors = errors;
+        hipLaunchKernelGGL(k_als_prep, dim3(1), dim3(256), psm, s, q);
+    };
+    prep(1, -1, -1);
+    prep(0, -1, -1);
+    prep(2, 0, -1);
+    ALS_HIP(hipGetLastError());
+
+    const bool vec = (K % 4 == 0) && (reinterpret_cast<uintptr_t>(X) & (x_type == MCL_X_F32 ? 15 : 7)) == 0;
+    auto pass = [&](bool second) {
+        if (p.NB == 1) passes_nb<XL, 1>(second, vec, X, p, segs, chunk_seg, (int)K, r, Cfrag, A64, B64, XC, Pa, Pc, s);
+        else if (p.NB == 2) passes_nb<XL, 2>(second, vec, X, p, segs, chunk_seg, (int)K, r, Cfrag, A64, B64, XC, Pa, Pc, s);
+        else passes_nb<XL, 4>(second, vec, X, p, segs, chunk_seg, (int)K, r, Cfrag, A64, B64, XC, Pa, Pc, s);
+    };
+    const int op = hals ? OP_HALS : OP_ALS;
+    double e_prev = 0.0;
+    int used = 0;
+    for (int t = 0; t < n_iter_max; ++t) {
+        pass(false);  // XC, M_A partials
+        u = AlsUpd{};
+        u.r = r, u.NB = p.NB, u.op = op, u.Gm = Gm, u.Ep = Ep, u.Cfrag = Cfrag;
+        hipLaunchKernelGGL(k_als_segsum, dim3((unsigned)((I * r + 255) / 256)), dim3(256), 0, s, (const double *)Pa, (const int *)slab_seg,
+                           (int)I, r, Ma);
+        u.mode = 0, u.n = (int)I, u.M = Ma, u.F64 = A64, u.Gp = GpM[0];
+        update(u, s);
+        const long EB = (long)Jm * r;
+        hipLaunchKernelGGL(k_als_mb, dim3((unsigned)((EB * p.ngrp + 255) / 256)), dim3(256), 0, s, (const float *)XC, (const double *)A64,
+                           (const int *)ext, (const int *)bgrp, p.ngrp, Jm, r, Pb);
+        hipLaunchKernelGGL(k_als_reduce, dim3((unsigned)((EB + 63) / 64)), dim3(256), 0, s, (const double *)Pb, p.ngrp, EB, Mb);
+        prep(0, 1, -1);
+        u.mode = 1, u.n = Jm, u.M = Mb, u.F64 = B64, u.Gp = GpM[1];
+        update(u, s);
+        prep(1, 2, -1);
+        pass(true);  // M_C partials
+        const long EC = (long)K * r;
+        hipLaunchKernelGGL(k_als_reduce, dim3((unsigned)((EC + 63) / 64)), dim3(256), 0, s, (const double *)Pc, p.nchunk, EC, Mc);
+        u.mode = 2, u.n = (int)K, u.M = Mc, u.F64 = C64, u.Gp = GpM[2];
+        update(u, s);
+        prep(2, 0, t);
+        ALS_HIP(hipGetLastError());
+        used = t + 1;
+        if (tol > 0.0) {  // TensorLy's abs_rec_error rule: one 8-byte read per sweep
+            double e_t = 0.0;
+            ALS_HIP(hipMemcpyAsync(&e_t, ews, sizeof(double), hipMemcpyDeviceToHost, s));
+            ALS_HIP(hipStreamSynchronize(s));
+            if (t >= 1 && std::fabs(e_prev - e_t) < tol) break;
+            e_prev = e_t;
+        }
+    }
+    const long big = std::max<long>((long)N, std::max<long>((long)I, (long)K)) * r;
+    hipLaunchKernelGGL(k_als_out, dim3((unsigned)((big + 255) / 256), 3), dim3(256), 0, s, (const double *)A64, (const double *)B64,
+                       (const double *)C64, (const int *)ext, (int)I, N, (int)K, r, A, B, C);
+    ALS_HIP(hipGetLastError());
+    ALS_HIP(hipMemcpyAsync(info, &used, sizeof(int32_t), hipMemcpyHostToDevice, s));
+    ALS_HIP(hipStreamSynchronize(s));  // (`used` is a local)
+#undef ALS_HIP
+    return 0;
+}
+
+std::string check_args(const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank) {
+    if (!row_ptr || I < 1 || K < 1) return "need row_ptr, I >= 1, K >= 1";
+    if (rank < 1 || rank > MCL_MAX_RANK) return "need 1 <= rank <= 64";
+    if (row_ptr[0] != 0) return "row_ptr[0] must be 0";
+    int64_t Jm = 0;
+    for (int64_t i = 0; i < I; ++i) {
+        if (row_ptr[i + 1] < row_ptr[i]) return "row_ptr must be non-decreasing";
+        Jm = std::max(Jm, row_ptr[i + 1] - row_ptr[i]);
+    }
+    if (K > 2048 || Jm > 2048) return "K and the longest matrix must be at most 2048 (the start's Gram matrices)";
+    if (rank > K || rank > Jm) return "rank exceeds min(longest matrix, K)";
+    if (row_ptr[I] >= (int64_t(1) << 31)) return "more than 2^31 packed rows are not supported";
+    return "";
+}
+
+}  // namespace
+
+extern "C" {
+
+const char *mcl_als_init_last_error(void) { return g_als_error.c_str(); }
+
+int64_t mcl_als_init_workspace_bytes(const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank) {
+    if (!check_args(row_ptr, I, K, rank).empty()) return -1;
+    return als_plan(row_ptr, I, K, rank).total;
+}
+
+int mcl_als_init_typed(const void *X, int32_t x_type, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank, int32_t method,
+                       int32_t n_iter_max, double tol, float *A, float *B, float *C, double *errors, int32_t *info, void *workspace,
+                       int64_t workspace_bytes, void *hip_stream) {
+    const std::string bad = check_args(row_ptr, I, K, rank);
+    if (!bad.empty()) {
+        g_als_error = "mcl_als_init: " + bad;
+        return 1;
+    }
+    if (!X || !A || !B || !C || !info || !workspace) {
+        g_als_error = "mcl_als_init: NULL argument";
+        return 1;
+    }
+    if (x_type != MCL_X_F32 && x_type != MCL_X_BF16 && x_type != MCL_X_F16) {
+        g_als_error = "mcl_als_init: unknown x_type " + std::to_string(x_type) + " (MCL_X_F32 = 0, MCL_X_BF16 = 1, MCL_X_F16 = 2)";
+        return 1;
+    }
+    if (method != MCL_ALS_CP && method != MCL_ALS_CP_HALS) {
+        g_als_error = "mcl_als_init: unknown method " + std::to_string(method) + " (MCL_ALS_CP = 0, MCL_ALS_CP_HALS = 1)";
+        return 1;
+    }
+    if (n_iter_max < 0 || !(tol >= 0.0)) {
+        g_als_error = "mcl_als_init: need n_iter_max >= 0 and tol >= 0";
+        return 1;
+    }
+    return mcl_x_dispatch(x_type, [&](auto xl) {
+        using XL = decltype(xl);
+        return als_init<XL>(static_cast<const typename XL::T *>(X), x_type, row_ptr, I, K, rank, method, n_iter_max, tol, A, B, C, errors,
+                            info, workspace, workspace_bytes, hip_stream);
+    });
+}
+
+}  // extern "C"

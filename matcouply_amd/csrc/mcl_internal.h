@@ -395,3 +395,14 @@ int mcl_try_rows_chain_last(mcl_context *c, const ModeView &mv, bool vec, bool r
 int mcl_launch_pf2_cond_track(mcl_context *c);                         // cond.hip: monitor slot 3 <- worst polar-factor conditioning of the last PARAFAC2 inner iteration
 int64_t mcl_cond_part_doubles(const mcl_context *c);                    // cond.hip
 int mcl_launch_cond_probe(mcl_context *c, int want, double *out, bool accumulate = false);  // cond.hip: kappa of the penalty-free modes' systems -> out[3]
+
+// ---- svdinit.hip: pieces of init="svd" that the CP initialiser (alsinit.hip) shares ------------------------------------------
+// C of mcl_svd_init_typed (bit for bit) without the per-matrix vectors; the workspace is mcl_svd_init's
+int64_t mcl_svd_stack_workspace_bytes(const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank);
+int mcl_svd_stack_right(const void *X, int32_t x_type, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank, int32_t threshold,
+                        float *C, void *workspace, int64_t workspace_bytes, int32_t *info, hipStream_t stream, std::string &err);
+// V [n, rank] = the leading eigenvectors of the symmetric fp64 n x n matrix G (device), the entry of largest magnitude of
+// every column positive (threshold: clipped at 0); the subspace iteration of mcl_svd_init.  info[info0] as there.
+int64_t mcl_gram_vectors_workspace_bytes(int64_t n, int32_t rank);
+int mcl_gram_vectors(const double *G, int64_t n, int32_t rank, int32_t threshold, float *V, void *workspace, int32_t *info,
+                     int32_t info0, hipStream_t stream, std::string &err);

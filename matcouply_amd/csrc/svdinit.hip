@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "mcl_internal.h"
+#include "symeig_lds.h"
 #include "xload.h"
 
 namespace {
@@ -89,72 +90,6 @@ __device__ __forceinline__ double hash_unit(unsigned a, unsigned b) {  // determ
     unsigned h = a * 0x9E3779B1u ^ (b + 0x7F4A7C15u) * 0x85EBCA77u;
     h ^= h >> 15, h *= 0x2C1B3C6Du, h ^= h >> 12, h *= 0x297A2D39u, h ^= h >> 15;
     return (double)(h >> 8) * (2.0 / 16777216.0) - 1.0;
-}
-
-// eigen-decomposition of the symmetric m x m matrix S (LDS) by cyclic Jacobi with round-robin pairs: W <- eigenvectors
-// (columns), the diagonal of S <- eigenvalues.  me = m rounded up to even (a dummy player idles).  All 256 threads call it.
-__device__ void jacobi_lds(double *S, double *W, double *cs, int m) {
-    const int tid = threadIdx.x;
-    const int me = (m + 1) & ~1, half = me / 2;
-    for (int e = tid; e < m * m; e += 256) W[e] = ((e / m) == (e % m)) ? 1.0 : 0.0;
-    __shared__ double off_sh, diag_sh;
-    __syncthreads();
-    for (int sweep = 0; sweep < 40; ++sweep) {
-        if (tid == 0) {
-            double off = 0.0, dg = 0.0;
-            for (int a = 0; a < m; ++a)
-                for (int b = 0; b < m; ++b) (a == b ? dg : off) += S[a * m + b] * S[a * m + b];
-            off_sh = off, diag_sh = dg;
-        }
-        __syncthreads();
-        if (!(off_sh > 1e-30 * diag_sh)) break;
-        for (int step = 0; step < me - 1; ++step) {
-            // pair k of this step: (p, q)
-            auto pair_of = [&](int k, int &p, int &q) {
-                if (k == 0) p = me - 1, q = step;
-                else p = (step + k) % (me - 1), q = (step - k + (me - 1)) % (me - 1);
-                if (p > q) { const int t = p; p = q; q = t; }
-            };
-            if (tid < half) {
-                int p, q;
-                pair_of(tid, p, q);
-                double c = 1.0, s = 0.0;
-                if (q < m) {
-                    const double apq = S[p * m + q], app = S[p * m + p], aqq = S[q * m + q];
-                    if (fabs(apq) > 1e-300 && fabs(apq) > 1e-18 * sqrt(fabs(app * aqq))) {
-                        const double tau = (aqq - app) / (2.0 * apq);
-                        const double t = (tau >= 0.0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
-                        c = 1.0 / sqrt(1.0 + t * t), s = t * c;
-                    }
-                }
-                cs[2 * tid] = c, cs[2 * tid + 1] = s;
-            }
-            __syncthreads();
-            for (int e = tid; e < half * m; e += 256) {  // columns p, q of S and of W, every row i
-                const int k = e / m, i = e - k * m;
-                int p, q;
-                pair_of(k, p, q);
-                if (q >= m) continue;
-                const double c = cs[2 * k], s = cs[2 * k + 1];
-                const double sp = S[i * m + p], sq = S[i * m + q];
-                S[i * m + p] = c * sp - s * sq, S[i * m + q] = s * sp + c * sq;
-                const double wp = W[i * m + p], wq = W[i * m + q];
-                W[i * m + p] = c * wp - s * wq, W[i * m + q] = s * wp + c * wq;
-            }
-            __syncthreads();
-            for (int e = tid; e < half * m; e += 256) {  // rows p, q of S, every column j
-                const int k = e / m, j = e - k * m;
-                int p, q;
-                pair_of(k, p, q);
-                if (q >= m) continue;
-                const double c = cs[2 * k], s = cs[2 * k + 1];
-                const double sp = S[p * m + j], sq = S[q * m + j];
-                S[p * m + j] = c * sp - s * sq, S[q * m + j] = s * sp + c * sq;
-            }
-            __syncthreads();
-        }
-    }
-    __syncthreads();
 }
 
 // Subspace iteration of one matrix per workgroup (see the file header).  G: [K, K]; Q, Y: [K, m] scratch; out: Q holds the
@@ -395,17 +330,19 @@ int64_t mcl_svd_init_workspace_bytes(const int64_t *row_ptr, int64_t I, int64_t 
 
 }  // extern "C"
 
+// slabs = false: C only (the stack's Gram matrix and its vectors; B is not touched and may be NULL, and a matrix may have fewer
+// rows than the rank) - the start of the CP initialiser (alsinit.hip), bit for bit the C of the full call
 template <class XL>
 static int svd_init(const typename XL::T *X, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank, int32_t threshold, float *B,
-                    float *C, void *workspace, int64_t workspace_bytes, int32_t *info, void *hip_stream) {
+                    float *C, void *workspace, int64_t workspace_bytes, int32_t *info, void *hip_stream, bool slabs = true) {
     auto fail = [](const std::string &msg) {
         g_svd_error = msg;
         return 1;
     };
-    if (!X || !row_ptr || !B || !C || !workspace || !info) return fail("mcl_svd_init: NULL argument");
+    if (!X || !row_ptr || (slabs && !B) || !C || !workspace || !info) return fail("mcl_svd_init: NULL argument");
     if (I < 1 || K < 1 || rank < 1 || rank > MCL_MAX_RANK) return fail("mcl_svd_init: need I >= 1, K >= 1, 1 <= rank <= 64");
     if (rank > K) return fail("mcl_svd_init: rank exceeds the number of columns");
-    for (int64_t i = 0; i < I; ++i)
+    for (int64_t i = 0; i < I && slabs; ++i)
         if (row_ptr[i + 1] - row_ptr[i] < rank) return fail("mcl_svd_init: a matrix has fewer rows than the rank");
     if (row_ptr[I] >= (int64_t(1) << 31)) return fail("mcl_svd_init: more than 2^31 packed rows are not supported");
     const SvdPlan p0 = svd_plan(I, K, rank, 1);
@@ -437,6 +374,7 @@ static int svd_init(const typename XL::T *X, const int64_t *row_ptr, int64_t I, 
         hipLaunchKernelGGL((MCL_XKERNEL0(k_svd_gram)), dim3((unsigned)tiles, (unsigned)tiles, (unsigned)nb), dim3(256), 0, s, X, (const int *)ext, (int)b0,
                            (int)K, G);
         hipLaunchKernelGGL(k_svd_add, dim3((unsigned)((KK + 255) / 256)), dim3(256), 0, s, (const double *)G, nb, KK, Gstack, b0 == 0 ? 1 : 0);
+        if (!slabs) continue;
         hipLaunchKernelGGL(k_svd_subspace, dim3((unsigned)nb), dim3(256), sm, s, (const double *)G, (int)K, m, (int)rank, Q, Y, theta, info,
                            (int)b0);
         hipLaunchKernelGGL((MCL_XKERNEL0(k_svd_left)), dim3((unsigned)nb), dim3(256), 0, s, X, (const int *)ext, (int)b0, (int)K, m, (int)rank,
@@ -470,3 +408,48 @@ int mcl_svd_init_typed(const void *X, int32_t x_type, const int64_t *row_ptr, in
 }
 
 }  // extern "C"
+
+// ---- shared with the CP initialiser (alsinit.hip), declared in mcl_internal.h ------------------------------------------------
+int64_t mcl_svd_stack_workspace_bytes(const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank) {
+    return mcl_svd_init_workspace_bytes(row_ptr, I, K, rank);
+}
+
+int mcl_svd_stack_right(const void *X, int32_t x_type, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank, int32_t threshold,
+                        float *C, void *workspace, int64_t workspace_bytes, int32_t *info, hipStream_t stream, std::string &err) {
+    const int rc = mcl_x_dispatch(x_type, [&](auto xl) {
+        using XL = decltype(xl);
+        return svd_init<XL>(static_cast<const typename XL::T *>(X), row_ptr, I, K, rank, threshold, nullptr, C, workspace,
+                            workspace_bytes, info, stream, false);
+    });
+    if (rc) err = g_svd_error;
+    return rc;
+}
+
+int64_t mcl_gram_vectors_workspace_bytes(int64_t n, int32_t rank) {
+    const int64_t m = svd_m(n, rank);
+    return 2 * ((n * m * 8 + 255) & ~int64_t(255)) + ((m * 8 + 255) & ~int64_t(255));
+}
+
+int mcl_gram_vectors(const double *G, int64_t n, int32_t rank, int32_t threshold, float *V, void *workspace, int32_t *info,
+                     int32_t info0, hipStream_t s, std::string &err) {
+    if (n < 1 || n > (int64_t(1) << 15) || rank < 1 || rank > MCL_MAX_RANK || rank > n) {
+        err = "mcl_gram_vectors: need 1 <= rank <= min(n, 64)";
+        return 1;
+    }
+    const int m = svd_m(n, rank);
+    char *ws = static_cast<char *>(workspace);
+    const int64_t qb = (n * m * 8 + 255) & ~int64_t(255);
+    double *Q = reinterpret_cast<double *>(ws), *Y = reinterpret_cast<double *>(ws + qb), *theta = reinterpret_cast<double *>(ws + 2 * qb);
+    const size_t sm = sizeof(double) * (size_t)(2 * m * m + m + 2 * ((m + 1) / 2 + 1) + m) + sizeof(int) * (size_t)m + 64;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_svd_subspace), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_svd_subspace, dim3(1), dim3(256), sm, s, G, (int)n, m, (int)rank, Q, Y, theta, info, (int)info0);
+        hipLaunchKernelGGL(k_svd_right, dim3(1), dim3(256), 0, s, (const double *)Q, (int)n, m, (int)rank, (int)threshold, V);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) {
+        err = std::string("mcl_gram_vectors: ") + hipGetErrorString(e);
+        return 1;
+    }
+    return 0;
+}

@@ -138,6 +138,44 @@ def _device_svd_applies(matrices, rank):
     return rank <= K <= _DEVICE_SVD_MAX_K and min(rows) >= rank
 
 
+# init= names of the CP initialisers (reference decomposition.py:64-73): the aliases name the same method
+_CP_INITS = {"parafac_als": _engine.ALS_CP, "cp_als": _engine.ALS_CP, "parafac_hals": _engine.ALS_CP_HALS,
+             "cp_hals": _engine.ALS_CP_HALS}
+
+
+def _cp_init_options(matrices, rank, init, init_params):
+    """(method, n_iter_max, tol) of a CP initialiser, or NotImplementedError for what the device form does not serve: init_params
+    other than n_iter_max (default 50, as the reference sets it) and tol (TensorLy's defaults: 1e-8 for ALS, 1e-7 for HALS),
+    and shapes where TensorLy would fill the start with random columns (rank > min(max J_i, K)) or whose Gram matrices exceed
+    the start's bound (K or max J_i above _DEVICE_SVD_MAX_K, rank above 64)."""
+    method = _CP_INITS[init]
+    params = dict(init_params or {})
+    n_iter_max = params.pop("n_iter_max", 50)
+    tol = params.pop("tol", 1e-8 if method == _engine.ALS_CP else 1e-7)
+    if params:
+        raise NotImplementedError(
+            f'init="{init}": init_params {sorted(params)} not supported (only "n_iter_max" and "tol"; TensorLy options such '
+            "as normalize_factors, svd or linesearch are not served)")
+    if int(n_iter_max) != n_iter_max or n_iter_max < 0:
+        raise ValueError(f"init_params['n_iter_max'] must be a non-negative integer, not {n_iter_max!r}")
+    tol = 0.0 if tol is None else float(tol)
+    if not tol >= 0:
+        raise ValueError(f"init_params['tol'] must be non-negative, not {tol!r}")
+    K = int(shape(matrices[0])[1])
+    rows = [int(shape(m)[0]) for m in matrices] if not isinstance(matrices, PackedMatrices) else \
+        [int(matrices.row_ptr[i + 1] - matrices.row_ptr[i]) for i in range(len(matrices))]
+    J_max = max(rows)
+    if rank > min(J_max, K):
+        raise NotImplementedError(
+            f'init="{init}": rank {rank} exceeds min(max J_i, K) = {min(J_max, K)} (TensorLy would pad the start with random '
+            "columns); pass an explicit (weights, (A, B_is, C)) tuple instead.")
+    if K > _DEVICE_SVD_MAX_K or J_max > _DEVICE_SVD_MAX_K or rank > 64:
+        raise NotImplementedError(
+            f'init="{init}": the device start needs K <= {_DEVICE_SVD_MAX_K}, max J_i <= {_DEVICE_SVD_MAX_K} and rank <= 64 '
+            f"(K = {K}, max J_i = {J_max}, rank = {rank})")
+    return method, int(n_iter_max), tol
+
+
 def initialize_cmf(matrices, rank, init, svd_fun, random_state=None, init_params=None):
     random_state = check_random_state(random_state)
     if isinstance(init, (tuple, list, CoupledMatrixFactorization)):
@@ -191,7 +229,15 @@ def initialize_cmf(matrices, rank, init, svd_fun, random_state=None, init_params
             B_is = [np.clip(B_i, 0, float("inf")) for B_i in B_is]
             C = np.clip(C, 0, float("inf"))
         return CoupledMatrixFactorization((None, [A, B_is, np.ascontiguousarray(C)]))
-    if init in ("parafac2_als", "cp_als", "parafac_als", "cp_hals", "parafac_hals"):
+    if init in _CP_INITS:
+        # CP-ALS / CP-HALS on the zero-padded tensor (reference: TensorLy's parafac / non_negative_parafac_hals,
+        # decomposition.py:64-73), on the device (mcl_als_init): every limit and option is checked before the device is touched
+        method, n_iter_max, tol = _cp_init_options(matrices, rank, init, init_params)
+        X, row_ptr = _pack(matrices, _device())
+        A, B, C, _ = _engine.als_init(X, row_ptr, rank, method, n_iter_max, tol)
+        out = _Out(matrices)
+        return CoupledMatrixFactorization((None, [out(A), out.split(B, row_ptr), out(C)]))
+    if init == "parafac2_als":
         raise NotImplementedError(
             f'init="{init}" delegates to TensorLy decompositions in the reference (decomposition.py:55-73) and is '
             "out of scope of this engine; pass an explicit (weights, (A, B_is, C)) tuple instead.")
@@ -693,8 +739,12 @@ def cmf_aoadmm(
 
     ``matrices`` is a list of I arrays (NumPy or torch, J_i x K) or a :class:`PackedMatrices` already in HBM.  The
     arithmetic runs in fp32 on the device (rank x rank systems and all reductions in fp64); results are returned in the
-    array type and dtype of the input.  Not supported (out of scope, raise ``NotImplementedError``): TensorLy-ALS
-    initialisations.  ``inner_tol`` > 0 is evaluated by the engine on the device (single-device runs; sharded runs: on a host-driven step path).  Penalties without a native kernel (user
+    array type and dtype of the input.  ``init`` is ``"random"``, ``"svd"``, ``"threshold_svd"``, an explicit
+    ``(weights, (A, B_is, C))`` tuple, or a CP start on the zero-padded tensor computed on the device: ``"parafac_als"`` /
+    ``"cp_als"`` (CP-ALS) and ``"parafac_hals"`` / ``"cp_hals"`` (non-negative CP-HALS), deterministic (``random_state``
+    draws nothing for them), with ``init_params`` keys ``n_iter_max`` (default 50) and ``tol`` (default 1e-8 / 1e-7; 0 runs
+    every sweep).  Not supported (out of scope, raise ``NotImplementedError``): ``"parafac2_als"``, other ``init_params``
+    keys, a CP start with rank above min(max J_i, K), K or max J_i above 2048, and CP starts under ``group=``.  ``inner_tol`` > 0 is evaluated by the engine on the device (single-device runs; sharded runs: on a host-driven step path).  Penalties without a native kernel (user
     subclasses of ``matcouply_amd.penalties.ADMMPenalty``) are evaluated through their own Python methods on device
     tensors between the native solve and dual-update steps.
 
@@ -726,6 +776,9 @@ def cmf_aoadmm(
         raise ValueError(f'arithmetic must be "auto", "exact" or "fast", not {arithmetic!r}')
     random_state = check_random_state(random_state)
     svd_fun = get_svd(svd)
+    if group is not None and isinstance(init, str) and init in _CP_INITS:
+        raise NotImplementedError(f'init="{init}" needs all matrices (its start is a decomposition of the whole padded '
+                                  "tensor): not supported with group=; pass an explicit (weights, (A, B_is, C)) tuple instead.")
     cmf = initialize_cmf(matrices, rank, init, svd_fun=svd_fun, random_state=random_state, init_params=init_params)
 
     l2_penalty = _listify(l2_penalty, "l2_penalty")
