@@ -297,6 +297,45 @@ int mcl_als_init_typed(const void *X, int32_t x_type, const int64_t *row_ptr, in
                        int64_t workspace_bytes, void *hip_stream);
 const char *mcl_als_init_last_error(void);
 
+/* ---- many random starts of one problem at once (cmf_aoadmm_multistart, csrc/multistart.hip) ------------------------------- */
+/* One workgroup per start runs the whole fit (phases B, C, A, diagnostics and the stopping rule of mcl_run) in fp64 with
+ * workgroup barriers only; X is shared and read-only.  Stateless; X, state, diag, n_iter, stop, workspace: device pointers;
+ * row_ptr: HOST int64[I+1].
+ * state: fp64 [n_starts, state_len], in/out.  One start's slice: A [I, r], B packed [N, r], C [K, r], then for every mode
+ * m = 0, 1, 2 and every penalty k of it: aux (rows of the mode x r; PARAFAC2: P packed [N, r] followed by Delta [r, r]) and
+ * dual (rows x r).  state_len is the sum of these sizes (no padding).
+ * diag: fp64 [n_starts, n_iter_max + 1, MCL_MS_DIAG]: row 0 the initial state, row t + 1 outer iteration t:
+ * {rec_error, loss, flags (bit 0 feasible, bit 1 loss evaluated), regularisation, gap[m * MCL_MAX_REGS + k] ...}.
+ * n_iter int32[n_starts]: outer iterations run; stop int32[n_starts]: 0 or the MCL_STOP_* code that ended the start.
+ * Needs rank <= 16, penalties NN / Box / L1 / L2 ball on any mode (L2 ball on mode 0 with constant_A) and PARAFAC2 on mode 1
+ * with every J_i >= rank.  Every reduction has a fixed order; a start's result does not depend on n_starts or its neighbours. */
+#define MCL_MS_DIAG (4 + 3 * MCL_MAX_REGS)
+typedef struct mcl_multistart_penalty {
+    int32_t kind;           /* enum mcl_penalty_kind */
+    int32_t non_negativity;
+    double p0, p1;          /* Box: min, max; L1: reg_strength; L2 ball: norm_bound */
+} mcl_multistart_penalty;
+typedef struct mcl_multistart_options {
+    int32_t n_regs[3];
+    int32_t inner_n_iter_max;
+    mcl_multistart_penalty regs[3][MCL_MAX_REGS];
+    double l2_penalty[3];
+    double feasibility_penalty_scale;
+    double inner_tol;       /* <= 0: every inner iteration runs */
+    double tol, absolute_tol, feasibility_tol;  /* 0 = not set */
+    int32_t constant_A, constant_B;
+    int32_t update_A, update_B, update_C;
+    int32_t evaluate_loss_always;  /* return_errors: the loss of infeasible iterates is recorded too */
+    int32_t n_iter_max;
+    int32_t reserved;
+} mcl_multistart_options;
+int64_t mcl_multistart_workspace_bytes(const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank, const mcl_multistart_options *opt,
+                                       int32_t n_starts);
+int mcl_multistart_run(const void *X, int32_t x_type, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank,
+                       const mcl_multistart_options *opt, int32_t n_starts, double *state, double *diag, int32_t *n_iter, int32_t *stop,
+                       void *workspace, int64_t workspace_bytes, void *hip_stream);
+const char *mcl_multistart_last_error(void);
+
 /* ---- introspection for tests / profiling ------------------------------------------------------------- */
 /* device pointers to internal by-products / planner tables (the int32 tables: read the bits) */
 enum mcl_buffer_id {

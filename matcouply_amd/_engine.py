@@ -60,6 +60,7 @@ EXPORTED_SYMBOLS = [
     "mcl_svd_init_workspace_bytes", "mcl_svd_init", "mcl_svd_init_last_error", "mcl_read_bandwidth",
     "mcl_set_problem_typed", "mcl_svd_init_typed",
     "mcl_als_init_workspace_bytes", "mcl_als_init_typed", "mcl_als_init_last_error",
+    "mcl_multistart_workspace_bytes", "mcl_multistart_run", "mcl_multistart_last_error",
 ]
 
 
@@ -81,6 +82,25 @@ class StopRule(ctypes.Structure):
                 ("initial_loss", ctypes.c_double), ("penalty_weight", (ctypes.c_double * MCL_MAX_REGS) * 3),
                 ("evaluate_loss_always", ctypes.c_int32), ("max_run_ahead", ctypes.c_int32)]
 
+
+class MultistartPenalty(ctypes.Structure):
+    """mcl_multistart_penalty of include/matcouply_hip.h"""
+    _fields_ = [("kind", ctypes.c_int32), ("non_negativity", ctypes.c_int32), ("p0", ctypes.c_double), ("p1", ctypes.c_double)]
+
+
+class MultistartOptions(ctypes.Structure):
+    """mcl_multistart_options of include/matcouply_hip.h (a tolerance of 0 = not set)"""
+    _fields_ = [("n_regs", ctypes.c_int32 * 3), ("inner_n_iter_max", ctypes.c_int32),
+                ("regs", (MultistartPenalty * MCL_MAX_REGS) * 3), ("l2_penalty", ctypes.c_double * 3),
+                ("feasibility_penalty_scale", ctypes.c_double), ("inner_tol", ctypes.c_double), ("tol", ctypes.c_double),
+                ("absolute_tol", ctypes.c_double), ("feasibility_tol", ctypes.c_double), ("constant_A", ctypes.c_int32),
+                ("constant_B", ctypes.c_int32), ("update_A", ctypes.c_int32), ("update_B", ctypes.c_int32),
+                ("update_C", ctypes.c_int32), ("evaluate_loss_always", ctypes.c_int32), ("n_iter_max", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+MS_DIAG = 4 + 3 * MCL_MAX_REGS  # MCL_MS_DIAG: {rec_error, loss, flags, regularisation, gaps[3][MCL_MAX_REGS]}
+MS_MAX_RANK = 16
 
 STOP_RELATIVE, STOP_ABSOLUTE = 1, 2
 VERDICT_FEASIBLE, VERDICT_LOSS_EVALUATED = 1, 2  # flag bits of a verdict row; the stop code sits above them (>> 2)
@@ -164,6 +184,10 @@ def load_library():
         "mcl_als_init_typed": (ctypes.c_int, [P, I32, ctypes.POINTER(I64), I64, I64, I32, I32, I32, ctypes.c_double, P, P, P, P, P, P,
                                               I64, P]),
         "mcl_als_init_last_error": (ctypes.c_char_p, []),
+        "mcl_multistart_workspace_bytes": (I64, [ctypes.POINTER(I64), I64, I64, I32, ctypes.POINTER(MultistartOptions), I32]),
+        "mcl_multistart_run": (ctypes.c_int, [P, I32, ctypes.POINTER(I64), I64, I64, I32, ctypes.POINTER(MultistartOptions), I32, P, P,
+                                              P, P, P, I64, P]),
+        "mcl_multistart_last_error": (ctypes.c_char_p, []),
         "mcl_read_bandwidth": (ctypes.c_int, [P, I64, I32, P, P, ctypes.POINTER(ctypes.c_double)]),
     }
     for name, (res, args) in sig.items():
@@ -288,6 +312,53 @@ def als_init(X, row_ptr, rank, method, n_iter_max, tol):
     if rc != 0:
         raise EngineError(lib.mcl_als_init_last_error().decode())
     return A, B, C, errors[: int(info.item())]
+
+
+def multistart_state_len(I, N, K, rank, kinds):
+    """doubles of one start's state slice (mcl_multistart_run): A, B, C, then aux (+ Delta for PARAFAC2) and dual of every
+    penalty; `kinds` lists the PEN_* kinds per mode"""
+    rows = (I, N, K)
+    n = (I + N + K) * rank
+    for m in range(3):
+        for kind in kinds[m]:
+            n += 2 * rows[m] * rank + (rank * rank if kind == PEN_PARAFAC2 else 0)
+    return n
+
+
+def multistart_run(X, row_ptr, rank, options, state):
+    """Fit state.shape[0] starts of one problem at once (mcl_multistart_run), one workgroup per start.  X packed [sum J_i, K]
+    float32 / bfloat16 / float16 CUDA tensor; options a MultistartOptions; state float64 [n_starts, state_len] CUDA tensor (the
+    layout of matcouply_hip.h), updated in place -> (diag float64 [n_starts, n_iter_max + 1, MS_DIAG], n_iter int32 [n_starts],
+    stop int32 [n_starts]) on the device."""
+    import torch
+
+    lib = load_library()
+    xt = x_type_of(X.dtype)
+    if not (X.is_cuda and X.is_contiguous()):
+        raise EngineError("X must be a contiguous CUDA tensor")
+    if not (state.is_cuda and state.dtype == torch.float64 and state.is_contiguous() and state.dim() == 2):
+        raise EngineError("state must be a contiguous float64 CUDA tensor [n_starts, state_len]")
+    row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int64)
+    I, K = len(row_ptr) - 1, int(X.shape[1])
+    S = int(state.shape[0])
+    rp = row_ptr.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+    nbytes = lib.mcl_multistart_workspace_bytes(rp, I, K, int(rank), ctypes.byref(options), S)
+    if nbytes < 0:
+        lib.mcl_multistart_run(None, xt, rp, I, K, int(rank), ctypes.byref(options), S, None, None, None, None, None, 0, None)
+        raise EngineError(lib.mcl_multistart_last_error().decode())
+    ws = torch.empty(int(nbytes) + 256, dtype=torch.uint8, device=X.device)
+    off = (-ws.data_ptr()) % 256
+    diag = torch.zeros((S, int(options.n_iter_max) + 1, MS_DIAG), dtype=torch.float64, device=X.device)
+    n_iter = torch.zeros(S, dtype=torch.int32, device=X.device)
+    stop = torch.zeros(S, dtype=torch.int32, device=X.device)
+    with torch.cuda.device(X.device):
+        stream = torch.cuda.current_stream(X.device).cuda_stream
+        rc = lib.mcl_multistart_run(X.data_ptr(), xt, rp, I, K, int(rank), ctypes.byref(options), S, state.data_ptr(),
+                                    diag.data_ptr(), n_iter.data_ptr(), stop.data_ptr(), ws.data_ptr() + off, nbytes,
+                                    ctypes.c_void_p(stream))
+    if rc != 0:
+        raise EngineError(lib.mcl_multistart_last_error().decode())
+    return diag, n_iter, stop
 
 
 class NativeReg:

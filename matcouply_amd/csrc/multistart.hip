@@ -1,0 +1,893 @@
+// cmf_aoadmm_multistart (decomposition.py): many random starts of ONE problem fitted at once, one workgroup per start.
+//
+// A start of the examples' size (150 .. 500 rows, K = 15 .. 20, rank 3 .. 4) leaves almost the whole device idle and spends its
+// time on launches and host set-up.  Its phases need cross-workgroup synchronisation only because one problem is spread over
+// many workgroups; here a start lives in ONE workgroup (256 threads = 4 wave64s), so the whole fit - every outer iteration, its
+// B, C and A phases with their inner ADMM loops, the diagnostics and the stopping rule - runs inside one launch with nothing but
+// workgroup barriers.  Starts are independent: blockIdx.x is the start, and a finished workgroup frees its CU for the next.
+//
+// Order per outer iteration (reference decomposition.py): B phase :222-292, C phase :295-344, A phase :120-219, feasibility
+// gaps :351-417, reconstruction error from the A phase's by-products :445-449 (:430-444 when A is not updated), loss and the
+// stopping rule of the outer loop :945-1053 - the rule of mcl_run / k_diag_verdict: the relative criterion against the last
+// RECORDED loss, the absolute one on the newest, both only on feasible iterates and only when `tol` is set.
+//
+// Numerics: fp64 throughout; X is read in its stored type and converted exactly (xload.h: ld1), then widened.  The r x r systems
+// are inverted by Cholesky in LDS (one thread per system, a batch of systems at a time), the PARAFAC2 polar factor of
+// M_i = Y_i Delta^T is M_i (M_i^T M_i)^{-1/2} from a cyclic Jacobi eigen-decomposition of the r x r Gram in LDS (the rotation of
+// symeig_lds.h, one thread per slab: the I Grams are independent, and one workgroup-wide solve per slab would cost ~60
+// barriers each).  No atomics; every sum runs in a fixed order that depends only on the problem's shape, so a start's result
+// is bitwise independent of how many starts share the launch and of which.
+//
+// Memory: X, row_ptr and the row -> slab map are shared.  Each start owns a slice of `state` (factors, aux, duals: the caller's
+// layout, matcouply_hip.h) and a slice of the scratch workspace (right-hand sides, inverses, X C, ...), all fp64.  At the sizes
+// this serves, the slices stay in L2 / MALL.
+#include <algorithm>
+#include <cmath>
+#include <string>
+#include <vector>
+
+#include "mcl_internal.h"
+#include "xload.h"
+
+namespace {
+
+static std::string g_ms_error;
+constexpr int MS_THREADS = 256;
+constexpr int MS_MAX_RANK = 16;
+constexpr int MS_SYS_BYTES = 40960;  // LDS for a batch of r x r systems (two r x r matrices per thread)
+
+struct MsArgs {
+    const void *X;
+    const int64_t *row_ptr;
+    const int32_t *slab_of_row;
+    int64_t I, N, K;
+    int64_t state_len, scratch_len, diag_stride;
+    double *state, *scratch, *diag;
+    int32_t *n_iter, *stop;
+    int64_t off_aux[3][MCL_MAX_REGS], off_dual[3][MCL_MAX_REGS], off_delta[3][MCL_MAX_REGS];
+    mcl_multistart_options o;
+};
+
+// scratch of one start, in doubles
+struct MsScratch {
+    int64_t rhsB, XC, RC, LinvB, rhoB, LinvA, rhoA, Q, rhsA, PF, colsq, small, total;
+};
+
+static __host__ __device__ inline MsScratch ms_scratch(int64_t I, int64_t N, int64_t K, int r) {
+    MsScratch s{};
+    int64_t o = 0;
+    auto take = [&](int64_t n) { const int64_t at = o; o += (n + 31) & ~int64_t(31); return at; };
+    s.rhsB = take(N * r);
+    s.XC = take(N * r);
+    s.RC = take(K * r);
+    s.LinvB = take(I * r * r);
+    s.rhoB = take(I);
+    s.LinvA = take(I * r * r);
+    s.rhoA = take(I);
+    s.Q = take(I * r * r);
+    s.rhsA = take(I * r);
+    s.PF = take(I * r * r);
+    s.colsq = take(I * r);
+    s.small = take(8 * r * r + 64);
+    s.total = o;
+    return s;
+}
+
+// ---- workgroup helpers (every thread calls them) --------------------------------------------------------------------------
+// sum of one value per thread, tree order fixed; the total in every thread
+static __device__ __forceinline__ double wg_sum(double v, double *red) {
+    const int t = threadIdx.x;
+    red[t] = v;
+    __syncthreads();
+    for (int h = MS_THREADS / 2; h > 0; h >>= 1) {
+        if (t < h) red[t] += red[t + h];
+        __syncthreads();
+    }
+    const double s = red[0];
+    __syncthreads();
+    return s;
+}
+
+// out[e] = sum_{j < n} f(j, e) for e < P: groups of threads take rows j = g, g + G, ..., the G partials are added in group order
+template <class F>
+static __device__ __forceinline__ void rows_reduce(int P, int64_t n, double *out, double *red, F f) {
+    const int t = threadIdx.x;
+    if (P > MS_THREADS / 2) {
+        for (int e = t; e < P; e += MS_THREADS) {
+            double acc = 0.0;
+            for (int64_t j = 0; j < n; ++j) acc += f(j, e);
+            out[e] = acc;
+        }
+        __syncthreads();
+        return;
+    }
+    const int G = MS_THREADS / P, e = t % P, g = t / P;
+    double acc = 0.0;
+    if (g < G)
+        for (int64_t j = g; j < n; j += G) acc += f(j, e);
+    red[t] = acc;
+    __syncthreads();
+    if (t < P) {
+        double s = 0.0;
+        for (int q = 0; q < G; ++q) s += red[q * P + t];
+        out[t] = s;
+    }
+    __syncthreads();
+}
+
+// S (R x R, row-major, SPD) <- S^-1 by Cholesky: S = L L^T, W = L^-1, S^-1 = W^T W.  One thread, LDS.
+template <int R>
+static __device__ __forceinline__ void spd_inverse(double *S, double *W) {
+    for (int j = 0; j < R; ++j) {  // L in the lower triangle of S
+        double d = S[j * R + j];
+        for (int k = 0; k < j; ++k) d -= S[j * R + k] * S[j * R + k];
+        const double l = sqrt(d);
+        S[j * R + j] = l;
+        for (int i = j + 1; i < R; ++i) {
+            double v = S[i * R + j];
+            for (int k = 0; k < j; ++k) v -= S[i * R + k] * S[j * R + k];
+            S[i * R + j] = v / l;
+        }
+    }
+    for (int j = 0; j < R; ++j) {  // W = L^-1, lower
+        W[j * R + j] = 1.0 / S[j * R + j];
+        for (int i = j + 1; i < R; ++i) {
+            double v = 0.0;
+            for (int k = j; k < i; ++k) v += S[i * R + k] * W[k * R + j];
+            W[i * R + j] = -v / S[i * R + i];
+        }
+    }
+    for (int a = 0; a < R; ++a)
+        for (int b = a; b < R; ++b) {
+            double v = 0.0;
+            for (int k = b; k < R; ++k) v += W[k * R + a] * W[k * R + b];
+            S[a * R + b] = v, S[b * R + a] = v;
+        }
+}
+
+// S (R x R symmetric PSD Gram) <- S^{-1/2} on its range: cyclic Jacobi (the rotation of symeig_lds.h), eigenvalues at or below
+// 1e-13 of the largest dropped.  One thread, LDS.
+template <int R>
+static __device__ __forceinline__ void gram_inv_sqrt(double *S, double *W) {
+    for (int e = 0; e < R * R; ++e) W[e] = (e / R == e % R) ? 1.0 : 0.0;
+    for (int sweep = 0; sweep < 40; ++sweep) {
+        double off = 0.0, dg = 0.0;
+        for (int a = 0; a < R; ++a)
+            for (int b = 0; b < R; ++b) (a == b ? dg : off) += S[a * R + b] * S[a * R + b];
+        if (!(off > 1e-30 * dg)) break;
+        for (int p = 0; p < R - 1; ++p)
+            for (int q = p + 1; q < R; ++q) {
+                const double apq = S[p * R + q], app = S[p * R + p], aqq = S[q * R + q];
+                if (!(fabs(apq) > 1e-300 && fabs(apq) > 1e-18 * sqrt(fabs(app * aqq)))) continue;
+                const double tau = (aqq - app) / (2.0 * apq);
+                const double tt = (tau >= 0.0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
+                const double c = 1.0 / sqrt(1.0 + tt * tt), s = tt * c;
+                for (int i = 0; i < R; ++i) {
+                    const double sp = S[i * R + p], sq = S[i * R + q];
+                    S[i * R + p] = c * sp - s * sq, S[i * R + q] = s * sp + c * sq;
+                    const double wp = W[i * R + p], wq = W[i * R + q];
+                    W[i * R + p] = c * wp - s * wq, W[i * R + q] = s * wp + c * wq;
+                }
+                for (int j = 0; j < R; ++j) {
+                    const double sp = S[p * R + j], sq = S[q * R + j];
+                    S[p * R + j] = c * sp - s * sq, S[q * R + j] = s * sp + c * sq;
+                }
+            }
+    }
+    double lam[R], lmax = 0.0;
+    #pragma unroll
+    for (int k = 0; k < R; ++k) lam[k] = S[k * R + k], lmax = fmax(lmax, lam[k]);
+    #pragma unroll
+    for (int k = 0; k < R; ++k) lam[k] = lam[k] > 1e-13 * lmax ? 1.0 / sqrt(lam[k]) : 0.0;
+    for (int a = 0; a < R; ++a)
+        for (int b = a; b < R; ++b) {
+            double v = 0.0;
+            #pragma unroll
+            for (int k = 0; k < R; ++k) v += W[a * R + k] * lam[k] * W[b * R + k];
+            S[a * R + b] = v, S[b * R + a] = v;
+        }
+}
+
+// the prox of a row-separable kind on one value (oracle prox_elementwise; rho: the row's feasibility penalty)
+static __device__ inline double prox_value(const mcl_multistart_penalty &p, double y, double rho) {
+    if (p.kind == MCL_PEN_NN) return fmax(y, 0.0);
+    if (p.kind == MCL_PEN_BOX) return fmin(fmax(y, p.p0), p.p1);
+    if (p.kind == MCL_PEN_L1) {
+        const double thr = p.p0 / rho;
+        if (p.non_negativity) return fmax(y - thr, 0.0);
+        const double m = fmax(fabs(y) - thr, 0.0);
+        return y > 0.0 ? m : (y < 0.0 ? -m : 0.0);
+    }
+    return y;
+}
+
+template <int R, class XL>
+struct Start {
+    const MsArgs &a;
+    const typename XL::T *X;
+    const int64_t *rp;
+    const int32_t *slab;
+    int64_t I, N, K;
+    double *A, *B, *C, *ws;
+    MsScratch sc;
+    double *red, *sys, *sh;  // LDS: reduction scratch, system batch, small shared values
+    int nb;                  // systems per batch
+
+    __device__ int64_t rows_of(int m) const { return m == 0 ? I : (m == 1 ? N : K); }
+    __device__ __forceinline__ double *F(int m) const { return m == 0 ? A : (m == 1 ? B : C); }
+    __device__ __forceinline__ double *aux(int m, int k) const { return A + a.off_aux[m][k]; }
+    __device__ __forceinline__ double *dual(int m, int k) const { return A + a.off_dual[m][k]; }
+    __device__ __forceinline__ double *delta(int m, int k) const { return A + a.off_delta[m][k]; }
+    __device__ __forceinline__ double x(int64_t j, int64_t c) const { return (double)XL::ld1(X + j * K + c); }
+
+    // aux of penalty k of mode m as a packed matrix, element (j, l): P Delta for PARAFAC2 (Delta copied to sh_delta first)
+    __device__ __forceinline__ double auxp(int m, int k, int64_t j, int l, const double *dl) const {
+        if (a.o.regs[m][k].kind == MCL_PEN_PARAFAC2) {
+            const double *P = aux(m, k) + j * R;
+            double v = 0.0;
+            for (int q = 0; q < R; ++q) v += P[q] * dl[q * R + l];
+            return v;
+        }
+        return aux(m, k)[j * R + l];
+    }
+
+    // invert n systems: build(i, S) writes system i into S (one thread), the inverse goes to out + i R R
+    template <class Build>
+    __device__ __forceinline__ void invert_systems(int64_t n, double *out, Build build) {
+        const int t = threadIdx.x;
+        for (int64_t base = 0; base < n; base += nb) {
+            const int64_t i = base + t;
+            if (t < nb && i < n) {
+                double *S = sys + t * 2 * R * R, *W = S + R * R;
+                build(i, S);
+                spd_inverse<R>(S, W);
+                for (int e = 0; e < R * R; ++e) out[i * R * R + e] = S[e];
+            }
+        }
+        __syncthreads();
+    }
+
+    // C^T C into cc (global scratch), rows_reduce order
+    __device__ __forceinline__ void ctc(double *cc) {
+        rows_reduce(R * R, K, cc, red, [&](int64_t c, int e) { return C[c * R + e / R] * C[c * R + e % R]; });
+    }
+
+    // ---- prox + dual update of penalty k of mode m; F is the new factor, rho_row(j) the row's penalty, rho_mat(seg) a matrix's
+    __device__ __forceinline__ void prox_mode(int m, int k, const double *rho_rows_slab, double rho_scalar) {
+        const mcl_multistart_penalty &p = a.o.regs[m][k];
+        const int t = threadIdx.x;
+        const int64_t rows = rows_of(m);
+        double *Fm = F(m), *Z = aux(m, k), *U = dual(m, k);
+        auto rho_of = [&](int64_t j) {
+            if (m == 1) return rho_rows_slab[slab[j]];
+            if (m == 0) return rho_rows_slab[j];
+            return rho_scalar;
+        };
+        if (p.kind == MCL_PEN_NN || p.kind == MCL_PEN_BOX || p.kind == MCL_PEN_L1) {
+            for (int64_t e = t; e < rows * R; e += MS_THREADS) {
+                const int64_t j = e / R;
+                const double f = Fm[e], u = U[e];
+                const double z = prox_value(p, f + u, rho_of(j));
+                Z[e] = z;
+                U[e] = f - (z - u);
+            }
+            __syncthreads();
+            return;
+        }
+        if (p.kind == MCL_PEN_L2BALL) {
+            for (int64_t e = t; e < rows * R; e += MS_THREADS) {
+                const double y = Fm[e] + U[e];
+                Z[e] = p.non_negativity ? fmax(y, 0.0) : y;
+            }
+            __syncthreads();
+            double *cs = ws + sc.colsq;
+            if (m == 1) {  // column norms per matrix B_i
+                for (int64_t e = t; e < I * R; e += MS_THREADS) {
+                    const int64_t i = e / R;
+                    const int l = (int)(e % R);
+                    double s = 0.0;
+                    for (int64_t j = rp[i]; j < rp[i + 1]; ++j) s += Z[j * R + l] * Z[j * R + l];
+                    cs[e] = s;
+                }
+                __syncthreads();
+            } else {
+                rows_reduce(R, rows, cs, red, [&](int64_t j, int l) { return Z[j * R + l] * Z[j * R + l]; });
+            }
+            for (int64_t e = t; e < rows * R; e += MS_THREADS) {
+                const int64_t j = e / R;
+                const int l = (int)(e % R);
+                const double nrm = sqrt(m == 1 ? cs[slab[j] * R + l] : cs[l]);
+                const double z = Z[e] * p.p0 / fmax(nrm, p.p0);
+                Z[e] = z;
+                U[e] = Fm[e] - (z - U[e]);
+            }
+            __syncthreads();
+            return;
+        }
+        // PARAFAC2 (mode 1): P_i = polar(Y_i Delta^T), Delta <- sum_i rho_i P_i^T Y_i / sum_i rho_i, Y = B + U
+        double *P = Z, *D = delta(m, k);
+        double *dl = sh;  // Delta (old) in LDS
+        for (int e = t; e < R * R; e += MS_THREADS) dl[e] = D[e];
+        __syncthreads();
+        double *PF = ws + sc.PF;
+        // Gram of M_i = Y_i Delta^T per slab
+        for (int64_t e = t; e < I * R * R; e += MS_THREADS) {
+            const int64_t i = e / (R * R);
+            const int ab = (int)(e % (R * R)), ra = ab / R, rb = ab % R;
+            double s = 0.0;
+            for (int64_t j = rp[i]; j < rp[i + 1]; ++j) {
+                double ma = 0.0, mb = 0.0;
+                #pragma unroll
+                for (int l = 0; l < R; ++l) {
+                    const double y = B[j * R + l] + U[j * R + l];
+                    ma += y * dl[ra * R + l];
+                    mb += y * dl[rb * R + l];
+                }
+                s += ma * mb;
+            }
+            PF[e] = s;
+        }
+        __syncthreads();
+        for (int64_t base = 0; base < I; base += nb) {
+            const int64_t i = base + t;
+            if (t < nb && i < I) {
+                double *S = sys + t * 2 * R * R, *W = S + R * R;
+                for (int e = 0; e < R * R; ++e) S[e] = PF[i * R * R + e];
+                gram_inv_sqrt<R>(S, W);
+                for (int e = 0; e < R * R; ++e) PF[i * R * R + e] = S[e];
+            }
+        }
+        __syncthreads();
+        for (int64_t j = t; j < N; j += MS_THREADS) {  // P_j = (Y_j Delta^T) G_i^{-1/2}
+            double mrow[R];
+            #pragma unroll
+            for (int q = 0; q < R; ++q) {
+                double v = 0.0;
+                for (int l = 0; l < R; ++l) v += (B[j * R + l] + U[j * R + l]) * dl[q * R + l];
+                mrow[q] = v;
+            }
+            const double *G = PF + (int64_t)slab[j] * R * R;
+            #pragma unroll 1
+            for (int l = 0; l < R; ++l) {
+                double v = 0.0;
+                #pragma unroll
+                for (int q = 0; q < R; ++q) v += mrow[q] * G[q * R + l];
+                P[j * R + l] = v;
+            }
+        }
+        __syncthreads();
+        for (int64_t e = t; e < I * R * R; e += MS_THREADS) {  // rho_i P_i^T Y_i per slab
+            const int64_t i = e / (R * R);
+            const int ab = (int)(e % (R * R)), ra = ab / R, rb = ab % R;
+            double s = 0.0;
+            for (int64_t j = rp[i]; j < rp[i + 1]; ++j) s += P[j * R + ra] * (B[j * R + rb] + U[j * R + rb]);
+            PF[e] = rho_rows_slab[i] * s;
+        }
+        __syncthreads();
+        if (t < R * R) {
+            double s = 0.0, rs = 0.0;
+            for (int64_t i = 0; i < I; ++i) s += PF[i * R * R + t], rs += rho_rows_slab[i];
+            D[t] = s / rs;
+            dl[t] = s / rs;
+        }
+        __syncthreads();
+        for (int64_t e = t; e < N * R; e += MS_THREADS) {
+            const int64_t j = e / R;
+            const int l = (int)(e % R);
+            double v = 0.0;
+            for (int q = 0; q < R; ++q) v += P[j * R + q] * dl[q * R + l];
+            U[e] = B[e] - (v - U[e]);
+        }
+        __syncthreads();
+    }
+
+    // ||F_m||^2, ||aux_k - F_m||^2 per penalty and sum |F_m| (L1 values), in fixed order
+    __device__ __forceinline__ void mode_stats(int m, double *nf, double *gap, double *abs_sum) {
+        const int t = threadIdx.x;
+        const int64_t n = rows_of(m) * R;
+        const double *Fm = F(m);
+        double v = 0.0, w = 0.0;
+        for (int64_t e = t; e < n; e += MS_THREADS) v += Fm[e] * Fm[e], w += fabs(Fm[e]);
+        *nf = wg_sum(v, red);
+        *abs_sum = wg_sum(w, red);
+#pragma unroll
+        for (int k = 0; k < MCL_MAX_REGS; ++k) {
+            if (k >= a.o.n_regs[m]) break;
+            double *dl = sh + R * R;
+            if (a.o.regs[m][k].kind == MCL_PEN_PARAFAC2) {
+                for (int e = t; e < R * R; e += MS_THREADS) dl[e] = delta(m, k)[e];
+                __syncthreads();
+            }
+            double g = 0.0;
+            for (int64_t e = t; e < n; e += MS_THREADS) {
+                const double d = auxp(m, k, e / R, (int)(e % R), dl) - Fm[e];
+                g += d * d;
+            }
+            gap[k] = wg_sum(g, red);
+        }
+    }
+
+    // inner_tol (decomposition.py:90-117): relative change <= tol and every gap of the mode < tol
+    __device__ __forceinline__ bool inner_converged(int m, double diff_partial) {
+        const double tol = a.o.inner_tol;
+        const double diff = wg_sum(diff_partial, red);
+        double nf, gp[MCL_MAX_REGS], as;
+        mode_stats(m, &nf, gp, &as);
+        if (sqrt(diff) > tol * sqrt(nf)) return false;
+        double worst = -INFINITY;
+#pragma unroll
+        for (int k = 0; k < MCL_MAX_REGS; ++k)
+            if (k < a.o.n_regs[m]) worst = fmax(worst, sqrt(gp[k]) / sqrt(nf));
+        return a.o.n_regs[m] == 0 || worst < tol;
+    }
+
+    // ---- B phase ----------------------------------------------------------------------------------------------------------
+    __device__ __forceinline__ void phase_B() {
+        const int t = threadIdx.x;
+        const int n = a.o.n_regs[1];
+        double *cc = ws + sc.small, *rhs = ws + sc.rhsB, *Linv = ws + sc.LinvB, *rho = ws + sc.rhoB;
+        ctc(cc);
+        for (int64_t j = t; j < N; j += MS_THREADS) {  // rhs_i = X_i (C * a_i)
+            const double *ai = A + (int64_t)slab[j] * R;
+            double acc[R];
+            #pragma unroll
+            for (int l = 0; l < R; ++l) acc[l] = 0.0;
+            for (int64_t c = 0; c < K; ++c) {
+                const double xv = x(j, c);
+                #pragma unroll
+                for (int l = 0; l < R; ++l) acc[l] += xv * (C[c * R + l] * ai[l]);
+            }
+            #pragma unroll
+            for (int l = 0; l < R; ++l) rhs[j * R + l] = acc[l];
+        }
+        for (int64_t i = t; i < I; i += MS_THREADS) {
+            double tr = 0.0;
+            for (int l = 0; l < R; ++l) tr += cc[l * R + l] * A[i * R + l] * A[i * R + l];
+            rho[i] = 0.5 * tr * a.o.feasibility_penalty_scale;
+        }
+        __syncthreads();
+        if (a.o.constant_B) {
+            if (t == 0) {
+                double mx = rho[0];
+                for (int64_t i = 1; i < I; ++i) mx = fmax(mx, rho[i]);
+                sh[2 * R * R] = mx;
+            }
+            __syncthreads();
+            const double mx = sh[2 * R * R];
+            for (int64_t i = t; i < I; i += MS_THREADS) rho[i] = mx;
+            __syncthreads();
+        }
+        invert_systems(I, Linv, [&](int64_t i, double *S) {
+            const double *ai = A + i * R;
+            const double shift = rho[i] * n + a.o.l2_penalty[1];
+            for (int p = 0; p < R; ++p)
+                for (int q = 0; q < R; ++q) S[p * R + q] = cc[p * R + q] * ai[p] * ai[q] + (p == q ? shift : 0.0);
+        });
+        for (int it = 0; it < a.o.inner_n_iter_max; ++it) {
+            // Delta of every PARAFAC2 penalty into LDS for the right-hand side
+            for (int k = 0; k < n; ++k)
+                if (a.o.regs[1][k].kind == MCL_PEN_PARAFAC2)
+                    for (int e = t; e < R * R; e += MS_THREADS) sh[3 * R * R + 8 + k * R * R + e] = delta(1, k)[e];
+            __syncthreads();
+            double diff = 0.0;
+            for (int64_t j = t; j < N; j += MS_THREADS) {
+                const int64_t i = slab[j];
+                double T[R];
+                #pragma unroll
+                for (int l = 0; l < R; ++l) {
+                    double s = 0.0;
+                    for (int k = 0; k < n; ++k) s += auxp(1, k, j, l, sh + 3 * R * R + 8 + k * R * R) - dual(1, k)[j * R + l];
+                    T[l] = n ? rho[i] * s + rhs[j * R + l] : rhs[j * R + l];
+                }
+                const double *L = Linv + i * R * R;
+                #pragma unroll 1
+                for (int l = 0; l < R; ++l) {
+                    double v = 0.0;
+                    #pragma unroll
+                    for (int q = 0; q < R; ++q) v += T[q] * L[q * R + l];
+                    const double d = v - B[j * R + l];
+                    diff += d * d;
+                    B[j * R + l] = v;
+                }
+            }
+            __syncthreads();
+            for (int k = 0; k < n; ++k) prox_mode(1, k, rho, 0.0);
+            if (a.o.inner_tol > 0.0 && inner_converged(1, diff)) break;
+        }
+    }
+
+    // ---- C phase ----------------------------------------------------------------------------------------------------------
+    __device__ __forceinline__ void phase_C() {
+        const int t = threadIdx.x;
+        const int n = a.o.n_regs[2];
+        double *G = ws + sc.small + R * R, *Linv = ws + sc.small + 2 * R * R, *RC = ws + sc.RC;
+        auto ba = [&](int64_t j, int l) { return B[j * R + l] * A[(int64_t)slab[j] * R + l]; };
+        rows_reduce(R * R, N, G, red, [&](int64_t j, int e) { return ba(j, e / R) * ba(j, e % R); });
+        rows_reduce((int)(K * R), N, RC, red, [&](int64_t j, int e) { return x(j, e / R) * ba(j, e % R); });
+        double tr = 0.0;
+        for (int l = 0; l < R; ++l) tr += G[l * R + l];
+        const double rho = 0.5 * tr * a.o.feasibility_penalty_scale;
+        if (t == 0) {
+            double *S = sys, *W = sys + R * R;
+            for (int e = 0; e < R * R; ++e) S[e] = G[e] + ((e / R == e % R) ? rho * n + a.o.l2_penalty[2] : 0.0);
+            spd_inverse<R>(S, W);
+            for (int e = 0; e < R * R; ++e) Linv[e] = S[e];
+        }
+        __syncthreads();
+        for (int it = 0; it < a.o.inner_n_iter_max; ++it) {
+            double diff = 0.0;
+            for (int64_t c = t; c < K; c += MS_THREADS) {
+                double T[R];
+                #pragma unroll
+                for (int l = 0; l < R; ++l) {
+                    double s = 0.0;
+                    for (int k = 0; k < n; ++k) s += aux(2, k)[c * R + l] - dual(2, k)[c * R + l];
+                    T[l] = n ? s * rho + RC[c * R + l] : RC[c * R + l];
+                }
+                #pragma unroll 1
+                for (int l = 0; l < R; ++l) {
+                    double v = 0.0;
+                    #pragma unroll
+                    for (int q = 0; q < R; ++q) v += T[q] * Linv[q * R + l];
+                    const double d = v - C[c * R + l];
+                    diff += d * d;
+                    C[c * R + l] = v;
+                }
+            }
+            __syncthreads();
+            for (int k = 0; k < n; ++k) prox_mode(2, k, nullptr, rho);
+            if (a.o.inner_tol > 0.0 && inner_converged(2, diff)) break;
+        }
+    }
+
+    // ---- A phase (leaves rhs_A and Q for the reconstruction error) ---------------------------------------------------------
+    __device__ __forceinline__ void phase_A() {
+        const int t = threadIdx.x;
+        const int n = a.o.n_regs[0];
+        double *cc = ws + sc.small, *XC = ws + sc.XC, *rhsA = ws + sc.rhsA, *Q = ws + sc.Q, *Linv = ws + sc.LinvA, *rho = ws + sc.rhoA;
+        ctc(cc);
+        x_times_C(XC);
+        for (int64_t e = t; e < I * R; e += MS_THREADS) {
+            const int64_t i = e / R;
+            const int l = (int)(e % R);
+            double s = 0.0;
+            for (int64_t j = rp[i]; j < rp[i + 1]; ++j) s += B[j * R + l] * XC[j * R + l];
+            rhsA[e] = s;
+        }
+        for (int64_t e = t; e < I * R * R; e += MS_THREADS) {
+            const int64_t i = e / (R * R);
+            const int ab = (int)(e % (R * R)), p = ab / R, q = ab % R;
+            double s = 0.0;
+            for (int64_t j = rp[i]; j < rp[i + 1]; ++j) s += B[j * R + p] * B[j * R + q];
+            Q[e] = s * cc[ab];
+        }
+        __syncthreads();
+        for (int64_t i = t; i < I; i += MS_THREADS) {
+            double tr = 0.0;
+            for (int l = 0; l < R; ++l) tr += Q[i * R * R + l * R + l];
+            rho[i] = 0.5 * tr * a.o.feasibility_penalty_scale;
+        }
+        __syncthreads();
+        if (a.o.constant_A) {
+            if (t == 0) {
+                double mx = rho[0];
+                for (int64_t i = 1; i < I; ++i) mx = fmax(mx, rho[i]);
+                sh[2 * R * R] = mx;
+            }
+            __syncthreads();
+            const double mx = sh[2 * R * R];
+            for (int64_t i = t; i < I; i += MS_THREADS) rho[i] = mx;
+            __syncthreads();
+        }
+        invert_systems(I, Linv, [&](int64_t i, double *S) {
+            const double shift = rho[i] * n + a.o.l2_penalty[0];
+            for (int e = 0; e < R * R; ++e) S[e] = Q[i * R * R + e] + ((e / R == e % R) ? shift : 0.0);
+        });
+        for (int it = 0; it < a.o.inner_n_iter_max; ++it) {
+            double diff = 0.0;
+            for (int64_t i = t; i < I; i += MS_THREADS) {
+                double T[R];
+                #pragma unroll
+                for (int l = 0; l < R; ++l) {
+                    double s = 0.0;
+                    for (int k = 0; k < n; ++k) s += aux(0, k)[i * R + l] - dual(0, k)[i * R + l];
+                    T[l] = n ? rho[i] * s + rhsA[i * R + l] : rhsA[i * R + l];
+                }
+                const double *L = Linv + i * R * R;
+                #pragma unroll 1
+                for (int l = 0; l < R; ++l) {
+                    double v = 0.0;
+                    #pragma unroll
+                    for (int q = 0; q < R; ++q) v += T[q] * L[q * R + l];
+                    const double d = v - A[i * R + l];
+                    diff += d * d;
+                    A[i * R + l] = v;
+                }
+            }
+            __syncthreads();
+            for (int k = 0; k < n; ++k) prox_mode(0, k, rho, 0.0);
+            if (a.o.inner_tol > 0.0 && inner_converged(0, diff)) break;
+        }
+    }
+
+    __device__ __forceinline__ void x_times_C(double *XC) {
+        for (int64_t j = threadIdx.x; j < N; j += MS_THREADS) {
+            double acc[R];
+            #pragma unroll
+            for (int l = 0; l < R; ++l) acc[l] = 0.0;
+            for (int64_t c = 0; c < K; ++c) {
+                const double xv = x(j, c);
+                #pragma unroll
+                for (int l = 0; l < R; ++l) acc[l] += xv * C[c * R + l];
+            }
+            #pragma unroll
+            for (int l = 0; l < R; ++l) XC[j * R + l] = acc[l];
+        }
+        __syncthreads();
+    }
+
+    // (<X, model>, ||model||^2): from the A phase's rhs and Q (decomposition.py:445-449), or with a pass over X (:430-444)
+    __device__ __forceinline__ void model_terms(bool from_A, double *inner, double *model) {
+        const int t = threadIdx.x;
+        double *Q = ws + sc.Q, *rhsA = ws + sc.rhsA;
+        if (from_A) {
+            double s = 0.0, m = 0.0;
+            for (int64_t e = t; e < I * R; e += MS_THREADS) s += rhsA[e] * A[e];
+            for (int64_t i = t; i < I; i += MS_THREADS) {
+                const double *ai = A + i * R, *Qi = Q + i * R * R;
+                double v = 0.0;
+                for (int p = 0; p < R; ++p) {
+                    double w = 0.0;
+                    for (int q = 0; q < R; ++q) w += Qi[p * R + q] * ai[q];
+                    v += ai[p] * w;
+                }
+                m += v;
+            }
+            *inner = wg_sum(s, red);
+            *model = wg_sum(m, red);
+            return;
+        }
+        double *cc = ws + sc.small, *XC = ws + sc.XC;
+        ctc(cc);
+        x_times_C(XC);
+        double s = 0.0;
+        for (int64_t j = t; j < N; j += MS_THREADS) {
+            const double *ai = A + (int64_t)slab[j] * R;
+            for (int l = 0; l < R; ++l) s += XC[j * R + l] * (B[j * R + l] * ai[l]);
+        }
+        double m = 0.0;
+        for (int64_t e = t; e < I * R * R; e += MS_THREADS) {
+            const int64_t i = e / (R * R);
+            const int ab = (int)(e % (R * R)), p = ab / R, q = ab % R;
+            double g = 0.0;
+            for (int64_t j = rp[i]; j < rp[i + 1]; ++j) g += (B[j * R + p] * A[i * R + p]) * (B[j * R + q] * A[i * R + q]);
+            m += g * cc[ab];
+        }
+        *inner = wg_sum(s, red);
+        *model = wg_sum(m, red);
+    }
+
+    // one diagnostics row: rec_error, loss, flags, regularisation, gaps; returns the flags
+    __device__ __forceinline__ int diagnostics(bool from_A, double x_sq, double *row) {
+        double inner, model;
+        model_terms(from_A, &inner, &model);
+        double reg = 0.0, worst = -INFINITY, gaps[3][MCL_MAX_REGS];
+#pragma unroll
+        for (int m = 0; m < 3; ++m) {
+            double nf, gp[MCL_MAX_REGS], as;
+            mode_stats(m, &nf, gp, &as);
+#pragma unroll
+            for (int k = 0; k < MCL_MAX_REGS; ++k) {
+                gaps[m][k] = 0.0;
+                if (k >= a.o.n_regs[m]) continue;
+                gaps[m][k] = sqrt(gp[k]) / sqrt(nf);
+                worst = fmax(worst, gaps[m][k]);
+                if (a.o.regs[m][k].kind == MCL_PEN_L1) reg += a.o.regs[m][k].p0 * as;
+            }
+            if (a.o.l2_penalty[m] != 0.0) reg += 0.5 * a.o.l2_penalty[m] * nf;
+        }
+        const double rec = sqrt(fmax(0.0, x_sq - 2.0 * inner + model)) / sqrt(x_sq);
+        const double loss = 0.5 * rec * rec + reg;
+        const bool feasible = a.o.feasibility_tol > 0.0 && worst < a.o.feasibility_tol;
+        if (threadIdx.x == 0) {
+            row[0] = rec, row[1] = loss, row[3] = reg;
+#pragma unroll
+            for (int m = 0; m < 3; ++m)
+#pragma unroll
+                for (int k = 0; k < MCL_MAX_REGS; ++k) row[4 + m * MCL_MAX_REGS + k] = gaps[m][k];
+        }
+        return feasible ? 1 : 0;
+    }
+};
+
+template <int R, class XL>
+__global__ __launch_bounds__(MS_THREADS) void k_multistart(MsArgs a0) {
+    __shared__ double red[MS_THREADS];
+    __shared__ double sys[MS_SYS_BYTES / 8];
+    __shared__ double sh[4 * R * R + 16 + MCL_MAX_REGS * R * R];
+    __shared__ MsArgs sa;  // the arguments in LDS: the helpers keep a reference to them (no private copy of the kernarg)
+    if (threadIdx.x == 0) sa = a0;
+    __syncthreads();
+    const MsArgs &a = sa;
+    const int64_t s = blockIdx.x;
+    Start<R, XL> st{a, static_cast<const typename XL::T *>(a.X), a.row_ptr, a.slab_of_row, a.I, a.N, a.K};
+    st.A = a.state + s * a.state_len;
+    st.B = st.A + a.I * R;
+    st.C = st.B + a.N * R;
+    st.ws = a.scratch + s * a.scratch_len;
+    st.sc = ms_scratch(a.I, a.N, a.K, R);
+    st.red = red, st.sys = sys, st.sh = sh;
+    st.nb = std::min(MS_THREADS, MS_SYS_BYTES / (2 * R * R * 8));
+    double *diag = a.diag + s * a.diag_stride;
+    const int t = threadIdx.x;
+
+    double xs = 0.0;  // ||X||^2 (every start: the same order, the same bits)
+    for (int64_t e = t; e < a.N * a.K; e += MS_THREADS) {
+        const double v = (double)XL::ld1(st.X + e);
+        xs += v * v;
+    }
+    const double x_sq = wg_sum(xs, red);
+
+    int f0 = st.diagnostics(false, x_sq, diag);
+    if (t == 0) diag[2] = (double)(f0 | 2);
+    __syncthreads();
+    const mcl_multistart_options &o = a.o;
+    const bool active = o.tol > 0.0 || o.absolute_tol > 0.0;
+    double prev = diag[1];
+    int it = 0, code = 0;
+    for (; it < o.n_iter_max && !code; ++it) {
+        if (o.update_B) st.phase_B();
+        if (o.update_C) st.phase_C();
+        if (o.update_A) st.phase_A();
+        double *row = diag + (int64_t)(it + 1) * MCL_MS_DIAG;
+        const int feasible = st.diagnostics(o.update_A != 0, x_sq, row);
+        __syncthreads();
+        const double loss = row[1];
+        const bool evaluated = !active || feasible || o.evaluate_loss_always;
+        if (active && evaluated && o.tol > 0.0 && feasible) {
+            if (fabs(prev - loss) < o.tol * prev) code = MCL_STOP_RELATIVE;
+            else if (loss < o.absolute_tol) code = MCL_STOP_ABSOLUTE;
+        }
+        if (evaluated) prev = loss;
+        __syncthreads();
+        if (t == 0) row[2] = (double)(feasible | (evaluated ? 2 : 0));
+    }
+    if (t == 0) a.n_iter[s] = it, a.stop[s] = code;
+}
+
+struct MsPlan {
+    int64_t N, state_len, scratch_len, off_rowptr, off_slab, off_scratch, total;
+    int64_t off_aux[3][MCL_MAX_REGS], off_dual[3][MCL_MAX_REGS], off_delta[3][MCL_MAX_REGS];
+};
+
+std::string ms_check(const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank, const mcl_multistart_options *o, int32_t n_starts) {
+    if (!row_ptr || !o || I < 1 || K < 1) return "need row_ptr, options, I >= 1, K >= 1";
+    if (rank < 1 || rank > MS_MAX_RANK) return "need 1 <= rank <= 16";
+    if (n_starts < 1) return "need n_starts >= 1";
+    if (row_ptr[0] != 0) return "row_ptr[0] must be 0";
+    int64_t Jmin = INT64_MAX;
+    for (int64_t i = 0; i < I; ++i) {
+        if (row_ptr[i + 1] < row_ptr[i]) return "row_ptr must be non-decreasing";
+        Jmin = std::min(Jmin, row_ptr[i + 1] - row_ptr[i]);
+    }
+    if (row_ptr[I] >= (int64_t(1) << 31)) return "more than 2^31 packed rows are not supported";
+    if (o->inner_n_iter_max < 0 || o->n_iter_max < 0) return "need inner_n_iter_max >= 0 and n_iter_max >= 0";
+    for (int m = 0; m < 3; ++m) {
+        if (o->n_regs[m] < 0 || o->n_regs[m] > MCL_MAX_REGS) return "at most MCL_MAX_REGS penalties per mode";
+        for (int k = 0; k < o->n_regs[m]; ++k) {
+            const int kind = o->regs[m][k].kind;
+            if (kind == MCL_PEN_PARAFAC2) {
+                if (m != 1) return "PARAFAC2 only on mode 1";
+                if (Jmin < rank) return "PARAFAC2 needs every J_i >= rank";
+            } else if (kind == MCL_PEN_L2BALL) {
+                if (m == 0 && !o->constant_A) return "an L2 ball on mode 0 needs constant_A";
+            } else if (kind != MCL_PEN_NN && kind != MCL_PEN_BOX && kind != MCL_PEN_L1) {
+                return "penalty kind " + std::to_string(kind) + " is not served (NN, Box, L1, L2 ball, PARAFAC2)";
+            }
+        }
+    }
+    return "";
+}
+
+MsPlan ms_plan(const int64_t *row_ptr, int64_t I, int64_t K, int rank, const mcl_multistart_options *o, int32_t n_starts) {
+    MsPlan p{};
+    p.N = row_ptr[I];
+    const int64_t r = rank, rows[3] = {I, p.N, K};
+    int64_t off = (I + p.N + K) * r;
+    for (int m = 0; m < 3; ++m)
+        for (int k = 0; k < o->n_regs[m]; ++k) {
+            p.off_aux[m][k] = off;
+            off += rows[m] * r;
+            if (o->regs[m][k].kind == MCL_PEN_PARAFAC2) {
+                p.off_delta[m][k] = off;
+                off += r * r;
+            }
+            p.off_dual[m][k] = off;
+            off += rows[m] * r;
+        }
+    p.state_len = off;
+    p.scratch_len = ms_scratch(I, p.N, K, rank).total;
+    auto al = [](int64_t b) { return (b + 255) & ~int64_t(255); };
+    p.off_rowptr = 0;
+    p.off_slab = al((I + 1) * 8);
+    p.off_scratch = p.off_slab + al(p.N * 4);
+    p.total = p.off_scratch + al(p.scratch_len * 8 * int64_t(n_starts));
+    return p;
+}
+
+template <class XL, int R>
+void launch(const MsArgs &a, int n_starts, hipStream_t s) {
+    hipLaunchKernelGGL((k_multistart<R, XL>), dim3(n_starts), dim3(MS_THREADS), 0, s, a);
+}
+
+template <class XL>
+void launch_rank(int rank, const MsArgs &a, int n_starts, hipStream_t s) {
+    switch (rank) {
+#define MS_CASE(R) \
+    case R: launch<XL, R>(a, n_starts, s); break;
+        MS_CASE(1) MS_CASE(2) MS_CASE(3) MS_CASE(4) MS_CASE(5) MS_CASE(6) MS_CASE(7) MS_CASE(8)
+        MS_CASE(9) MS_CASE(10) MS_CASE(11) MS_CASE(12) MS_CASE(13) MS_CASE(14) MS_CASE(15) MS_CASE(16)
+#undef MS_CASE
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+const char *mcl_multistart_last_error(void) { return g_ms_error.c_str(); }
+
+int64_t mcl_multistart_workspace_bytes(const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank, const mcl_multistart_options *opt,
+                                       int32_t n_starts) {
+    if (!ms_check(row_ptr, I, K, rank, opt, n_starts).empty()) return -1;
+    return ms_plan(row_ptr, I, K, rank, opt, n_starts).total;
+}
+
+int mcl_multistart_run(const void *X, int32_t x_type, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank,
+                       const mcl_multistart_options *opt, int32_t n_starts, double *state, double *diag, int32_t *n_iter, int32_t *stop,
+                       void *workspace, int64_t workspace_bytes, void *hip_stream) {
+    auto fail = [](const std::string &m) {
+        g_ms_error = "mcl_multistart_run: " + m;
+        return 1;
+    };
+    const std::string bad = ms_check(row_ptr, I, K, rank, opt, n_starts);
+    if (!bad.empty()) return fail(bad);
+    if (!X || !state || !diag || !n_iter || !stop || !workspace) return fail("NULL argument");
+    if (x_type != MCL_X_F32 && x_type != MCL_X_BF16 && x_type != MCL_X_F16)
+        return fail("unknown x_type " + std::to_string(x_type) + " (MCL_X_F32 = 0, MCL_X_BF16 = 1, MCL_X_F16 = 2)");
+    const MsPlan p = ms_plan(row_ptr, I, K, rank, opt, n_starts);
+    if (workspace_bytes < p.total) return fail("workspace too small (mcl_multistart_workspace_bytes)");
+    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail("workspace must be 256-byte aligned");
+    hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+    char *ws = static_cast<char *>(workspace);
+    std::vector<int32_t> slab(p.N);
+    for (int64_t i = 0; i < I; ++i)
+        for (int64_t j = row_ptr[i]; j < row_ptr[i + 1]; ++j) slab[j] = (int32_t)i;
+    if (hipMemcpyAsync(ws + p.off_rowptr, row_ptr, (I + 1) * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
+        (p.N && hipMemcpyAsync(ws + p.off_slab, slab.data(), p.N * 4, hipMemcpyHostToDevice, s) != hipSuccess) ||
+        hipStreamSynchronize(s) != hipSuccess)
+        return fail("upload of row_ptr failed");
+    MsArgs a{};
+    a.X = X;
+    a.row_ptr = reinterpret_cast<const int64_t *>(ws + p.off_rowptr);
+    a.slab_of_row = reinterpret_cast<const int32_t *>(ws + p.off_slab);
+    a.I = I, a.N = p.N, a.K = K;
+    a.state_len = p.state_len, a.scratch_len = p.scratch_len;
+    a.diag_stride = int64_t(opt->n_iter_max + 1) * MCL_MS_DIAG;
+    a.state = state, a.scratch = reinterpret_cast<double *>(ws + p.off_scratch), a.diag = diag;
+    a.n_iter = n_iter, a.stop = stop;
+    for (int m = 0; m < 3; ++m)
+        for (int k = 0; k < MCL_MAX_REGS; ++k)
+            a.off_aux[m][k] = p.off_aux[m][k], a.off_dual[m][k] = p.off_dual[m][k], a.off_delta[m][k] = p.off_delta[m][k];
+    a.o = *opt;
+    mcl_x_dispatch(x_type, [&](auto xl) {
+        using XL = decltype(xl);
+        launch_rank<XL>(rank, a, n_starts, s);
+        return 0;
+    });
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(std::string("launch failed: ") + hipGetErrorString(e));
+    return 0;
+}
+
+}  // extern "C"

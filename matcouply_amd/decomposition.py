@@ -1696,3 +1696,234 @@ def parafac2_aoadmm(
         feasibility_tol=feasibility_tol, inner_tol=inner_tol, inner_n_iter_max=inner_n_iter_max, update_A=update_A,
         update_B_is=update_B_is, update_C=update_C, return_errors=return_errors, return_admm_vars=return_admm_vars,
         verbose=verbose, group=group, gather_A=gather_A, arithmetic=arithmetic)
+
+
+# ------------------------------------------------------------------------------------------------------------
+# many random starts of one problem (not in the reference: its examples hand-roll this loop)
+# ------------------------------------------------------------------------------------------------------------
+# fused starts are served up to this many elements of X (sum J_i * K): the largest shape of profiles/multistart_rate.txt, where
+# 16 fused starts take 0.42 x the time of 16 sequential calls.  method="auto" takes the fused kernel from the first start up to
+# _MULTISTART_AUTO_ANY_N elements (examples' size: 1 fused start 0.53 x one call) and from _MULTISTART_AUTO_MIN_N starts above
+# (one fused start is a whole fit on one CU: 1.9 x one call at 2^16 elements, 6.3 x at 2^18; the crossovers lie at 2 and 7 starts)
+_MULTISTART_MAX_ELEMENTS = 1 << 18
+_MULTISTART_AUTO_ANY_N = 1 << 13
+_MULTISTART_AUTO_MIN_N = 8
+_MULTISTART_KINDS = (_engine.PEN_NN, _engine.PEN_BOX, _engine.PEN_L1, _engine.PEN_L2BALL, _engine.PEN_PARAFAC2)
+
+
+def _cmf_kwargs(kwargs):
+    """the keyword arguments of a cmf_aoadmm call as a complete dict of its parameters (TypeError for unknown ones)"""
+    import inspect
+
+    bound = inspect.signature(cmf_aoadmm).bind(None, 1, **kwargs)
+    bound.apply_defaults()
+    kw = dict(bound.arguments)
+    del kw["matrices"], kw["rank"]
+    return kw
+
+
+def _start_penalties(kw, matrices, rank, random_state):
+    """one start's initial state exactly as cmf_aoadmm draws it: factors, then aux of modes 0, 1, 2, then duals"""
+    cmf = initialize_cmf(matrices, rank, kw["init"], svd_fun=None, random_state=random_state, init_params=kw["init_params"])
+    regs = _parse_all_penalties(
+        non_negative=kw["non_negative"], lower_bound=kw["lower_bound"], upper_bound=kw["upper_bound"],
+        l2_norm_bound=kw["l2_norm_bound"], unimodal=kw["unimodal"], parafac2=kw["parafac2"], l1_penalty=kw["l1_penalty"],
+        tv_penalty=kw["tv_penalty"], generalized_l2_penalty=kw["generalized_l2_penalty"], svd=kw["svd"], regs=kw["regs"],
+        dual_init=kw["dual_init"], aux_init=kw["aux_init"], verbose=False)
+    for mode, on in enumerate((kw["update_A"], kw["update_B_is"], kw["update_C"])):
+        if not on:
+            regs[mode] = []
+    auxes = initialize_aux(matrices, rank, regs, random_state=random_state)
+    duals = initialize_dual(matrices, rank, regs, random_state=random_state)
+    return cmf, regs, auxes, duals
+
+
+def _constant_flags(constant_feasibility_penalty):
+    c = constant_feasibility_penalty
+    if isinstance(c, str) and c not in {"A", "B"}:
+        raise ValueError(f"If `constant_feasibility_penalty` is a string, it must be 'A' or 'B', not {c}")
+    return bool((c and not isinstance(c, str)) or c == "A"), bool((c and not isinstance(c, str)) or c == "B")
+
+
+def _multistart_unfused_reason(matrices, rank, kw):
+    """why the fused kernel cannot run these starts (a sentence), or None.  Looks at the arguments only: no device call."""
+    if _test_engine_factory() is not None:
+        return "a substitute compute engine is installed (the fused kernel runs on the HIP engine only)"
+    if not 1 <= rank <= _engine.MS_MAX_RANK:
+        return f"rank {rank} is above {_engine.MS_MAX_RANK}"
+    if kw["verbose"]:
+        return "verbose output is not produced by the fused kernel"
+    if kw["group"] is not None or kw["gather_A"]:
+        return "group= (sharded runs) is not served"
+    if kw["arithmetic"] != "auto":
+        return f"arithmetic={kw['arithmetic']!r} is not served (the fused kernel is fp64 throughout)"
+    if kw["_byproducts"] is not None:
+        return "_byproducts is not served"
+    if kw["tol"] and kw["absolute_tol"] is None:
+        return "tol with absolute_tol=None (the reference raises TypeError in its comparison)"
+    if kw["inner_n_iter_max"] is None or int(kw["inner_n_iter_max"]) != kw["inner_n_iter_max"] or kw["n_iter_max"] is None \
+            or int(kw["n_iter_max"]) != kw["n_iter_max"] or kw["n_iter_max"] > (1 << 30):
+        return "n_iter_max and inner_n_iter_max must be integers"
+    try:
+        rows = [int(matrices.row_ptr[i + 1] - matrices.row_ptr[i]) for i in range(len(matrices))] \
+            if isinstance(matrices, PackedMatrices) else [int(shape(m)[0]) for m in matrices]
+        K = int(shape(matrices[0])[1])
+    except Exception:
+        return "the matrices are not a list of 2-D arrays"
+    if sum(rows) * K > _MULTISTART_MAX_ELEMENTS:
+        return f"X has {sum(rows) * K} elements, above the fused bound of {_MULTISTART_MAX_ELEMENTS}"
+    try:
+        _, regs, _, _ = _start_penalties(kw, matrices, rank, np.random.RandomState(0))
+    except Exception as e:  # let the sequential path raise the reference's error
+        return f"the penalties could not be set up ({type(e).__name__})"
+    constant_A, _ = _constant_flags(kw["constant_feasibility_penalty"])
+    for mode in range(3):
+        if len(regs[mode]) > _engine.MCL_MAX_REGS:
+            return f"more than {_engine.MCL_MAX_REGS} penalties on mode {mode}"
+        for reg in regs[mode]:
+            desc = penalties.native_descriptor_of(reg)
+            if desc is None or desc[0] not in _MULTISTART_KINDS:
+                return f"{type(reg).__name__} on mode {mode} is not served (NonNegativity, Box, L1Penalty, L2Ball, Parafac2)"
+            if desc[0] == _engine.PEN_PARAFAC2 and (mode != 1 or min(rows) < rank):
+                return "Parafac2 is served on mode 1 with every J_i >= rank"
+            if desc[0] == _engine.PEN_L2BALL and mode == 0 and not constant_A:
+                return "an L2Ball on mode 0 needs constant_feasibility_penalty"
+    return None
+
+
+def _multistart_fused(matrices, rank, random_states, kw):
+    device = _device()
+    X, row_ptr = _pack(matrices, device)
+    I, N, K = len(row_ptr) - 1, int(row_ptr[-1]), int(X.shape[1])
+    f32 = lambda a: np.asarray(to_numpy(a), dtype=np.float32).astype(np.float64).ravel()  # cmf_aoadmm keeps its state in fp32
+    vectors, descs = [], None
+    for rs in random_states:
+        cmf, regs, auxes, duals = _start_penalties(kw, matrices, rank, check_random_state(rs))
+        _, (A0, B0_is, C0) = cmf
+        parts = [f32(A0), np.concatenate([f32(b) for b in B0_is]), f32(C0)]
+        for mode in range(3):
+            for aux, dual in zip(auxes[mode], duals[mode]):
+                if isinstance(aux, tuple):  # PARAFAC2: (P_i list, Delta)
+                    parts += [np.concatenate([f32(p) for p in aux[0]]), f32(aux[1])]
+                else:
+                    parts.append(np.concatenate([f32(a) for a in aux]) if mode == 1 else f32(aux))
+                parts.append(np.concatenate([f32(d) for d in dual]) if mode == 1 else f32(dual))
+        vectors.append(np.concatenate(parts))
+        descs = [[penalties.native_descriptor_of(r) for r in regs[m]] for m in range(3)]
+    kinds = [[d[0] for d in descs[m]] for m in range(3)]
+    L = _engine.multistart_state_len(I, N, K, rank, kinds)
+    assert all(v.size == L for v in vectors), "multistart: state layout mismatch"
+
+    o = _engine.MultistartOptions()
+    for mode in range(3):
+        o.n_regs[mode] = len(descs[mode])
+        for k, (kind, nonneg, p0, p1) in enumerate(descs[mode]):
+            o.regs[mode][k].kind, o.regs[mode][k].non_negativity = int(kind), int(bool(nonneg))
+            o.regs[mode][k].p0, o.regs[mode][k].p1 = float(p0), float(p1)
+    l2 = [0 if v is None else v for v in _listify(kw["l2_penalty"], "l2_penalty")]
+    for mode in range(3):
+        o.l2_penalty[mode] = float(l2[mode])
+    o.feasibility_penalty_scale = float(kw["feasibility_penalty_scale"])
+    o.inner_tol = float(kw["inner_tol"]) if kw["inner_tol"] and kw["inner_tol"] > 0 else 0.0
+    o.inner_n_iter_max = int(kw["inner_n_iter_max"])
+    tol, absolute_tol, feasibility_tol = kw["tol"], kw["absolute_tol"], kw["feasibility_tol"]
+    o.tol, o.absolute_tol, o.feasibility_tol = float(tol or 0), float(absolute_tol or 0), float(feasibility_tol or 0)
+    o.constant_A, o.constant_B = _constant_flags(kw["constant_feasibility_penalty"])
+    o.update_A, o.update_B, o.update_C = bool(kw["update_A"]), bool(kw["update_B_is"]), bool(kw["update_C"])
+    o.evaluate_loss_always = bool(kw["return_errors"])
+    o.n_iter_max = max(int(kw["n_iter_max"]), 0)
+
+    state = torch.from_numpy(np.stack(vectors)).to(device)
+    diag, n_iter, stop = _engine.multistart_run(X, row_ptr, rank, o, state)
+    diag, n_iter, stop = diag.cpu().numpy(), n_iter.cpu().numpy(), stop.cpu().numpy()
+
+    out = _Out(matrices)
+    rows = (I, N, K)
+    results = []
+    for s in range(len(vectors)):
+        st = state[s]
+        pos = 0
+
+        def nxt(n_rows, cols=rank):
+            nonlocal pos
+            t = st[pos: pos + n_rows * cols].view(n_rows, cols)
+            pos += n_rows * cols
+            return t
+
+        A, B, C = nxt(I), nxt(N), nxt(K)
+        result = [CoupledMatrixFactorization((None, (out(A), out.split(B, row_ptr), out(C))))]
+        auxes_o, duals_o = [[], [], []], [[], [], []]
+        for mode in range(3):
+            for kind in kinds[mode]:
+                aux = nxt(rows[mode])
+                if kind == _engine.PEN_PARAFAC2:
+                    auxes_o[mode].append((out.split(aux, row_ptr), out(nxt(rank))))
+                else:
+                    auxes_o[mode].append(out.split(aux, row_ptr) if mode == 1 else out(aux))
+                dual = nxt(rows[mode])
+                duals_o[mode].append(out.split(dual, row_ptr) if mode == 1 else out(dual))
+        if kw["return_admm_vars"]:
+            result.append(ADMMVars(auxes=tuple(auxes_o), duals=tuple(duals_o)))
+        if kw["return_errors"]:
+            n = int(n_iter[s])
+            d = diag[s, : n + 1]
+            flags = d[:, 2].astype(np.int64)
+            kept = [0] + [t for t in range(1, n + 1) if flags[t] & 2]
+            gaps = [tuple([np.float64(d[t, 4 + m * _engine.MCL_MAX_REGS + k]) for k in range(len(kinds[m]))] for m in range(3))
+                    for t in range(n + 1)]
+            code = int(stop[s])
+            satisfied = bool(code) if (tol or absolute_tol) else None
+            message = (_StopRule.RELATIVE if code == _engine.STOP_RELATIVE else _StopRule.ABSOLUTE) if code else _StopRule.EXHAUSTED
+            feasible = _check_feasibility(gaps[-1], feasibility_tol) if feasibility_tol else None
+            result.append(DiagnosticMetrics(
+                rec_errors=[float(d[t, 0]) for t in kept], feasibility_gaps=gaps, regularized_loss=[float(d[t, 1]) for t in kept],
+                satisfied_stopping_condition=satisfied, satisfied_feasibility_condition=feasible, message=message, n_iter=n))
+        results.append(result[0] if len(result) == 1 else tuple(result))
+    return results
+
+
+def cmf_aoadmm_multistart(matrices, rank, random_states, *, method="auto", **cmf_aoadmm_kwargs):
+    """Fit the same problem from several random starts: element ``s`` of the list returned is what
+    ``cmf_aoadmm(matrices, rank, random_state=random_states[s], **cmf_aoadmm_kwargs)`` returns (same tuple structure, array
+    types and dtypes).  Start ``s`` draws its initial factors, auxiliary and dual variables with the initialisers of
+    ``cmf_aoadmm``, in its order.  The usual selection afterwards: the lowest ``regularized_loss[-1]`` among the starts with
+    ``satisfied_stopping_condition``.
+
+    ``method="sequential"`` calls ``cmf_aoadmm`` once per start (every option).  ``method="fused"`` fits all starts in one launch
+    of a HIP kernel, one workgroup per start, in fp64 (csrc/multistart.hip); it serves rank <= 16, the penalties NonNegativity,
+    Box, L1Penalty, L2Ball (mode 0: with ``constant_feasibility_penalty``) and Parafac2 on the B_i (every J_i >= rank), and X of
+    at most ``_MULTISTART_MAX_ELEMENTS`` elements; anything else raises ``NotImplementedError`` before the device is touched
+    (``verbose``, ``group=``, ``arithmetic`` other than ``"auto"``, Unimodality, TV, GeneralizedL2, UnitSimplex, user penalty
+    classes).  ``method="auto"`` takes the fused kernel when it serves the call, else the sequential loop.  Only
+    ``init="random"``: any other start would be the same N times (``ValueError``).
+    """
+    if method not in ("auto", "fused", "sequential"):
+        raise ValueError(f'method must be "auto", "fused" or "sequential", not {method!r}')
+    if "random_state" in cmf_aoadmm_kwargs:
+        raise TypeError("cmf_aoadmm_multistart takes random_states, not random_state")
+    init = cmf_aoadmm_kwargs.get("init", "random")
+    if not (isinstance(init, str) and init == "random"):
+        raise ValueError(f"cmf_aoadmm_multistart needs init=\"random\" (init={init!r} gives the same start every time)")
+    random_states = list(random_states)
+    kw = _cmf_kwargs(cmf_aoadmm_kwargs)
+    if method != "sequential":
+        reason = _multistart_unfused_reason(matrices, rank, kw)
+        if reason is None and method == "auto" and len(random_states) < _MULTISTART_AUTO_MIN_N:
+            n_el = sum(int(shape(matrices[i])[0]) for i in range(len(matrices))) * int(shape(matrices[0])[1])
+            if n_el > _MULTISTART_AUTO_ANY_N:
+                reason = f"{len(random_states)} starts of {n_el} elements run faster one by one"
+        if reason is None:
+            return _multistart_fused(matrices, rank, random_states, kw) if random_states else []
+        if method == "fused":
+            raise NotImplementedError(f"cmf_aoadmm_multistart(method=\"fused\"): {reason}")
+    return [cmf_aoadmm(matrices, rank, random_state=rs, **cmf_aoadmm_kwargs) for rs in random_states]
+
+
+def parafac2_aoadmm_multistart(matrices, rank, random_states, *, method="auto", **parafac2_aoadmm_kwargs):
+    """:func:`cmf_aoadmm_multistart` with the PARAFAC2 constraint on mode 1: element ``s`` is what
+    ``parafac2_aoadmm(matrices, rank, random_state=random_states[s], **parafac2_aoadmm_kwargs)`` returns."""
+    if "parafac2" in parafac2_aoadmm_kwargs:
+        raise TypeError("parafac2_aoadmm_multistart() got an unexpected keyword argument 'parafac2'")
+    kwargs = dict(parafac2_aoadmm_kwargs)
+    kwargs.setdefault("l2_penalty", 0)
+    return cmf_aoadmm_multistart(matrices, rank, random_states, method=method, parafac2=True, **kwargs)

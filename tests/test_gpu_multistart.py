@@ -1,0 +1,254 @@
+"""GPU: cmf_aoadmm_multistart / parafac2_aoadmm_multistart with the fused kernel (csrc/multistart.hip) - oracle parity per
+start, the examples' multi-start selection, bitwise independence of the batch, 16-bit X, return types, speed and resources."""
+import time
+
+import numpy as np
+import pytest
+
+torch = pytest.importorskip("torch")
+
+from matcouply_amd import decomposition as dec  # noqa: E402
+from matcouply_amd import penalties as pen  # noqa: E402
+from matcouply_amd._utils import check_random_state  # noqa: E402
+from oracle import aoadmm_oracle as orc  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+
+def _ragged(seed=0, I=6, K=9, r=3):
+    rng = np.random.RandomState(seed)
+    J = rng.randint(5, 12, size=I)
+    X, row_ptr = orc.synthetic_problem(I, J, K, r, seed=seed, dtype=np.float32)
+    return [X[row_ptr[i]: row_ptr[i + 1]].astype(np.float64) for i in range(I)], X, row_ptr
+
+
+def _truncated_normal(rng, size):
+    x = rng.standard_normal(size=size)
+    x[x < 0] = 0
+    return x
+
+
+def _example_problem(I, J, K, rank, noise_level, c_normal):
+    """the simulated PARAFAC2 data of the reference's examples (plot_simulated_nonnegative, plot_examining_...)"""
+    rng = np.random.default_rng(0)
+    A = rng.uniform(size=(I, rank)) + 0.1
+    B_blueprint = _truncated_normal(rng, (J, rank))
+    B_is = [np.roll(B_blueprint, i, axis=0) for i in range(I)]
+    C = rng.standard_normal(size=(K, rank)) if c_normal else _truncated_normal(rng, (K, rank))
+    matrices = [(B_i * A[i]) @ C.T for i, B_i in enumerate(B_is)]
+    noise = [rng.uniform(size=M.shape) for M in matrices]
+    return [M + N * noise_level * np.linalg.norm(M) / np.linalg.norm(N) for M, N in zip(matrices, noise)]
+
+
+def _desc(reg):
+    if isinstance(reg, pen.Parafac2):
+        return {"kind": "parafac2"}
+    if isinstance(reg, pen.L1Penalty):
+        return {"kind": "l1", "reg_strength": reg.reg_strength, "non_negativity": reg.non_negativity}
+    if isinstance(reg, pen.L2Ball):
+        return {"kind": "l2ball", "norm_bound": reg.norm_bound, "non_negativity": reg.non_negativity}
+    if isinstance(reg, pen.Box):
+        return {"kind": "box", "min_val": reg.min_val, "max_val": reg.max_val}
+    if isinstance(reg, pen.NonNegativity):
+        return {"kind": "nn"}
+    raise AssertionError(type(reg))
+
+
+def _oracle_state(mats, X, row_ptr, rank, seed, kw):
+    """the oracle started from start `seed`'s exact initial state (drawn as cmf_aoadmm draws it, stored in fp32)"""
+    full = dec._cmf_kwargs(kw)
+    cmf, regs, auxes, duals = dec._start_penalties(full, mats, rank, check_random_state(seed))
+    f = lambda a: np.asarray(a, dtype=np.float32).astype(np.float64)
+    _, (A, B_is, C) = cmf
+    descs = [[_desc(r) for r in regs[m]] for m in range(3)]
+    aux = [[], [], []]
+    dual = [[], [], []]
+    for m in range(3):
+        for a_, d_ in zip(auxes[m], duals[m]):
+            if isinstance(a_, tuple):
+                aux[m].append((f(np.concatenate(a_[0])), f(a_[1])))
+            else:
+                aux[m].append(f(np.concatenate(a_)) if m == 1 else f(a_))
+            dual[m].append(f(np.concatenate(d_)) if m == 1 else f(d_))
+    l2 = dec._listify(full["l2_penalty"], "l2_penalty")
+    cA, cB = dec._constant_flags(full["constant_feasibility_penalty"])
+    return orc.OracleState(X.astype(np.float64), row_ptr, f(A), f(np.concatenate(B_is)), f(C), descs, aux, dual,
+                           l2=[v or 0.0 for v in l2], inner_n_iter_max=full["inner_n_iter_max"],
+                           feasibility_penalty_scale=full["feasibility_penalty_scale"], constant_A=cA, constant_B=cB)
+
+
+STACKS = {
+    "nn_l1C": dict(non_negative={0: True, 1: True}, l1_penalty={2: 0.05}),
+    "box_l2ball": dict(lower_bound={1: -0.5}, upper_bound={1: 2.0}, l2_norm_bound={0: 3.0, 2: 2.0},
+                       constant_feasibility_penalty=True),
+    "parafac2_nn": dict(parafac2=True, non_negative=True),
+    "ridge_constant": dict(l2_penalty=[0.1, 0.2, 0.05], non_negative={2: True}, constant_feasibility_penalty=True),
+}
+
+
+@pytest.mark.parametrize("stack", sorted(STACKS))
+def test_oracle_parity_per_start(stack):
+    mats, X, row_ptr = _ragged()
+    rank = 3
+    kw = dict(STACKS[stack], n_iter_max=20, tol=None, return_errors=True)
+    got = dec.cmf_aoadmm_multistart(mats, rank, range(8), method="fused", **kw)
+    assert len(got) == 8
+    worst = 0.0
+    for s, (cmf, diag) in enumerate(got):
+        st = _oracle_state(mats, X, row_ptr, rank, s, kw)
+        res = orc.run(st, 20, tol=None, absolute_tol=None)
+        _, (A, B_is, C) = cmf
+        rel = lambda a, b: np.linalg.norm(np.asarray(a) - b) / max(np.linalg.norm(b), 1e-300)
+        errs = [rel(A, st.A), rel(np.concatenate(B_is), st.B), rel(C, st.C),
+                np.max(np.abs(np.array(diag.rec_errors) - res["rec_errors"]) / np.array(res["rec_errors"])),
+                np.max(np.abs(np.array(diag.regularized_loss) - res["losses"]) / np.array(res["losses"]))]
+        for g_got, g_ref in zip(diag.feasibility_gaps, res["gaps"]):
+            for m in range(3):
+                if len(g_ref[m]):
+                    errs.append(np.max(np.abs(np.array(g_got[m]) - g_ref[m]) / np.maximum(np.abs(g_ref[m]), 1e-3)))
+        assert diag.n_iter == 20 and diag.satisfied_stopping_condition is False  # (absolute_tol stays set, as in cmf_aoadmm)
+        worst = max(worst, max(errs))
+        assert max(errs) < 1e-5, (stack, s, errs)
+
+
+@pytest.mark.parametrize("problem", ["simulated_nonnegative", "examining_components"])
+def test_examples_pick_the_same_start(problem):
+    """The examples' loop (default tolerances, 1000 iterations, 5 starts).  The fused kernel follows the fp64 restatement of
+    the reference from every start: the same iteration count, stopping verdict and best start.  The sequential engine keeps
+    its factors in fp32, below the resolution of tol=1e-8 on the relative loss change, so its verdicts can differ from start
+    to start; the best loss found agrees."""
+    if problem == "simulated_nonnegative":
+        mats, rank, kw = _example_problem(10, 15, 20, 3, 0.2, False), 3, dict(non_negative=True)
+    else:
+        mats, rank, kw = _example_problem(5, 10, 15, 4, 0.1, True), 4, dict(non_negative=[True, False, False])
+    args = dict(kw, n_iter_max=1000, return_errors=True)
+    fused = dec.parafac2_aoadmm_multistart(mats, rank, range(5), method="fused", **args)
+    seq = dec.parafac2_aoadmm_multistart(mats, rank, range(5), method="sequential", **args)
+    X = np.concatenate(mats).astype(np.float32)
+    row_ptr = np.concatenate([[0], np.cumsum([m.shape[0] for m in mats])])
+    oracle = []
+    for s in range(5):
+        st = _oracle_state(mats, X, row_ptr, rank, s, dict(args, parafac2=True, l2_penalty=0))
+        oracle.append(orc.run(st, 1000))
+
+    def best(losses, ok):
+        losses = [l if o else np.inf for l, o in zip(losses, ok)]
+        return int(np.argmin(losses)), min(losses)
+
+    assert [d.satisfied_stopping_condition for _, d in fused] == [r["satisfied_stopping_condition"] for r in oracle]
+    assert [d.n_iter for _, d in fused] == [r["n_iter"] for r in oracle]
+    i_f, l_f = best([d.regularized_loss[-1] for _, d in fused], [d.satisfied_stopping_condition for _, d in fused])
+    i_o, l_o = best([r["losses"][-1] for r in oracle], [r["satisfied_stopping_condition"] for r in oracle])
+    i_s, l_s = best([d.regularized_loss[-1] for _, d in seq], [d.satisfied_stopping_condition for _, d in seq])
+    assert i_f == i_o and abs(l_f - l_o) <= 1e-8 * l_o
+    assert abs(l_f - l_s) <= 1e-4 * abs(l_s)
+    # auto takes the fused kernel here
+    auto = dec.parafac2_aoadmm_multistart(mats, rank, range(5), **args)
+    for (c_a, d_a), (c_f, d_f) in zip(auto, fused):
+        np.testing.assert_array_equal(c_a[1][0], c_f[1][0])
+        assert d_a.regularized_loss == d_f.regularized_loss
+
+
+def _bits(res):
+    cmf, admm, diag = res
+    _, (A, B_is, C) = cmf
+    arrays = [A, *B_is, C] + [x for mode in admm.auxes for a in mode for x in (a if isinstance(a, tuple) else [a])
+                              for x in (x if isinstance(x, list) else [x])]
+    return [np.asarray(a).tobytes() for a in arrays] + [np.array(diag.regularized_loss).tobytes(), diag.n_iter]
+
+
+def test_start_alone_equals_start_in_a_batch_and_runs_repeat():
+    mats, _, _ = _ragged(seed=2)
+    kw = dict(parafac2=True, non_negative=True, n_iter_max=300, return_errors=True, return_admm_vars=True)
+    batch = dec.cmf_aoadmm_multistart(mats, 3, range(64), method="fused", **kw)
+    again = dec.cmf_aoadmm_multistart(mats, 3, range(64), method="fused", **kw)
+    for s in (0, 17, 63):
+        alone = dec.cmf_aoadmm_multistart(mats, 3, [s], method="fused", **kw)[0]
+        assert _bits(alone) == _bits(batch[s])
+    assert all(_bits(a) == _bits(b) for a, b in zip(batch, again))
+
+
+@pytest.mark.parametrize("dtype", ["bfloat16", "float16"])
+def test_x16_equals_upcast(dtype):
+    mats, _, _ = _ragged(seed=3)
+    m16 = [torch.tensor(m, dtype=getattr(torch, dtype), device="cuda") for m in mats]
+    m32 = [m.float() for m in m16]
+    kw = dict(non_negative=True, l1_penalty={2: 0.05}, n_iter_max=50, return_errors=True, return_admm_vars=True)
+    a = dec.cmf_aoadmm_multistart(m16, 3, range(4), method="fused", **kw)
+    b = dec.cmf_aoadmm_multistart(m32, 3, range(4), method="fused", **kw)
+    for (ca, _, da), (cb, _, db) in zip(a, b):
+        # the fp64 diagnostics are bitwise equal; the factors come back in the input's dtype
+        assert da.regularized_loss == db.regularized_loss and da.rec_errors == db.rec_errors
+        assert da.feasibility_gaps == db.feasibility_gaps
+        for x, y in zip([ca[1][0], *ca[1][1], ca[1][2]], [cb[1][0], *cb[1][1], cb[1][2]]):
+            assert x.dtype == getattr(torch, dtype) and torch.equal(x, y.to(x.dtype))
+
+
+@pytest.mark.parametrize("kind", ["numpy", "torch_cpu", "torch_cuda"])
+def test_return_types_match_cmf_aoadmm(kind):
+    mats, _, _ = _ragged(seed=4)
+    if kind == "torch_cpu":
+        mats = [torch.tensor(m, dtype=torch.float32) for m in mats]
+    elif kind == "torch_cuda":
+        mats = [torch.tensor(m, dtype=torch.float32, device="cuda") for m in mats]
+    kw = dict(parafac2=True, non_negative=True, n_iter_max=5, return_errors=True, return_admm_vars=True)
+    fused = dec.cmf_aoadmm_multistart(mats, 3, [0], method="fused", **kw)[0]
+    single = dec.cmf_aoadmm(mats, 3, random_state=0, **kw)
+
+    def walk(a, b):
+        assert type(a) is type(b), (type(a), type(b))
+        if isinstance(a, (tuple, list)):
+            assert len(a) == len(b)
+            for x, y in zip(a, b):
+                walk(x, y)
+        elif isinstance(a, np.ndarray) or (torch.is_tensor(a)):
+            assert a.dtype == b.dtype and tuple(a.shape) == tuple(b.shape)
+            if torch.is_tensor(a):
+                assert a.device == b.device
+
+    cmf_f, admm_f, diag_f = fused
+    cmf_s, admm_s, diag_s = single
+    walk(cmf_f[1], cmf_s[1])
+    walk(admm_f.auxes, admm_s.auxes)
+    walk(admm_f.duals, admm_s.duals)
+    assert type(diag_f) is type(diag_s) and diag_f.n_iter == diag_s.n_iter
+    assert len(diag_f.rec_errors) == len(diag_s.rec_errors) and len(diag_f.feasibility_gaps) == len(diag_s.feasibility_gaps)
+    assert dec.cmf_aoadmm_multistart(mats, 3, [0], method="fused", n_iter_max=2)[0].__class__ is \
+        dec.cmf_aoadmm(mats, 3, random_state=0, n_iter_max=2).__class__
+
+
+# profiles/multistart_rate.txt: at the examples' shape (10 x 15 x 20, rank 3, NN PARAFAC2, 200 iterations, tol=None) fused /
+# sequential is 0.042 at 16 starts and 0.017 at 64 (about 0.03 at 32).  The guard asks for 10x (the issue's expectation); the
+# headroom over the measured ratio absorbs the run-to-run noise of a ~40 ms measurement on a shared machine
+RATE_GUARD = 0.10
+
+
+def test_rate_guard_examples_size():
+    mats = _example_problem(10, 15, 20, 3, 0.2, False)
+    kw = dict(non_negative=True, n_iter_max=200, tol=None)
+    dec.parafac2_aoadmm_multistart(mats, 3, range(32), method="fused", **kw)  # warm-up (library load, code objects)
+    dec.parafac2_aoadmm_multistart(mats, 3, range(2), method="sequential", **kw)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    dec.parafac2_aoadmm_multistart(mats, 3, range(32), method="fused", **kw)
+    torch.cuda.synchronize()
+    t_fused = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    dec.parafac2_aoadmm_multistart(mats, 3, range(32), method="sequential", **kw)
+    torch.cuda.synchronize()
+    t_seq = time.perf_counter() - t0
+    print(f"fused {t_fused * 1e3:.1f} ms, sequential {t_seq * 1e3:.1f} ms, ratio {t_fused / t_seq:.3f}")
+    assert t_fused <= RATE_GUARD * t_seq, (t_fused, t_seq)
+
+
+def test_no_scratch_in_the_fused_kernel():
+    import os
+    import sys
+
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+    import kernel_resources
+
+    ms = [k for k in kernel_resources.resources() if k["kernel"].startswith("k_multistart<")]
+    assert len(ms) == 48, [k["kernel"] for k in ms]  # ranks 1..16 x {fp32, bf16, fp16}
+    spilled = [(k["kernel"], k["scratch_bytes"], k["vgpr_spill"]) for k in ms if k["scratch_bytes"] or k["vgpr_spill"]]
+    assert not spilled, spilled
