@@ -297,6 +297,22 @@ int mcl_als_init_typed(const void *X, int32_t x_type, const int64_t *row_ptr, in
                        int64_t workspace_bytes, void *hip_stream);
 const char *mcl_als_init_last_error(void);
 
+/* ---- parafac2_als (decomposition.py, csrc/parafac2als.hip): unconstrained PARAFAC2-ALS for data resident in HBM ------------- */
+/* Model X_i ~ P_i B diag(a_i) C^T, P_i^T P_i = I.  Start: A0 [I, rank], B0 [rank, rank], C0 [K, rank] (fp64, device), or all NULL:
+ * A = 1, B = I, C = the C of mcl_svd_init (needs K <= 2048).  Per iteration: the projections from the polar factor of
+ * X_i C diag(a_i) B^T, then n_iter_parafac CP sweeps (modes A, B, C) on the projected tensor; ALS normal equations, one HALS
+ * column pass for the modes in nn_modes (bit 0: A, bit 2: C; mode B cannot be non-negative).  tol > 0: errors[t] = the relative
+ * reconstruction error after iteration t; stop after t >= 1 when |e_{t-1}^2 - e_t^2| <= tol e_{t-1}^2 or e_t^2 < absolute_tol
+ * (evaluated on the device; the host reads the verdict every 16 iterations).  Outputs A [I, rank], B [rank, rank], C [K, rank],
+ * P packed [N, rank] (the projections), info int32[1] = iterations used.  Needs rank <= 32 and rank <= min(J_i, K).
+ * Deterministic (fixed reduction orders).  row_ptr: HOST int64[I+1]; everything else: device pointers. */
+int64_t mcl_parafac2_als_workspace_bytes(const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank);
+int mcl_parafac2_als_typed(const void *X, int32_t x_type, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank, const double *A0,
+                           const double *B0, const double *C0, int32_t n_iter_max, int32_t n_iter_parafac, double tol,
+                           double absolute_tol, int32_t nn_modes, float *A, float *B, float *C, float *P, double *errors,
+                           int32_t *info, void *workspace, int64_t workspace_bytes, void *hip_stream);
+const char *mcl_parafac2_als_last_error(void);
+
 /* ---- many random starts of one problem at once (cmf_aoadmm_multistart, csrc/multistart.hip) ------------------------------- */
 /* One workgroup per start runs the whole fit (phases B, C, A, diagnostics and the stopping rule of mcl_run) in fp64 with
  * workgroup barriers only; X is shared and read-only.  Stateless; X, state, diag, n_iter, stop, workspace: device pointers;

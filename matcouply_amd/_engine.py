@@ -61,6 +61,7 @@ EXPORTED_SYMBOLS = [
     "mcl_set_problem_typed", "mcl_svd_init_typed",
     "mcl_als_init_workspace_bytes", "mcl_als_init_typed", "mcl_als_init_last_error",
     "mcl_multistart_workspace_bytes", "mcl_multistart_run", "mcl_multistart_last_error",
+    "mcl_parafac2_als_workspace_bytes", "mcl_parafac2_als_typed", "mcl_parafac2_als_last_error",
 ]
 
 
@@ -188,6 +189,10 @@ def load_library():
         "mcl_multistart_run": (ctypes.c_int, [P, I32, ctypes.POINTER(I64), I64, I64, I32, ctypes.POINTER(MultistartOptions), I32, P, P,
                                               P, P, P, I64, P]),
         "mcl_multistart_last_error": (ctypes.c_char_p, []),
+        "mcl_parafac2_als_workspace_bytes": (I64, [ctypes.POINTER(I64), I64, I64, I32]),
+        "mcl_parafac2_als_typed": (ctypes.c_int, [P, I32, ctypes.POINTER(I64), I64, I64, I32, P, P, P, I32, I32, ctypes.c_double,
+                                                  ctypes.c_double, I32, P, P, P, P, P, P, P, I64, P]),
+        "mcl_parafac2_als_last_error": (ctypes.c_char_p, []),
         "mcl_read_bandwidth": (ctypes.c_int, [P, I64, I32, P, P, ctypes.POINTER(ctypes.c_double)]),
     }
     for name, (res, args) in sig.items():
@@ -312,6 +317,52 @@ def als_init(X, row_ptr, rank, method, n_iter_max, tol):
     if rc != 0:
         raise EngineError(lib.mcl_als_init_last_error().decode())
     return A, B, C, errors[: int(info.item())]
+
+
+PF2ALS_MAX_RANK = 32
+
+
+def parafac2_als(X, row_ptr, rank, start, n_iter_max, n_iter_parafac, tol, absolute_tol, nn_modes):
+    """parafac2_als on the device (mcl_parafac2_als_typed).  X packed [sum J_i, K] float32 / bfloat16 / float16 CUDA tensor;
+    start: (A0 [I, rank], B0 [rank, rank], C0 [K, rank]) float64 CUDA tensors, or None for the svd start; nn_modes: modes (0 / 2)
+    fitted non-negative.  -> (A [I, rank], B [rank, rank], C [K, rank], P packed [sum J_i, rank] (the projections), errors
+    float64 [iterations used] (empty when tol = 0))"""
+    import torch
+
+    lib = load_library()
+    xt = x_type_of(X.dtype)
+    if not (X.is_cuda and X.is_contiguous()):
+        raise EngineError("X must be a contiguous CUDA tensor")
+    row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int64)
+    I, K, N, r = len(row_ptr) - 1, int(X.shape[1]), int(X.shape[0]), int(rank)
+    rp = row_ptr.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+    nbytes = lib.mcl_parafac2_als_workspace_bytes(rp, I, K, r)
+    if nbytes < 0:
+        raise EngineError("mcl_parafac2_als_workspace_bytes: bad arguments")
+    dev = X.device
+    if start is not None:
+        start = [torch.as_tensor(t, dtype=torch.float64, device=dev).contiguous() for t in start]
+        if [tuple(t.shape) for t in start] != [(I, r), (r, r), (K, r)]:
+            raise EngineError("start factors must be [I, rank], [rank, rank], [K, rank]")
+    ws = torch.empty(int(nbytes) + 256, dtype=torch.uint8, device=dev)
+    off = (-ws.data_ptr()) % 256
+    A = torch.empty((I, r), dtype=torch.float32, device=dev)
+    B = torch.empty((r, r), dtype=torch.float32, device=dev)
+    C = torch.empty((K, r), dtype=torch.float32, device=dev)
+    P = torch.empty((N, r), dtype=torch.float32, device=dev)
+    errors = torch.zeros(max(int(n_iter_max), 1), dtype=torch.float64, device=dev)
+    info = torch.zeros(1, dtype=torch.int32, device=dev)
+    mask = sum(1 << int(m) for m in (nn_modes or ()))
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = lib.mcl_parafac2_als_typed(X.data_ptr(), xt, rp, I, K, r, *(t.data_ptr() for t in start) if start is not None else
+                                        (None, None, None), int(n_iter_max), int(n_iter_parafac), float(tol), float(absolute_tol),
+                                        int(mask), A.data_ptr(), B.data_ptr(), C.data_ptr(), P.data_ptr(), errors.data_ptr(),
+                                        info.data_ptr(), ws.data_ptr() + off, nbytes, ctypes.c_void_p(stream))
+    if rc != 0:
+        raise EngineError(lib.mcl_parafac2_als_last_error().decode())
+    used = int(info.item())
+    return A, B, C, P, errors[: used if tol > 0 else 0]
 
 
 def multistart_state_len(I, N, K, rank, kinds):

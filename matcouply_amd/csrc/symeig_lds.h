@@ -4,11 +4,13 @@
 #include <hip/hip_runtime.h>
 
 // eigen-decomposition of the symmetric m x m matrix S (LDS) by cyclic Jacobi with round-robin pairs: W <- eigenvectors
-// (columns), the diagonal of S <- eigenvalues.  me = m rounded up to even (a dummy player idles).  All 256 threads call it.
-static __device__ void jacobi_lds(double *S, double *W, double *cs, int m) {
+// (columns), the diagonal of S <- eigenvalues.  me = m rounded up to even (a dummy player idles).  All NT threads of the
+// workgroup call it.
+template <int NT>
+static __device__ void jacobi_lds_nt(double *S, double *W, double *cs, int m) {
     const int tid = threadIdx.x;
     const int me = (m + 1) & ~1, half = me / 2;
-    for (int e = tid; e < m * m; e += 256) W[e] = ((e / m) == (e % m)) ? 1.0 : 0.0;
+    for (int e = tid; e < m * m; e += NT) W[e] = ((e / m) == (e % m)) ? 1.0 : 0.0;
     __shared__ double off_sh, diag_sh;
     __syncthreads();
     for (int sweep = 0; sweep < 40; ++sweep) {
@@ -42,7 +44,7 @@ static __device__ void jacobi_lds(double *S, double *W, double *cs, int m) {
                 cs[2 * tid] = c, cs[2 * tid + 1] = s;
             }
             __syncthreads();
-            for (int e = tid; e < half * m; e += 256) {  // columns p, q of S and of W, every row i
+            for (int e = tid; e < half * m; e += NT) {  // columns p, q of S and of W, every row i
                 const int k = e / m, i = e - k * m;
                 int p, q;
                 pair_of(k, p, q);
@@ -54,7 +56,7 @@ static __device__ void jacobi_lds(double *S, double *W, double *cs, int m) {
                 W[i * m + p] = c * wp - s * wq, W[i * m + q] = s * wp + c * wq;
             }
             __syncthreads();
-            for (int e = tid; e < half * m; e += 256) {  // rows p, q of S, every column j
+            for (int e = tid; e < half * m; e += NT) {  // rows p, q of S, every column j
                 const int k = e / m, j = e - k * m;
                 int p, q;
                 pair_of(k, p, q);
@@ -68,3 +70,5 @@ static __device__ void jacobi_lds(double *S, double *W, double *cs, int m) {
     }
     __syncthreads();
 }
+// the same with the 256 threads of the initialisers' workgroups
+static __device__ void jacobi_lds(double *S, double *W, double *cs, int m) { jacobi_lds_nt<256>(S, W, cs, m); }

@@ -22,7 +22,7 @@ from ._utils import check_random_state, get_svd, is_iterable, is_tensor, is_torc
 from .coupled_matrices import CoupledMatrixFactorization
 
 __all__ = ["compute_feasibility_gaps", "ADMMVars", "DiagnosticMetrics", "cmf_aoadmm", "parafac2_aoadmm",
-           "PackedMatrices", "partition_slabs"]
+           "PackedMatrices", "partition_slabs", "parafac2_als"]
 
 # TEST-ONLY seam.  The CPU test-suite (tests/oracle_engine.py) substitutes a checker engine here to exercise the host and
 # multi-process logic without a GPU.  The substitution is honoured only under MATCOUPLY_AMD_TEST_ENGINE=1, which
@@ -240,7 +240,8 @@ def initialize_cmf(matrices, rank, init, svd_fun, random_state=None, init_params
     if init == "parafac2_als":
         raise NotImplementedError(
             f'init="{init}" delegates to TensorLy decompositions in the reference (decomposition.py:55-73) and is '
-            "out of scope of this engine; pass an explicit (weights, (A, B_is, C)) tuple instead.")
+            "out of scope of this engine; pass an explicit (weights, (A, B_is, C)) tuple instead, e.g. "
+            "CoupledMatrixFactorization.from_Parafac2Tensor(parafac2_als(matrices, rank)).")
     raise ValueError('Initialization method "{}" not recognized'.format(init))
 
 
@@ -532,6 +533,88 @@ class DiagnosticMetrics(NamedTuple):
     satisfied_feasibility_condition: Optional[bool]  #: None if no tolerance is set
     n_iter: int  #: Number of iterations ran
     message: str  #: Convergence message
+
+
+# ------------------------------------------------------------------------------------------------------------
+# parafac2_als: unconstrained PARAFAC2-ALS (TensorLy's parafac2) on the device
+# ------------------------------------------------------------------------------------------------------------
+# TensorLy keywords of parafac2 that are not served, with the value that is (their default)
+_PF2ALS_TENSORLY_DEFAULTS = {"svd": "truncated_svd", "normalize_factors": False, "verbose": False, "linesearch": False}
+
+
+def _parafac2_als_options(matrices, rank, init, nn_modes, n_iter_max, n_iter_parafac, kwargs):
+    """the checked (I, K, rows, nn_modes) of a parafac2_als call; raises before the device is touched"""
+    for key, value in kwargs.items():
+        if key not in _PF2ALS_TENSORLY_DEFAULTS:
+            raise TypeError(f"parafac2_als() got an unexpected keyword argument {key!r}")
+        if value != _PF2ALS_TENSORLY_DEFAULTS[key]:
+            raise NotImplementedError(f"parafac2_als: {key}={value!r} is not supported (only {key}="
+                                      f"{_PF2ALS_TENSORLY_DEFAULTS[key]!r})")
+    if not isinstance(init, str) or init not in ("random", "svd"):
+        raise ValueError(f'parafac2_als: init must be "random" or "svd", not {init!r}')
+    if nn_modes is None:
+        modes = set()
+    elif isinstance(nn_modes, str):
+        if nn_modes != "all":
+            raise ValueError(f'parafac2_als: nn_modes must be None, "all" or a collection of modes, not {nn_modes!r}')
+        modes = {0, 1, 2}
+    else:
+        try:
+            modes = set(nn_modes)
+        except TypeError:
+            raise ValueError(f"parafac2_als: nn_modes must be None, \"all\" or a collection of modes, not {nn_modes!r}") from None
+        if not all(isinstance(m, (int, np.integer)) and not isinstance(m, bool) and 0 <= m <= 2 for m in modes):
+            raise ValueError(f"parafac2_als: nn_modes may hold the modes 0, 1 and 2 only, not {sorted(modes, key=str)!r}")
+    if 1 in modes:
+        raise NotImplementedError("parafac2_als: non-negativity on mode 1 (B) cannot be met by PARAFAC2-ALS (TensorLy only warns "
+                                  "and leaves it unconstrained); constrain the modes 0 and 2 only, or fit parafac2_aoadmm")
+    for name, v in (("n_iter_max", n_iter_max), ("n_iter_parafac", n_iter_parafac)):
+        if isinstance(v, bool) or int(v) != v or v < 1:
+            raise ValueError(f"parafac2_als: {name} must be a positive integer, not {v!r}")
+    K = int(shape(matrices[0])[1])
+    rows = [int(shape(m)[0]) for m in matrices] if not isinstance(matrices, PackedMatrices) else \
+        [int(matrices.row_ptr[i + 1] - matrices.row_ptr[i]) for i in range(len(matrices))]
+    if rank > _engine.PF2ALS_MAX_RANK:
+        raise NotImplementedError(f"parafac2_als: rank {rank} is above the served bound {_engine.PF2ALS_MAX_RANK}")
+    if min(rows) < rank or K < rank:
+        raise NotImplementedError(f"parafac2_als: every matrix needs J_i >= rank and K >= rank (min J_i = {min(rows)}, K = {K}, "
+                                  f"rank = {rank})")
+    if init == "svd" and K > _DEVICE_SVD_MAX_K:
+        raise NotImplementedError(f'parafac2_als: init="svd" needs K <= {_DEVICE_SVD_MAX_K} (K = {K})')
+    return len(rows), K, rows, sorted(modes)
+
+
+def parafac2_als(matrices, rank, n_iter_max=2000, init="random", tol=1e-8, absolute_tol=1e-13, nn_modes=None, n_iter_parafac=5,
+                 random_state=None, return_errors=False, **kwargs):
+    """Unconstrained PARAFAC2 fitted by alternating least squares (TensorLy's ``parafac2``), on the device.
+
+    Model ``X_i ~ P_i B diag(a_i) C^T`` with orthonormal projections ``P_i``.  Every iteration forms the projections from the
+    polar factor of ``X_i C diag(a_i) B^T``, projects the slabs and runs ``n_iter_parafac`` CP sweeps on the projected tensor
+    (modes in ``nn_modes`` - 0 and/or 2 - take one non-negative HALS pass instead of the ALS normal equations).
+    ``init="svd"``: A = 1, B = I, C = the right singular vectors of the stacked matrices; ``init="random"``: A, B, C drawn
+    uniformly from ``check_random_state(random_state)`` in that order.  With a truthy ``tol`` the relative reconstruction error
+    is tracked and the fit stops when ``|e_{t-1}^2 - e_t^2| <= tol e_{t-1}^2`` or ``e_t^2 < absolute_tol``.
+
+    ``matrices``: as for :func:`cmf_aoadmm`.  Returns ``(weights, (A, B, C), projections)`` with ``weights`` None, B of shape
+    rank x rank and ``projections[i]`` J_i x rank, in the input's array type; with ``return_errors=True`` also the list of
+    errors.  Not served (``NotImplementedError``): nn_modes containing 1, rank above 32, J_i < rank or K < rank, and the
+    TensorLy options ``svd``, ``normalize_factors``, ``linesearch`` and ``verbose`` other than their defaults.
+    """
+    rank = int(rank)
+    I, K, rows, modes = _parafac2_als_options(matrices, rank, init, nn_modes, n_iter_max, n_iter_parafac, kwargs)
+    start = None
+    if init == "random":
+        rs = check_random_state(random_state)
+        start = (rs.uniform(size=(I, rank)), rs.uniform(size=(rank, rank)), rs.uniform(size=(K, rank)))
+    tol = float(tol) if tol else 0.0
+    absolute_tol = float(absolute_tol) if absolute_tol else 0.0
+    X, row_ptr = _pack(matrices, _device())
+    A, B, C, P, errors = _engine.parafac2_als(X, row_ptr, rank, start, int(n_iter_max), int(n_iter_parafac), tol, absolute_tol, modes)
+    out = _Out(matrices)
+    result = (None, (out(A), out(B), out(C)), out.split(P, row_ptr))
+    if return_errors:
+        return result, [float(e) for e in errors.cpu().numpy()]
+    return result
 
 
 # ------------------------------------------------------------------------------------------------------------
