@@ -1871,6 +1871,16 @@ def _multistart_unfused_reason(matrices, rank, kw):
                 return "Parafac2 is served on mode 1 with every J_i >= rank"
             if desc[0] == _engine.PEN_L2BALL and mode == 0 and not constant_A:
                 return "an L2Ball on mode 0 needs constant_feasibility_penalty"
+    if min(rows) == 0:
+        # an empty X_i has B_i^T B_i = 0 and a_i = 0: its A row and B_i systems are l2 + rho n times the identity, where rho is
+        # the slab's own (zero) feasibility penalty unless it is held constant over the slabs.  Singular systems raise in the
+        # reference; the fused kernel would invert them
+        l2 = _listify(kw["l2_penalty"], "l2_penalty")
+        _, constant_B = _constant_flags(kw["constant_feasibility_penalty"])
+        for mode, constant in ((0, constant_A), (1, constant_B)):
+            if not ((l2[mode] or 0) > 0 or (constant and regs[mode])):
+                return (f"an empty matrix leaves its mode-{mode} system singular (needs l2_penalty on mode {mode}, or a "
+                        "penalty there with constant_feasibility_penalty)")
     return None
 
 

@@ -76,14 +76,15 @@ def cp_init(matrices, rank, hals=False, n_iter_max=50, tol=None):
     return A, [B[:j] for j in J], C, np.array(errors)
 
 
-def cp_problem(I, J_range, K, rank, seed, noise=0.01):
+def cp_problem(I, J_range, K, rank, seed, noise=0.01, J=None):
     """X_i = X~_i[:J_i] for a padded tensor X~ = CP(A, B, C) + `noise` relative Gaussian noise on the stored rows, rounded to float32.
     Component q has B[:, q] supported on the rows below L_q and a_i[q] = 0 for the slabs shorter than L_q, so the zero padding
     is part of the low-rank model; sparse non-negative factors with decaying weights: a clear gap behind the rank-th eigenvalue
-    of both Gram matrices of the start and well-conditioned normal equations."""
+    of both Gram matrices of the start and well-conditioned normal equations.  `J`: explicit row counts (J_range unused; a 0 is
+    an empty matrix)."""
     rng = np.random.RandomState(seed)
-    J = rng.randint(J_range[0], J_range[1] + 1, size=I)
-    Js = np.sort(J)
+    J = rng.randint(J_range[0], J_range[1] + 1, size=I) if J is None else np.asarray(J, dtype=np.int64)
+    Js = np.sort(J[J > 0])  # (an empty matrix carries no component)
     L = Js[(np.arange(rank) * I) // (2 * rank)]  # every component is active on at least half of the slabs
     w = np.linspace(1.0, 0.5, rank)
     A = rng.uniform(0.5, 1.0, size=(I, rank)) * w * (J[:, None] >= L[None, :])
@@ -94,5 +95,5 @@ def cp_problem(I, J_range, K, rank, seed, noise=0.01):
     for i in range(I):
         M = (B[: J[i]] * A[i]) @ C.T
         E = rng.standard_normal(M.shape)
-        mats.append((M + noise * np.linalg.norm(M) / np.linalg.norm(E) * E).astype(np.float32))
+        mats.append((M + noise * np.linalg.norm(M) / max(np.linalg.norm(E), 1e-300) * E).astype(np.float32))
     return mats

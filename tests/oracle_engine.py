@@ -173,7 +173,7 @@ class OracleEngine:
         B, C, rp = self._n(self.B), self._n(self.C), self.row_ptr
         CtC = C.T @ C
         XC = self.Xn @ C
-        self.rhs_A = np.add.reduceat(B * XC, rp[:-1], axis=0) if self.I else np.zeros((0, self.r))
+        self.rhs_A = orc.segment_sums(B * XC, rp) if self.I else np.zeros((0, self.r))
         self.Q = np.stack([(B[rp[i]: rp[i + 1]].T @ B[rp[i]: rp[i + 1]]) * CtC for i in range(self.I)]) \
             if self.I else np.zeros((0, self.r, self.r))
         self.rho_A = 0.5 * np.trace(self.Q, axis1=1, axis2=2) * self.scale if self.I else np.zeros(0)

@@ -65,11 +65,11 @@ def parafac2_als(matrices, rank, n_iter_max=2000, init="random", tol=1e-8, absol
     return A, B, C, P, np.array(errors), np.array(e2s)
 
 
-def parafac2_problem(I, J_range, K, rank, seed, noise=0.1, nonneg=False):
+def parafac2_problem(I, J_range, K, rank, seed, noise=0.1, nonneg=False, J=None):
     """X_i = P_i B diag(a_i) C^T + `noise` relative Gaussian noise, rounded to float32; P_i random orthonormal, A, C positive (or
-    sparse non-negative with nonneg), B well conditioned.  -> (mats, (A, B, C, [P_i]))"""
+    sparse non-negative with nonneg), B well conditioned.  `J`: explicit row counts (J_range unused).  -> (mats, (A, B, C, [P_i]))"""
     rng = np.random.RandomState(seed)
-    J = rng.randint(J_range[0], J_range[1] + 1, size=I)
+    J = rng.randint(J_range[0], J_range[1] + 1, size=I) if J is None else np.asarray(J, dtype=np.int64)
     A = rng.uniform(0.5, 1.5, size=(I, rank))
     B = np.eye(rank) + 0.3 * rng.uniform(size=(rank, rank))
     C = rng.uniform(0.0, 1.0, size=(K, rank))

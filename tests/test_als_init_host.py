@@ -56,3 +56,23 @@ def test_solver_refuses_cp_starts_under_group(init):
 def test_parafac2_als_still_raises():
     with pytest.raises(NotImplementedError, match="parafac2_als"):
         dec.initialize_cmf(_mats([(5, 10), (8, 10)]), 2, "parafac2_als", None)
+
+
+# ---- the fixtures of the GPU rank-bucket / load-path / ragged tests are well posed (tests/kernel_edge_cases.py) -------------------
+from tests import als_restatement as R  # noqa: E402
+from tests import kernel_edge_cases as E  # noqa: E402
+
+
+@pytest.mark.parametrize("name", sorted(E.ALS_CASES))
+def test_edge_fixture_is_well_posed(name, monkeypatch):
+    mats, rank = E.als_problem(name)
+    K, J_max = mats[0].shape[1], max(m.shape[0] for m in mats)
+    assert rank <= min(K, J_max)
+    for G in E.als_start_grams(mats):
+        gap, tail = E.gram_gaps(G, rank)
+        assert gap >= E.GAP_MIN and tail <= E.TAIL_RATIO_MAX, (name, gap, tail)
+    rec = E.StepRecorder(monkeypatch, R)
+    R.cp_init(mats, rank, hals=False, n_iter_max=3, tol=0)
+    assert rec.cholesky_failed == 0 and max(rec.kappa) < E.KAPPA_MAX, (name, rec.cholesky_failed, max(rec.kappa))
+    A, B, C, _ = R.cp_init(mats, rank, hals=True, n_iter_max=3, tol=0)
+    assert np.isfinite(A).all() and np.isfinite(C).all() and all(np.isfinite(b).all() for b in B)

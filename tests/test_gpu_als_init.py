@@ -189,3 +189,85 @@ def test_rate_guard_config3(hals):
     print(f"config-3 shape, {'HALS' if hals else 'ALS'}: {t * 1e6:.1f} us per sweep, two reads of X at "
           f"{2 * read_s / t:.2f} of the streaming-read rate ({read_s * 1e6:.1f} us per read)")
     assert t <= 4.5 * read_s + 60e-6, (t, read_s)
+
+
+# ---- rank buckets, load paths and ragged edges (fixtures: tests/kernel_edge_cases.py, checked on the CPU by
+# tests/test_als_init_host.py) -----------------------------------------------------------------------------------------------------
+from tests import kernel_edge_cases as E  # noqa: E402
+
+
+def _three_sweep_parity(name, hals, fac=1e-5):
+    mats, rank = E.als_problem(name)
+    packed = _packed(mats)
+    A, B, C, errors = _device_run(packed, rank, hals, 3, 0.0)
+    rA, rB, rC, rerr = R.cp_init(mats, rank, hals=hals, n_iter_max=3, tol=0)
+    assert len(errors) == 3
+    eA, eB, eC = _rel(A, rA), _rel(B, np.concatenate(rB)), _rel(C, rC)
+    assert max(eA, eB, eC) < fac, (name, eA, eB, eC)
+    assert np.abs(errors.cpu().numpy() - rerr).max() < 1e-7, (errors.cpu().numpy(), rerr)
+
+
+@pytest.mark.parametrize("hals", [False, True], ids=["als", "hals"])
+@pytest.mark.parametrize("name", ["r17", "r32_rank_is_K", "r33", "r64"])
+def test_rank_buckets(name, hals):
+    # als_nb: NB = 2 (ranks 17, 32) and NB = 4 (33, 64), a partial and a full last column block each; launch_update<32 / 64>.
+    # HALS at rank 64: 3.4e-5 measured in B / C (ALS: 2.1e-6).  The start agrees to 4e-8; HALS's clipping amplifies it where
+    # the start Gram matrices have close eigenvalues (gap 3.5e-6 here; at rank 32 a gap of 3.6e-6 gave 1.5e-5, 3.3e-5 gave
+    # 4.3e-6), and no rank-64 fixture found has a gap above 7.2e-6
+    _three_sweep_parity(name, hals, 5e-5 if hals and name == "r64" else 1e-5)
+
+
+@pytest.mark.parametrize("hals", [False, True], ids=["als", "hals"])
+@pytest.mark.parametrize("name", E.ALS_START_CASES)
+def test_start_alone(name, hals):
+    # n_iter_max = 0: the start (mcl_svd_stack_right + the row-Gram vectors) and k_als_out, one rank per NB bucket
+    mats, rank = E.als_problem(name)
+    A, B, C, errors = _device_run(_packed(mats), rank, hals, 0, 0.0)
+    rA, rB, rC = R.cp_start(mats, rank, hals)
+    assert len(errors) == 0
+    J = [m.shape[0] for m in mats]
+    rBp = np.concatenate([rB[:j] for j in J])
+    eA, eB, eC = _rel(A, rA), _rel(B, rBp), _rel(C, rC)
+    assert max(eA, eB, eC) < 2e-6, (name, eA, eB, eC)
+
+
+@pytest.mark.parametrize("hals", [False, True], ids=["als", "hals"])
+@pytest.mark.parametrize("name", ["k13", "k130"])
+def test_scalar_loads(name, hals):
+    # K % 4 != 0: the VEC = false loads of both passes (a K below one 64-column chunk, one just past two)
+    _three_sweep_parity(name, hals)
+
+
+@pytest.mark.parametrize("hals", [False, True], ids=["als", "hals"])
+def test_ragged_edges_and_an_empty_matrix(hals):
+    # J_i in {64, 65, 128, 129} (the ALS_SEG = 64 segment edges) and a 0-row matrix, through a PackedMatrices row_ptr
+    _three_sweep_parity("ragged", hals)
+
+
+def _offset_view(X, offset=1):
+    """X's values in a contiguous view at element `offset` inside a larger buffer (in bounds: the buffer holds offset + numel)"""
+    buf = torch.zeros(X.numel() + offset, dtype=X.dtype, device=X.device)
+    view = buf[offset: offset + X.numel()].view(X.shape)
+    view.copy_(X)
+    assert view.is_contiguous() and view.data_ptr() % 16 != 0
+    return view
+
+
+@pytest.mark.parametrize("dtype", ["float32", "bfloat16", "float16"])
+@pytest.mark.parametrize("name", ["r16", "r33"])
+def test_unaligned_base_is_bitwise_the_aligned_run(name, dtype):
+    # K % 4 == 0, X at element offset 1: the scalar loads (VEC = false) read the same values as the vector loads of the aligned
+    # run and feed the same products in the same order.  16-bit: the base is not 8-B aligned; the reference is the aligned
+    # float32 run of the upcast values
+    mats, rank = E.als_problem(name)
+    packed = _packed(mats, getattr(torch, dtype))
+    X32 = packed.X.float().contiguous()
+    Xu = _offset_view(packed.X)
+    from matcouply_amd import _engine
+
+    for hals in (False, True):
+        method = _engine.ALS_CP_HALS if hals else _engine.ALS_CP
+        ref = _engine.als_init(X32, packed.row_ptr, rank, method, 3, 0.0)
+        got = _engine.als_init(Xu, packed.row_ptr, rank, method, 3, 0.0)
+        torch.cuda.synchronize()
+        assert all(torch.equal(x, y) for x, y in zip(got, ref)), (name, dtype, hals)

@@ -252,3 +252,93 @@ def test_no_scratch_in_the_fused_kernel():
     assert len(ms) == 48, [k["kernel"] for k in ms]  # ranks 1..16 x {fp32, bf16, fp16}
     spilled = [(k["kernel"], k["scratch_bytes"], k["vgpr_spill"]) for k in ms if k["scratch_bytes"] or k["vgpr_spill"]]
     assert not spilled, spilled
+
+
+# ---- every instantiation, batches and strides (fixtures: tests/kernel_edge_cases.py, checked on the CPU by
+# tests/test_multistart_host.py) -------------------------------------------------------------------------------------------------
+from tests import kernel_edge_cases as E  # noqa: E402
+
+
+def _per_start_parity(case, stack, n_starts, n_iter=20, gap_bar=1e-5):
+    c = E.MS_CASES[case]
+    mats, X, row_ptr = E.ms_problem(c["I"], c["J_range"], c["K"], c["r"], c["seed"])
+    rank = c["r"]
+    kw = dict(STACKS[stack], n_iter_max=n_iter, tol=None, return_errors=True)
+    got = dec.cmf_aoadmm_multistart(mats, rank, range(n_starts), method="fused", **kw)
+    assert len(got) == n_starts
+    for s, (cmf, diag) in enumerate(got):
+        st = _oracle_state(mats, X, row_ptr, rank, s, kw)
+        res = orc.run(st, n_iter, tol=None, absolute_tol=None)
+        _, (A, B_is, C) = cmf
+        rel = lambda a, b: np.linalg.norm(np.asarray(a) - b) / max(np.linalg.norm(b), 1e-300)
+        errs = [rel(A, st.A), rel(np.concatenate(B_is), st.B), rel(C, st.C),
+                np.max(np.abs(np.array(diag.rec_errors) - res["rec_errors"]) / np.array(res["rec_errors"])),
+                np.max(np.abs(np.array(diag.regularized_loss) - res["losses"]) / np.array(res["losses"]))]
+        gaps, worst = [0.0], None
+        for g_got, g_ref in zip(diag.feasibility_gaps, res["gaps"]):
+            for m in range(3):
+                if len(g_ref[m]):
+                    d = np.abs(np.array(g_got[m]) - g_ref[m]) / np.maximum(np.abs(g_ref[m]), 1e-3)
+                    if d.max() > max(gaps):
+                        worst = (m, np.array(g_got[m])[d.argmax()], np.asarray(g_ref[m])[d.argmax()])
+                    gaps.append(d.max())
+        assert diag.n_iter == n_iter
+        assert max(errs) < 1e-5, (case, stack, s, errs)
+        assert max(gaps) < gap_bar, (case, stack, s, max(gaps), "mode, device gap, oracle gap:", worst)
+
+
+@pytest.mark.parametrize("stack", ["parafac2_nn", "ridge_constant"])
+@pytest.mark.parametrize("rank", E.MS_RANKS)
+def test_oracle_parity_every_rank(rank, stack):
+    # k_multistart<R, float> for every R = 1..16: the Jacobi polar factor (parafac2_nn) and the Cholesky inverses of the A / B_i
+    # systems (ridge_constant).  PARAFAC2 at rank 16: 3.7e-5 measured in one feasibility gap while the factors agree to 5e-8.
+    # The gaps there are 1e-6 .. 2e-4, below the comparison's 1e-3 floor, and a gap ||F - Z|| / ||F|| carries the factors'
+    # relative difference as an absolute error: 5e-8 / 1e-3 = 5e-5
+    _per_start_parity(f"r{rank}", stack, 2, gap_bar=6e-5 if rank == 16 and stack == "parafac2_nn" else 1e-5)
+
+
+@pytest.mark.parametrize("case,stack", [("batches_r16", "parafac2_nn"), ("batches_r16", "ridge_constant"),
+                                        ("rows_reduce_r12", "nn_l1C"), ("strides_r3", "parafac2_nn"),
+                                        ("strides_r3", "box_l2ball")])
+def test_oracle_parity_batches_and_strides(case, stack):
+    # invert_systems in 4 batches of 10 (rank 16, I = 40); rows_reduce's one-thread-per-entry form (R * R > 128); I = 300 > 256
+    _per_start_parity(case, stack, 2)
+
+
+def test_oracle_parity_near_the_size_bound():
+    c = E.MS_CASES["near_bound_r16"]
+    assert sum(c["J_range"]) / 2 * c["I"] * c["K"] > 0.9 * dec._MULTISTART_MAX_ELEMENTS
+    _per_start_parity("near_bound_r16", "ridge_constant", 2, n_iter=5)
+
+
+@pytest.mark.parametrize("stack", ["ridge_constant", "box_l2ball"])
+def test_oracle_parity_with_an_empty_matrix(stack):
+    # a 0-row X_i with stacks whose A row / B_i systems stay regular (l2_penalty, or constant feasibility penalties); the
+    # singular ones are refused before the device is touched (tests/test_multistart_host.py)
+    _per_start_parity("empty_r3", stack, 3)
+
+
+def test_rank16_start_alone_equals_start_in_a_batch():
+    c = E.MS_CASES["r16"]
+    mats, _, _ = E.ms_problem(c["I"], c["J_range"], c["K"], c["r"], c["seed"])
+    kw = dict(parafac2=True, non_negative=True, n_iter_max=100, return_errors=True, return_admm_vars=True)
+    batch = dec.cmf_aoadmm_multistart(mats, 16, range(64), method="fused", **kw)
+    for s in (0, 37, 63):
+        alone = dec.cmf_aoadmm_multistart(mats, 16, [s], method="fused", **kw)[0]
+        assert _bits(alone) == _bits(batch[s])
+
+
+@pytest.mark.parametrize("dtype", ["bfloat16", "float16"])
+def test_rank16_x16_equals_upcast(dtype):
+    c = E.MS_CASES["r16"]
+    mats, _, _ = E.ms_problem(c["I"], c["J_range"], c["K"], c["r"], c["seed"])
+    m16 = [torch.tensor(m, dtype=getattr(torch, dtype), device="cuda") for m in mats]
+    m32 = [m.float() for m in m16]
+    kw = dict(non_negative=True, l1_penalty={2: 0.05}, n_iter_max=30, return_errors=True, return_admm_vars=True)
+    a = dec.cmf_aoadmm_multistart(m16, 16, range(3), method="fused", **kw)
+    b = dec.cmf_aoadmm_multistart(m32, 16, range(3), method="fused", **kw)
+    for (ca, _, da), (cb, _, db) in zip(a, b):
+        assert da.regularized_loss == db.regularized_loss and da.rec_errors == db.rec_errors
+        assert da.feasibility_gaps == db.feasibility_gaps
+        for x, y in zip([ca[1][0], *ca[1][1], ca[1][2]], [cb[1][0], *cb[1][1], cb[1][2]]):
+            assert x.dtype == getattr(torch, dtype) and torch.equal(x, y.to(x.dtype))

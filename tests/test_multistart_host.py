@@ -121,3 +121,44 @@ def test_bad_method_and_random_state(no_device):
         dec.cmf_aoadmm_multistart(_mats(), 2, range(2), random_state=0)
     with pytest.raises(TypeError):
         dec.cmf_aoadmm_multistart(_mats(), 2, range(2), method="fused", no_such_option=1)
+
+
+# ---- the fixtures of the GPU every-rank / batch / stride tests are served by the fused kernel (tests/kernel_edge_cases.py) --------
+from tests import kernel_edge_cases as E  # noqa: E402
+
+@pytest.mark.parametrize("name", sorted(E.MS_RUNS))
+def test_edge_fixture_is_served_fused(no_device, name):
+    from tests.test_gpu_multistart import STACKS
+
+    c = E.MS_CASES[name]
+    mats, X, row_ptr = E.ms_problem(c["I"], c["J_range"], c["K"], c["r"], c["seed"])
+    assert X.size <= dec._MULTISTART_MAX_ELEMENTS
+    for stack in E.MS_RUNS[name]:
+        reason = dec._multistart_unfused_reason(mats, c["r"], dec._cmf_kwargs(dict(STACKS[stack], n_iter_max=20, tol=None)))
+        assert reason is None, (name, stack, reason)
+
+
+@pytest.mark.parametrize("kwargs, match", [
+    (dict(non_negative={0: True, 1: True}, l1_penalty={2: 0.05}), "mode-0 system singular"),  # rho_i = 0, no l2
+    (dict(l2_penalty=[0.1, 0.0, 0.0], non_negative={1: True}), "mode-1 system singular"),
+    (dict(l2_penalty=[0.1, 0.1, 0.0], parafac2=True), "J_i >= rank"),
+])
+def test_fused_refuses_an_empty_matrix_with_a_singular_system(no_device, kwargs, match):
+    mats = _mats(((6, 8), (0, 8), (7, 8)))
+    with pytest.raises(NotImplementedError, match=match):
+        dec.cmf_aoadmm_multistart(mats, 2, range(2), method="fused", n_iter_max=2, **kwargs)
+
+
+def test_oracle_sums_an_empty_slab_to_zero():
+    # np.add.reduceat alone returns the next slab's first row for an empty segment: the oracle's A right-hand side gave the
+    # empty slab a non-zero A row and a wrong by-product error (0 instead of the full error)
+    from oracle import aoadmm_oracle as orc
+
+    V = np.arange(12.0).reshape(6, 2)
+    np.testing.assert_array_equal(orc.segment_sums(V, [0, 2, 2, 5, 6, 6]), [[2, 4], [0, 0], [18, 21], [10, 11], [0, 0]])
+    c = E.MS_CASES["empty_r3"]
+    _, X, row_ptr = E.ms_problem(c["I"], c["J_range"], c["K"], c["r"], c["seed"])
+    st = orc.random_state_for(X.astype(np.float64), row_ptr, 3, [[], [], []], l2=[0.1, 0.2, 0.05])
+    orc.run(st, 3, tol=None, absolute_tol=None)
+    assert np.all(st.A[1] == 0.0)
+    assert abs(st.rec_error_from_A_byproducts() - st.rec_error_full()) < 1e-12

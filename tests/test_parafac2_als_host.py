@@ -67,3 +67,18 @@ def test_restatement_recovers_a_planted_model(init):
     assert R.factor_match((A, B, C, P), true) > 0.95
     assert errors[-1] < 0.1
     assert np.all(np.diff(errors) <= 1e-12)
+
+
+# ---- the fixtures of the GPU RMAX = 32 / load-path / boundary tests are well posed (tests/kernel_edge_cases.py) -------------------
+from tests import kernel_edge_cases as E  # noqa: E402
+
+
+@pytest.mark.parametrize("name", sorted(E.PF2_CASES))
+def test_edge_fixture_is_well_posed(name, monkeypatch):
+    mats, rank = E.pf2_problem(name)
+    assert min(m.shape[0] for m in mats) >= rank and mats[0].shape[1] >= rank
+    gap, tail = E.gram_gaps(sum(m.T.astype(np.float64) @ m for m in mats), rank)  # the stack Gram of init="svd"
+    assert gap >= E.GAP_MIN and tail <= E.TAIL_RATIO_MAX, (name, gap, tail)
+    rec = E.StepRecorder(monkeypatch, R)
+    R.parafac2_als(mats, rank, n_iter_max=3, tol=1e-300, absolute_tol=0, init="svd")
+    assert rec.cholesky_failed == 0 and max(rec.kappa) < E.KAPPA_MAX, (name, rec.cholesky_failed, max(rec.kappa))
