@@ -352,6 +352,24 @@ int mcl_multistart_run(const void *X, int32_t x_type, const int64_t *row_ptr, in
                        void *workspace, int64_t workspace_bytes, void *hip_stream);
 const char *mcl_multistart_last_error(void);
 
+/* ---- many random starts of parafac2_als at once (parafac2_als_multistart, csrc/pf2als_multistart.hip) ---------------------- */
+/* One workgroup per start runs the whole unconstrained PARAFAC2-ALS fit of mcl_parafac2_als_typed (projections from the polar
+ * factor of X_i C diag(a_i) B^T, n_iter_parafac CP sweeps per iteration, ALS or one HALS column pass for the modes in nn_modes:
+ * bit 0 A, bit 2 C) in fp64 with workgroup barriers only; X is shared and read-only.  Stateless; X, factors, P, errors, n_iter,
+ * workspace: device pointers; row_ptr: HOST int64[I+1].
+ * factors: fp64 [n_starts, (I + rank + K) * rank], in/out: start s's A [I, rank], B [rank, rank], C [K, rank], row-major, no
+ * padding.  P: fp64 [n_starts, N, rank], the projections packed like X (from the last iteration).  errors: fp64
+ * [n_starts, n_iter_max] (may be NULL when tol = 0): tol > 0: errors[s][t] = the relative reconstruction error after iteration t,
+ * and a start stops after t >= 1 when |e_{t-1}^2 - e_t^2| <= tol e_{t-1}^2 or e_t^2 < absolute_tol.  n_iter: int32[n_starts],
+ * the iterations a start ran.  Needs 1 <= rank <= 16 and rank <= min(J_i, K).  Every reduction has a fixed order; a start's
+ * result does not depend on n_starts or its neighbours. */
+int64_t mcl_pf2als_multistart_workspace_bytes(const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank, int32_t n_starts);
+int mcl_pf2als_multistart_run(const void *X, int32_t x_type, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank, int32_t n_starts,
+                              int32_t n_iter_max, int32_t n_iter_parafac, double tol, double absolute_tol, int32_t nn_modes,
+                              double *factors, double *P, double *errors, int32_t *n_iter, void *workspace, int64_t workspace_bytes,
+                              void *hip_stream);
+const char *mcl_pf2als_multistart_last_error(void);
+
 /* ---- introspection for tests / profiling ------------------------------------------------------------- */
 /* device pointers to internal by-products / planner tables (the int32 tables: read the bits) */
 enum mcl_buffer_id {

@@ -62,6 +62,7 @@ EXPORTED_SYMBOLS = [
     "mcl_als_init_workspace_bytes", "mcl_als_init_typed", "mcl_als_init_last_error",
     "mcl_multistart_workspace_bytes", "mcl_multistart_run", "mcl_multistart_last_error",
     "mcl_parafac2_als_workspace_bytes", "mcl_parafac2_als_typed", "mcl_parafac2_als_last_error",
+    "mcl_pf2als_multistart_workspace_bytes", "mcl_pf2als_multistart_run", "mcl_pf2als_multistart_last_error",
 ]
 
 
@@ -193,6 +194,10 @@ def load_library():
         "mcl_parafac2_als_typed": (ctypes.c_int, [P, I32, ctypes.POINTER(I64), I64, I64, I32, P, P, P, I32, I32, ctypes.c_double,
                                                   ctypes.c_double, I32, P, P, P, P, P, P, P, I64, P]),
         "mcl_parafac2_als_last_error": (ctypes.c_char_p, []),
+        "mcl_pf2als_multistart_workspace_bytes": (I64, [ctypes.POINTER(I64), I64, I64, I32, I32]),
+        "mcl_pf2als_multistart_run": (ctypes.c_int, [P, I32, ctypes.POINTER(I64), I64, I64, I32, I32, I32, I32, ctypes.c_double,
+                                                     ctypes.c_double, I32, P, P, P, P, P, I64, P]),
+        "mcl_pf2als_multistart_last_error": (ctypes.c_char_p, []),
         "mcl_read_bandwidth": (ctypes.c_int, [P, I64, I32, P, P, ctypes.POINTER(ctypes.c_double)]),
     }
     for name, (res, args) in sig.items():
@@ -363,6 +368,63 @@ def parafac2_als(X, row_ptr, rank, start, n_iter_max, n_iter_parafac, tol, absol
         raise EngineError(lib.mcl_parafac2_als_last_error().decode())
     used = int(info.item())
     return A, B, C, P, errors[: used if tol > 0 else 0]
+
+
+PF2ALS_MS_MAX_RANK = 16
+
+
+def pf2als_multistart_scratch_len(I, N, K, rank):
+    """doubles of one start's scratch slice in mcl_pf2als_multistart_run (csrc/pf2als_multistart.hip, pm_scratch): W [N, r],
+    Y [I, r, K], T / WtW / V [I, r, r], M_A [I, r], M_C [K, r], each rounded up to 32 doubles"""
+    r = int(rank)
+    return sum((n + 31) // 32 * 32 for n in (N * r, I * r * K, I * r * r, I * r * r, I * r * r, I * r, K * r))
+
+
+def pf2als_multistart_workspace_bytes(I, N, K, rank, n_starts):
+    """mcl_pf2als_multistart_workspace_bytes restated: row_ptr (int64 [I + 1]), the row -> slab map (int32 [N]) and n_starts
+    scratch slices, each part rounded up to 256 bytes"""
+    al = lambda b: (b + 255) // 256 * 256
+    return al((I + 1) * 8) + al(N * 4) + al(pf2als_multistart_scratch_len(I, N, K, rank) * 8 * n_starts)
+
+
+def pf2als_multistart_run(X, row_ptr, rank, factors, n_iter_max, n_iter_parafac, tol, absolute_tol, nn_modes):
+    """Fit factors.shape[0] starts of one parafac2_als problem at once (mcl_pf2als_multistart_run), one workgroup per start.
+    X packed [sum J_i, K] float32 / bfloat16 / float16 CUDA tensor; factors float64 [n_starts, (I + rank + K) * rank] CUDA
+    tensor (A, B, C of every start), updated in place; nn_modes: modes (0 / 2) fitted non-negative.  -> (P float64
+    [n_starts, sum J_i, rank] (the projections), errors float64 [n_starts, n_iter_max] (rows valid up to n_iter when tol > 0),
+    n_iter int32 [n_starts]) on the device."""
+    import torch
+
+    lib = load_library()
+    xt = x_type_of(X.dtype)
+    if not (X.is_cuda and X.is_contiguous()):
+        raise EngineError("X must be a contiguous CUDA tensor")
+    row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int64)
+    I, K, N, r = len(row_ptr) - 1, int(X.shape[1]), int(X.shape[0]), int(rank)
+    if not (factors.is_cuda and factors.dtype == torch.float64 and factors.is_contiguous() and factors.dim() == 2
+            and factors.shape[1] == (I + r + K) * r):
+        raise EngineError("factors must be a contiguous float64 CUDA tensor [n_starts, (I + rank + K) * rank]")
+    S = int(factors.shape[0])
+    rp = row_ptr.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+    nbytes = lib.mcl_pf2als_multistart_workspace_bytes(rp, I, K, r, S)
+    if nbytes < 0:
+        lib.mcl_pf2als_multistart_run(None, xt, rp, I, K, r, S, 1, 1, 0.0, 0.0, 0, None, None, None, None, None, 0, None)
+        raise EngineError(lib.mcl_pf2als_multistart_last_error().decode())
+    dev = X.device
+    ws = torch.empty(int(nbytes) + 256, dtype=torch.uint8, device=dev)
+    off = (-ws.data_ptr()) % 256
+    P = torch.empty((S, N, r), dtype=torch.float64, device=dev)
+    errors = torch.zeros((S, max(int(n_iter_max), 1)), dtype=torch.float64, device=dev)
+    n_iter = torch.zeros(S, dtype=torch.int32, device=dev)
+    mask = sum(1 << int(m) for m in (nn_modes or ()))
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = lib.mcl_pf2als_multistart_run(X.data_ptr(), xt, rp, I, K, r, S, int(n_iter_max), int(n_iter_parafac), float(tol),
+                                           float(absolute_tol), int(mask), factors.data_ptr(), P.data_ptr(), errors.data_ptr(),
+                                           n_iter.data_ptr(), ws.data_ptr() + off, nbytes, ctypes.c_void_p(stream))
+    if rc != 0:
+        raise EngineError(lib.mcl_pf2als_multistart_last_error().decode())
+    return P, errors, n_iter
 
 
 def multistart_state_len(I, N, K, rank, kinds):

@@ -1,0 +1,469 @@
+// parafac2_als_multistart (decomposition.py): many random starts of ONE unconstrained PARAFAC2-ALS problem fitted at once, one
+// workgroup per start (the layout of csrc/multistart.hip).
+//
+// At the sizes PARAFAC2 users fit from many starts (about 100 matrices of ~100 x 20, rank 2-4) one parafac2_als call is
+// launch-bound and keeps a few CUs busy.  Here a start lives in ONE workgroup (256 threads): every outer iteration, its CP sweeps
+// and the stopping rule run inside one launch with nothing but workgroup barriers; blockIdx.x is the start.
+//
+// One outer iteration, as tests/parafac2_als_restatement.py states it:
+//   W_i = X_i C, WtW_i = W_i^T W_i, G_i = B D_i WtW_i D_i B^T, T_i = D_i B^T G_i^-1/2 (eigenvalues <= 1e-12 lam_max dropped),
+//   Y_i = T_i^T (W_i^T X_i) [r, K], then n_iter_parafac CP sweeps on Y over the modes A, B, C: ALS (Cholesky; the pseudo-inverse
+//   from a Jacobi eigen-decomposition when the Cholesky fails) or one Gauss-Seidel HALS column pass for the modes in nn_modes.
+//   With tol > 0: e^2 = (|X|^2 - 2 <M_C, C> + sum_i sum((D_i B^T P_i^T P_i B D_i) o C^T C)) / |X|^2, P_i^T P_i = T_i^T WtW_i T_i
+//   (no third read of X); stop after t >= 1 when |e_{t-1}^2 - e_t^2| <= tol e_{t-1}^2 or e_t^2 < absolute_tol.
+// The projections P_i = W_i T_i are written once, from the last iteration's W and T.
+//
+// Numerics: fp64 throughout; X is read in its stored type and converted exactly (xload.h).  No atomics; every sum runs in a
+// fixed order that depends only on the problem's shape (wg_fp64.h), so a start's result is bitwise independent of how many
+// starts share the launch and of which.
+//
+// Memory: X, row_ptr and the row -> slab map are shared.  Each start owns its factors (the caller's fp64 [I + r + K, r]), its
+// projections and errors, and a slice of the fp64 scratch workspace: W [N, r], Y [I, r, K], T / WtW / V [I, r, r], M_A [I, r],
+// M_C [K, r].  The r x r matrices of the sweeps (B, the Grams, M_B) live in LDS.
+#include <algorithm>
+#include <cmath>
+#include <string>
+#include <vector>
+
+#include "mcl_internal.h"
+#include "wg_fp64.h"
+#include "xload.h"
+
+namespace {
+
+static std::string g_pm_error;
+constexpr int PM_MAX_RANK = 16;
+constexpr int PM_SYS_BYTES = 40960;  // LDS for a batch of per-slab r x r polar steps (two r x r matrices per thread)
+constexpr double PM_DROP = 1e-12;    // eigenvalues at or below PM_DROP lam_max are dropped (polar factor, pseudo-inverse)
+
+struct PmArgs {
+    const void *X;
+    const int64_t *row_ptr;
+    const int32_t *slab_of_row;
+    int64_t I, N, K;
+    int64_t scratch_len;
+    double *factors, *P, *errors, *scratch;
+    int32_t *n_iter;
+    int32_t n_iter_max, n_iter_parafac, nn_modes;
+    double tol, absolute_tol;
+};
+
+// scratch of one start, in doubles (decomposition.py / _engine.pf2als_multistart_scratch_len restate it)
+struct PmScratch {
+    int64_t W, Y, T, WtW, V, MA, MC, total;
+};
+
+static __host__ __device__ inline PmScratch pm_scratch(int64_t I, int64_t N, int64_t K, int r) {
+    PmScratch s{};
+    int64_t o = 0;
+    auto take = [&](int64_t n) { const int64_t at = o; o += (n + 31) & ~int64_t(31); return at; };
+    s.W = take(N * r);
+    s.Y = take(I * r * K);
+    s.T = take(I * r * r);
+    s.WtW = take(I * r * r);
+    s.V = take(I * r * r);
+    s.MA = take(I * r);
+    s.MC = take(K * r);
+    s.total = o;
+    return s;
+}
+
+template <int R, class XL>
+struct Pf2Start {
+    static constexpr int RR = R * R;
+    const typename XL::T *X;
+    const int64_t *rp;
+    const int32_t *slab;
+    int64_t I, N, K;
+    double *A, *B, *C;                   // the start's factors (global, in/out)
+    double *W, *Y, *T, *WtW, *V, *MA, *MC;  // scratch (global)
+    double *red, *sys, *Bs, *BtB, *CtC, *AtA, *MB;  // LDS
+    int nb;                              // polar steps per batch
+
+    __device__ __forceinline__ double x(int64_t j, int64_t c) const { return (double)XL::ld1(X + j * K + c); }
+
+    // out (LDS, R x R) = F^T F for a factor of n rows
+    __device__ __forceinline__ void gram(const double *F, int64_t n, double *out) {
+        rows_reduce(RR, n, out, red, [&](int64_t j, int e) { return F[j * R + e / R] * F[j * R + e % R]; });
+    }
+
+    // G (LDS) = G1 o G2; then, for ALS, G <- G^-1: Cholesky, or the pseudo-inverse (Jacobi, eigenvalues <= 1e-12 lam_max dropped,
+    // (G^+1/2)^2) when a pivot is not positive.  HALS keeps G.
+    __device__ __forceinline__ void system(const double *G1, const double *G2, bool hals) {
+        double *G = sys, *Wk = sys + RR, *Gsave = sys + 2 * RR;
+        if (threadIdx.x == 0) {
+            for (int e = 0; e < RR; ++e) G[e] = G1[e] * G2[e], Gsave[e] = G[e];
+            if (!hals && !spd_inverse<R>(G, Wk)) {
+                for (int e = 0; e < RR; ++e) G[e] = Gsave[e];
+                gram_inv_sqrt<R>(G, Wk, PM_DROP);
+                for (int p = 0; p < R; ++p)
+                    for (int q = 0; q < R; ++q) {
+                        double v = 0.0;
+                        for (int u = 0; u < R; ++u) v += G[p * R + u] * G[u * R + q];
+                        Gsave[p * R + q] = v;
+                    }
+                for (int e = 0; e < RR; ++e) G[e] = Gsave[e];
+            }
+        }
+        __syncthreads();
+    }
+
+    // rows of F (n x R) from their right-hand sides M with the system of system(): ALS F = M G^-1, HALS one column pass
+    __device__ __forceinline__ void update_rows(const double *M, double *F, int64_t n, bool hals) {
+        const double *G = sys;
+        for (int64_t i = threadIdx.x; i < n; i += MS_THREADS) {
+            if (hals) {
+                #pragma unroll 1
+                for (int q = 0; q < R; ++q) {
+                    const double gqq = G[q * R + q];
+                    if (gqq == 0.0) continue;
+                    double fg = 0.0;
+                    #pragma unroll
+                    for (int p = 0; p < R; ++p) fg += F[i * R + p] * G[p * R + q];
+                    F[i * R + q] = fmax(0.0, F[i * R + q] + (M[i * R + q] - fg) / gqq);
+                }
+            } else {
+                double m[R];
+                #pragma unroll
+                for (int q = 0; q < R; ++q) m[q] = M[i * R + q];
+                #pragma unroll 1
+                for (int l = 0; l < R; ++l) {
+                    double v = 0.0;
+                    #pragma unroll
+                    for (int q = 0; q < R; ++q) v += m[q] * G[q * R + l];
+                    F[i * R + l] = v;
+                }
+            }
+        }
+        __syncthreads();
+    }
+
+    // W = X C, WtW_i, then per slab T_i = D_i B^T G_i^-1/2 (one thread per slab, a batch at a time in LDS), then Y_i
+    __device__ __forceinline__ void project() {
+        const int t = threadIdx.x;
+        for (int64_t j = t; j < N; j += MS_THREADS) {
+            double acc[R];
+            #pragma unroll
+            for (int l = 0; l < R; ++l) acc[l] = 0.0;
+            for (int64_t c = 0; c < K; ++c) {
+                const double xv = x(j, c);
+                #pragma unroll
+                for (int l = 0; l < R; ++l) acc[l] += xv * C[c * R + l];
+            }
+            #pragma unroll
+            for (int l = 0; l < R; ++l) W[j * R + l] = acc[l];
+        }
+        __syncthreads();
+        for (int64_t e = t; e < I * RR; e += MS_THREADS) {
+            const int64_t i = e / RR;
+            const int p = (int)(e % RR) / R, q = (int)(e % RR) % R;
+            double s = 0.0;
+            for (int64_t j = rp[i]; j < rp[i + 1]; ++j) s += W[j * R + p] * W[j * R + q];
+            WtW[e] = s;
+        }
+        __syncthreads();
+        for (int64_t base = 0; base < I; base += nb) {
+            const int64_t i = base + t;
+            if (t < nb && i < I) {
+                double *S = sys + t * 2 * RR, *H = S + RR;
+                const double *a = A + i * R, *Wt = WtW + i * RR;
+                for (int p = 0; p < R; ++p)  // H = D WtW D B^T
+                    for (int y = 0; y < R; ++y) {
+                        double v = 0.0;
+                        for (int q = 0; q < R; ++q) v += a[p] * a[q] * Wt[p * R + q] * Bs[y * R + q];
+                        H[p * R + y] = v;
+                    }
+                for (int u = 0; u < R; ++u)  // G = B H
+                    for (int y = 0; y < R; ++y) {
+                        double v = 0.0;
+                        for (int p = 0; p < R; ++p) v += Bs[u * R + p] * H[p * R + y];
+                        S[u * R + y] = v;
+                    }
+                for (int u = 0; u < R; ++u)  // (G + G^T) / 2
+                    for (int y = u + 1; y < R; ++y) {
+                        const double v = 0.5 * (S[u * R + y] + S[y * R + u]);
+                        S[u * R + y] = v, S[y * R + u] = v;
+                    }
+                gram_inv_sqrt<R>(S, H, PM_DROP);
+                double *Ti = T + i * RR;
+                for (int p = 0; p < R; ++p)  // T = D B^T G^-1/2
+                    for (int q = 0; q < R; ++q) {
+                        double v = 0.0;
+                        for (int u = 0; u < R; ++u) v += Bs[u * R + p] * S[u * R + q];
+                        Ti[p * R + q] = a[p] * v;
+                    }
+            }
+        }
+        __syncthreads();
+        for (int64_t e = t; e < I * K; e += MS_THREADS) {  // Y_i[:, k] = T_i^T (W_i^T X_i[:, k])
+            const int64_t i = e / K, k = e % K;
+            double z[R];
+            #pragma unroll
+            for (int p = 0; p < R; ++p) z[p] = 0.0;
+            for (int64_t j = rp[i]; j < rp[i + 1]; ++j) {
+                const double xv = x(j, k);
+                #pragma unroll
+                for (int p = 0; p < R; ++p) z[p] += W[j * R + p] * xv;
+            }
+            const double *Ti = T + i * RR;
+            #pragma unroll 1
+            for (int q = 0; q < R; ++q) {
+                double v = 0.0;
+                #pragma unroll
+                for (int p = 0; p < R; ++p) v += Ti[p * R + q] * z[p];
+                Y[(i * R + q) * K + k] = v;
+            }
+        }
+        __syncthreads();
+    }
+
+    // one CP sweep on Y over the modes A, B, C; leaves M_C in MC
+    __device__ __forceinline__ void sweep(bool hals_a, bool hals_c) {
+        const int t = threadIdx.x;
+        gram(C, K, CtC);
+        if (t < RR) {
+            double v = 0.0;
+            for (int q = 0; q < R; ++q) v += Bs[q * R + t / R] * Bs[q * R + t % R];
+            BtB[t] = v;
+        }
+        for (int64_t e = t; e < I * RR; e += MS_THREADS) {  // V_i = Y_i C
+            const int64_t i = e / RR;
+            const int q = (int)(e % RR) / R, s = (int)(e % RR) % R;
+            const double *y = Y + (i * R + q) * K;
+            double v = 0.0;
+            for (int64_t k = 0; k < K; ++k) v += y[k] * C[k * R + s];
+            V[e] = v;
+        }
+        __syncthreads();
+        for (int64_t e = t; e < I * R; e += MS_THREADS) {  // M_A[i][s] = sum_q B[q][s] V_i[q][s]
+            const int64_t i = e / R;
+            const int s = (int)(e % R);
+            double v = 0.0;
+            for (int q = 0; q < R; ++q) v += Bs[q * R + s] * V[i * RR + q * R + s];
+            MA[e] = v;
+        }
+        system(BtB, CtC, hals_a);
+        update_rows(MA, A, I, hals_a);
+        gram(A, I, AtA);
+        rows_reduce(RR, I, MB, red, [&](int64_t i, int e) { return V[i * RR + e] * A[i * R + e % R]; });  // M_B = sum_i V_i D_i
+        system(AtA, CtC, false);
+        update_rows(MB, B, R, false);
+        if (t < RR) Bs[t] = B[t];
+        __syncthreads();
+        if (t < RR) {
+            double v = 0.0;
+            for (int q = 0; q < R; ++q) v += Bs[q * R + t / R] * Bs[q * R + t % R];
+            BtB[t] = v;
+        }
+        // M_C[k][s] = sum_i a_i[s] sum_q Y_i[q][k] B[q][s]
+        rows_reduce((int)(K * R), I, MC, red, [&](int64_t i, int e) {
+            const int64_t k = e / R;
+            const int s = e % R;
+            double v = 0.0;
+            for (int q = 0; q < R; ++q) v += Y[(i * R + q) * K + k] * Bs[q * R + s];
+            return v * A[i * R + s];
+        });
+        system(AtA, BtB, hals_c);
+        update_rows(MC, C, K, hals_c);
+    }
+
+    // e^2 after the sweeps (every thread gets it): |X|^2 - 2 <M_C, C> + sum_i a_i^T ((B^T P_i^T P_i B) o C^T C) a_i, over |X|^2.
+    // Uses V and WtW as scratch (P_i^T P_i overwrites WtW_i).
+    __device__ __forceinline__ double error_sq(double x_sq) {
+        const int t = threadIdx.x;
+        double cr = 0.0;
+        for (int64_t e = t; e < K * R; e += MS_THREADS) cr += MC[e] * C[e];
+        const double cross = wg_sum(cr, red);
+        gram(C, K, CtC);
+        for (int64_t e = t; e < I * RR; e += MS_THREADS) {  // V_i = WtW_i T_i
+            const int64_t i = e / RR;
+            const int p = (int)(e % RR) / R, y = (int)(e % RR) % R;
+            double v = 0.0;
+            for (int u = 0; u < R; ++u) v += WtW[i * RR + p * R + u] * T[i * RR + u * R + y];
+            V[e] = v;
+        }
+        __syncthreads();
+        for (int64_t e = t; e < I * RR; e += MS_THREADS) {  // P_i^T P_i = T_i^T V_i (into WtW)
+            const int64_t i = e / RR;
+            const int x0 = (int)(e % RR) / R, y = (int)(e % RR) % R;
+            double v = 0.0;
+            for (int p = 0; p < R; ++p) v += T[i * RR + p * R + x0] * V[i * RR + p * R + y];
+            WtW[e] = v;
+        }
+        __syncthreads();
+        for (int64_t e = t; e < I * RR; e += MS_THREADS) {  // V_i = P_i^T P_i B
+            const int64_t i = e / RR;
+            const int p = (int)(e % RR) / R, s = (int)(e % RR) % R;
+            double v = 0.0;
+            for (int u = 0; u < R; ++u) v += WtW[i * RR + p * R + u] * Bs[u * R + s];
+            V[e] = v;
+        }
+        __syncthreads();
+        double f = 0.0;
+        for (int64_t e = t; e < I * RR; e += MS_THREADS) {
+            const int64_t i = e / RR;
+            const int x0 = (int)(e % RR) / R, s = (int)(e % RR) % R;
+            double v = 0.0;
+            for (int p = 0; p < R; ++p) v += Bs[p * R + x0] * V[i * RR + p * R + s];
+            f += A[i * R + x0] * A[i * R + s] * v * CtC[x0 * R + s];
+        }
+        const double fit = wg_sum(f, red);
+        return x_sq > 0.0 ? fmax(0.0, x_sq - 2.0 * cross + fit) / x_sq : 0.0;
+    }
+};
+
+template <int R, class XL>
+__global__ __launch_bounds__(MS_THREADS) void k_ms_pf2als(PmArgs a) {
+    constexpr int RR = R * R;
+    __shared__ double red[MS_THREADS];
+    __shared__ double sys[PM_SYS_BYTES / 8];
+    __shared__ double small[5 * RR];
+    const int64_t s = blockIdx.x;
+    const int t = threadIdx.x;
+    Pf2Start<R, XL> st{static_cast<const typename XL::T *>(a.X), a.row_ptr, a.slab_of_row, a.I, a.N, a.K};
+    st.A = a.factors + s * (a.I + R + a.K) * R;
+    st.B = st.A + a.I * R;
+    st.C = st.B + RR;
+    double *ws = a.scratch + s * a.scratch_len;
+    const PmScratch sc = pm_scratch(a.I, a.N, a.K, R);
+    st.W = ws + sc.W, st.Y = ws + sc.Y, st.T = ws + sc.T, st.WtW = ws + sc.WtW, st.V = ws + sc.V, st.MA = ws + sc.MA, st.MC = ws + sc.MC;
+    st.red = red, st.sys = sys;
+    st.Bs = small, st.BtB = small + RR, st.CtC = small + 2 * RR, st.AtA = small + 3 * RR, st.MB = small + 4 * RR;
+    st.nb = std::min(MS_THREADS, PM_SYS_BYTES / (2 * RR * 8));
+    if (t < RR) st.Bs[t] = st.B[t];
+
+    double xs = 0.0;  // |X|^2 (every start: the same order, the same bits)
+    for (int64_t e = t; e < a.N * a.K; e += MS_THREADS) {
+        const double v = st.x(0, e);
+        xs += v * v;
+    }
+    const double x_sq = wg_sum(xs, red);  // (its barriers also publish Bs)
+
+    const bool hals_a = a.nn_modes & 1, hals_c = (a.nn_modes >> 2) & 1;
+    double *errors = a.errors ? a.errors + s * a.n_iter_max : nullptr;
+    double prev = 0.0;
+    int it = 0;
+    while (it < a.n_iter_max) {
+        st.project();
+        for (int sw = 0; sw < a.n_iter_parafac; ++sw) st.sweep(hals_a, hals_c);
+        ++it;
+        if (a.tol > 0.0) {
+            const double e2 = st.error_sq(x_sq);
+            if (t == 0) errors[it - 1] = sqrt(e2);
+            const bool stop = it >= 2 && (fabs(prev - e2) <= a.tol * prev || e2 < a.absolute_tol);
+            prev = e2;
+            if (stop) break;
+        }
+    }
+    double *P = a.P + s * a.N * R;
+    for (int64_t e = t; e < a.N * R; e += MS_THREADS) {  // P = W T, from the last iteration's W and T
+        const int64_t j = e / R;
+        const int q = (int)(e % R);
+        const double *Ti = st.T + (int64_t)st.slab[j] * RR;
+        double v = 0.0;
+        for (int p = 0; p < R; ++p) v += st.W[j * R + p] * Ti[p * R + q];
+        P[e] = v;
+    }
+    if (t == 0) a.n_iter[s] = it;
+}
+
+struct PmPlan {
+    int64_t N, scratch_len, off_rowptr, off_slab, off_scratch, total;
+};
+
+std::string pm_check(const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank, int32_t n_starts) {
+    if (!row_ptr || I < 1 || K < 1) return "need row_ptr, I >= 1, K >= 1";
+    if (rank < 1 || rank > PM_MAX_RANK) return "need 1 <= rank <= 16";
+    if (n_starts < 1) return "need n_starts >= 1";
+    if (row_ptr[0] != 0) return "row_ptr[0] must be 0";
+    for (int64_t i = 0; i < I; ++i)
+        if (row_ptr[i + 1] - row_ptr[i] < rank) return "every matrix needs at least rank rows";
+    if (rank > K) return "rank exceeds K";
+    if (row_ptr[I] >= (int64_t(1) << 31)) return "more than 2^31 packed rows are not supported";
+    return "";
+}
+
+PmPlan pm_plan(const int64_t *row_ptr, int64_t I, int64_t K, int rank, int32_t n_starts) {
+    PmPlan p{};
+    p.N = row_ptr[I];
+    p.scratch_len = pm_scratch(I, p.N, K, rank).total;
+    auto al = [](int64_t b) { return (b + 255) & ~int64_t(255); };
+    p.off_rowptr = 0;
+    p.off_slab = al((I + 1) * 8);
+    p.off_scratch = p.off_slab + al(p.N * 4);
+    p.total = p.off_scratch + al(p.scratch_len * 8 * int64_t(n_starts));
+    return p;
+}
+
+template <class XL>
+void pm_launch(int rank, const PmArgs &a, int n_starts, hipStream_t s) {
+    switch (rank) {
+#define PM_CASE(R) \
+    case R: hipLaunchKernelGGL((k_ms_pf2als<R, XL>), dim3(n_starts), dim3(MS_THREADS), 0, s, a); break;
+        PM_CASE(1) PM_CASE(2) PM_CASE(3) PM_CASE(4) PM_CASE(5) PM_CASE(6) PM_CASE(7) PM_CASE(8)
+        PM_CASE(9) PM_CASE(10) PM_CASE(11) PM_CASE(12) PM_CASE(13) PM_CASE(14) PM_CASE(15) PM_CASE(16)
+#undef PM_CASE
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+const char *mcl_pf2als_multistart_last_error(void) { return g_pm_error.c_str(); }
+
+int64_t mcl_pf2als_multistart_workspace_bytes(const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank, int32_t n_starts) {
+    if (!pm_check(row_ptr, I, K, rank, n_starts).empty()) return -1;
+    return pm_plan(row_ptr, I, K, rank, n_starts).total;
+}
+
+int mcl_pf2als_multistart_run(const void *X, int32_t x_type, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank, int32_t n_starts,
+                              int32_t n_iter_max, int32_t n_iter_parafac, double tol, double absolute_tol, int32_t nn_modes,
+                              double *factors, double *P, double *errors, int32_t *n_iter, void *workspace, int64_t workspace_bytes,
+                              void *hip_stream) {
+    auto fail = [](const std::string &m) {
+        g_pm_error = "mcl_pf2als_multistart_run: " + m;
+        return 1;
+    };
+    const std::string bad = pm_check(row_ptr, I, K, rank, n_starts);
+    if (!bad.empty()) return fail(bad);
+    if (!X || !factors || !P || !n_iter || !workspace || (tol > 0.0 && !errors)) return fail("NULL argument");
+    if (x_type != MCL_X_F32 && x_type != MCL_X_BF16 && x_type != MCL_X_F16)
+        return fail("unknown x_type " + std::to_string(x_type) + " (MCL_X_F32 = 0, MCL_X_BF16 = 1, MCL_X_F16 = 2)");
+    if (nn_modes & ~5) return fail("nn_modes may hold modes 0 and 2 only (bits 1 and 4)");
+    if (n_iter_max < 1 || n_iter_parafac < 1 || !(tol >= 0.0) || !(absolute_tol >= 0.0))
+        return fail("need n_iter_max >= 1, n_iter_parafac >= 1, tol >= 0 and absolute_tol >= 0");
+    const PmPlan p = pm_plan(row_ptr, I, K, rank, n_starts);
+    if (workspace_bytes < p.total) return fail("workspace too small (mcl_pf2als_multistart_workspace_bytes)");
+    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail("workspace must be 256-byte aligned");
+    hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+    char *ws = static_cast<char *>(workspace);
+    std::vector<int32_t> slab(p.N);
+    for (int64_t i = 0; i < I; ++i)
+        for (int64_t j = row_ptr[i]; j < row_ptr[i + 1]; ++j) slab[j] = (int32_t)i;
+    if (hipMemcpyAsync(ws + p.off_rowptr, row_ptr, (I + 1) * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(ws + p.off_slab, slab.data(), p.N * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+        return fail("upload of row_ptr failed");
+    PmArgs a{};
+    a.X = X;
+    a.row_ptr = reinterpret_cast<const int64_t *>(ws + p.off_rowptr);
+    a.slab_of_row = reinterpret_cast<const int32_t *>(ws + p.off_slab);
+    a.I = I, a.N = p.N, a.K = K;
+    a.scratch_len = p.scratch_len;
+    a.factors = factors, a.P = P, a.errors = tol > 0.0 ? errors : nullptr;
+    a.scratch = reinterpret_cast<double *>(ws + p.off_scratch);
+    a.n_iter = n_iter;
+    a.n_iter_max = n_iter_max, a.n_iter_parafac = n_iter_parafac, a.nn_modes = nn_modes;
+    a.tol = tol, a.absolute_tol = absolute_tol;
+    mcl_x_dispatch(x_type, [&](auto xl) {
+        using XL = decltype(xl);
+        pm_launch<XL>(rank, a, n_starts, s);
+        return 0;
+    });
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(std::string("launch failed: ") + hipGetErrorString(e));
+    return 0;
+}
+
+}  // extern "C"

@@ -12,6 +12,7 @@ ITS OWN contiguous range of the I matrices; the replicated C-mode normal equatio
 all-reduced over the group (RCCL on MI355X, gloo in the CPU tests).
 """
 from copy import copy
+import inspect
 import os
 from typing import NamedTuple, Optional
 
@@ -22,7 +23,7 @@ from ._utils import check_random_state, get_svd, is_iterable, is_tensor, is_torc
 from .coupled_matrices import CoupledMatrixFactorization
 
 __all__ = ["compute_feasibility_gaps", "ADMMVars", "DiagnosticMetrics", "cmf_aoadmm", "parafac2_aoadmm",
-           "PackedMatrices", "partition_slabs", "parafac2_als"]
+           "PackedMatrices", "partition_slabs", "parafac2_als", "parafac2_als_multistart"]
 
 # TEST-ONLY seam.  The CPU test-suite (tests/oracle_engine.py) substitutes a checker engine here to exercise the host and
 # multi-process logic without a GPU.  The substitution is honoured only under MATCOUPLY_AMD_TEST_ENGINE=1, which
@@ -584,6 +585,13 @@ def _parafac2_als_options(matrices, rank, init, nn_modes, n_iter_max, n_iter_par
     return len(rows), K, rows, sorted(modes)
 
 
+def _pf2als_random_start(I, K, rank, random_state):
+    """init="random" of parafac2_als: A [I, rank], B [rank, rank], C [K, rank] uniform from check_random_state(random_state), in
+    that order"""
+    rs = check_random_state(random_state)
+    return rs.uniform(size=(I, rank)), rs.uniform(size=(rank, rank)), rs.uniform(size=(K, rank))
+
+
 def parafac2_als(matrices, rank, n_iter_max=2000, init="random", tol=1e-8, absolute_tol=1e-13, nn_modes=None, n_iter_parafac=5,
                  random_state=None, return_errors=False, **kwargs):
     """Unconstrained PARAFAC2 fitted by alternating least squares (TensorLy's ``parafac2``), on the device.
@@ -602,10 +610,7 @@ def parafac2_als(matrices, rank, n_iter_max=2000, init="random", tol=1e-8, absol
     """
     rank = int(rank)
     I, K, rows, modes = _parafac2_als_options(matrices, rank, init, nn_modes, n_iter_max, n_iter_parafac, kwargs)
-    start = None
-    if init == "random":
-        rs = check_random_state(random_state)
-        start = (rs.uniform(size=(I, rank)), rs.uniform(size=(rank, rank)), rs.uniform(size=(K, rank)))
+    start = _pf2als_random_start(I, K, rank, random_state) if init == "random" else None
     tol = float(tol) if tol else 0.0
     absolute_tol = float(absolute_tol) if absolute_tol else 0.0
     X, row_ptr = _pack(matrices, _device())
@@ -2020,3 +2025,97 @@ def parafac2_aoadmm_multistart(matrices, rank, random_states, *, method="auto", 
     kwargs = dict(parafac2_aoadmm_kwargs)
     kwargs.setdefault("l2_penalty", 0)
     return cmf_aoadmm_multistart(matrices, rank, random_states, method=method, parafac2=True, **kwargs)
+
+
+# ------------------------------------------------------------------------------------------------------------
+# many random starts of parafac2_als (csrc/pf2als_multistart.hip)
+# ------------------------------------------------------------------------------------------------------------
+# method="auto" takes the fused kernel from the first start while elements of X x rank <= _PF2ALS_MS_AUTO_ANY_WORK, and from
+# _PF2ALS_MS_AUTO_MIN_N starts above (profiles/pf2als_multistart_rate.txt: one fused start is 0.91 x one call at the
+# semiconductor size, 2.5e5 elements x rank 2, and 5.1 x at 64 x 64 x 64 rank 8, where the crossover lies at about 5 starts)
+_PF2ALS_MS_AUTO_ANY_WORK = 1 << 19
+_PF2ALS_MS_AUTO_MIN_N = 8
+
+
+def _pf2als_kwargs(kwargs):
+    """the keyword arguments of a parafac2_als call as a complete dict of its parameters; TensorLy options stay in "kwargs"
+    (checked by _parafac2_als_options)"""
+    bound = _PF2ALS_SIGNATURE.bind(None, 1, **kwargs)
+    bound.apply_defaults()
+    kw = dict(bound.arguments)
+    del kw["matrices"], kw["rank"]
+    return kw
+
+
+_PF2ALS_SIGNATURE = inspect.signature(parafac2_als)
+
+
+def _pf2als_unfused_reason(rank, rows, K):
+    """why the fused kernel cannot run these starts (a sentence), or None.  Looks at the arguments only: no device call."""
+    if _test_engine_factory() is not None:
+        return "a substitute compute engine is installed (the fused kernel runs on the HIP engine only)"
+    if rank > _engine.PF2ALS_MS_MAX_RANK:
+        return f"rank {rank} is above {_engine.PF2ALS_MS_MAX_RANK}"
+    if sum(rows) * K > _MULTISTART_MAX_ELEMENTS:
+        return f"X has {sum(rows) * K} elements, above the fused bound of {_MULTISTART_MAX_ELEMENTS}"
+    return None
+
+
+def _pf2als_fused(matrices, rank, random_states, modes, kw):
+    device = _device()
+    X, row_ptr = _pack(matrices, device)
+    I, N, K = len(row_ptr) - 1, int(row_ptr[-1]), int(X.shape[1])
+    starts = [_pf2als_random_start(I, K, rank, rs) for rs in random_states]
+    factors = torch.from_numpy(np.stack([np.concatenate([np.ravel(F) for F in st]) for st in starts])).to(device)
+    tol = float(kw["tol"]) if kw["tol"] else 0.0
+    absolute_tol = float(kw["absolute_tol"]) if kw["absolute_tol"] else 0.0
+    P, errors, n_iter = _engine.pf2als_multistart_run(X, row_ptr, rank, factors, int(kw["n_iter_max"]), int(kw["n_iter_parafac"]),
+                                                      tol, absolute_tol, modes)
+    errors, n_iter = errors.cpu().numpy(), n_iter.cpu().numpy()
+    out = _Out(matrices)
+    results = []
+    for s in range(len(starts)):
+        f = factors[s]
+        A, B, C = f[: I * rank].view(I, rank), f[I * rank: (I + rank) * rank].view(rank, rank), f[(I + rank) * rank:].view(K, rank)
+        result = (None, (out(A), out(B), out(C)), out.split(P[s], row_ptr))
+        if kw["return_errors"]:
+            result = (result, [float(e) for e in errors[s, : int(n_iter[s]) if tol > 0 else 0]])
+        results.append(result)
+    return results
+
+
+def parafac2_als_multistart(matrices, rank, random_states, *, method="auto", **parafac2_als_kwargs):
+    """Fit one unconstrained PARAFAC2-ALS problem from several random starts: element ``s`` of the list returned is what
+    ``parafac2_als(matrices, rank, random_state=random_states[s], **parafac2_als_kwargs)`` returns (same tuple structure, array
+    types and dtypes).  The usual selection afterwards: the start with the lowest final error (``return_errors=True``).
+
+    ``method="sequential"`` calls ``parafac2_als`` once per start.  ``method="fused"`` fits all starts in one launch of a HIP
+    kernel, one workgroup per start, in fp64 (csrc/pf2als_multistart.hip); it serves rank <= 16 and X of at most
+    ``_MULTISTART_MAX_ELEMENTS`` elements, anything else raises ``NotImplementedError`` before the device is touched.  Being fp64,
+    it resolves the default ``tol=1e-8`` where the sequential fit's fp32 X passes do not, so the two
+    methods can stop at different iterations.  ``method="auto"`` takes the fused kernel when it serves the call and is faster
+    (DESIGN.md section 13), else the sequential loop.  Only ``init="random"``: any other start would be the same N times
+    (``ValueError``).  ``parafac2_als``'s own refusals raise for every method.
+    """
+    if method not in ("auto", "fused", "sequential"):
+        raise ValueError(f'method must be "auto", "fused" or "sequential", not {method!r}')
+    if "random_state" in parafac2_als_kwargs:
+        raise TypeError("parafac2_als_multistart takes random_states, not random_state")
+    init = parafac2_als_kwargs.get("init", "random")
+    if not (isinstance(init, str) and init == "random"):
+        raise ValueError(f"parafac2_als_multistart needs init=\"random\" (init={init!r} gives the same start every time)")
+    random_states = list(random_states)
+    kw = _pf2als_kwargs(parafac2_als_kwargs)
+    rank = int(rank)
+    _, K, rows, modes = _parafac2_als_options(matrices, rank, kw["init"], kw["nn_modes"], kw["n_iter_max"], kw["n_iter_parafac"],
+                                              kw["kwargs"])
+    if method != "sequential":
+        reason = _pf2als_unfused_reason(rank, rows, K)
+        if reason is None and method == "auto" and len(random_states) < _PF2ALS_MS_AUTO_MIN_N \
+                and sum(rows) * K * rank > _PF2ALS_MS_AUTO_ANY_WORK:
+            reason = f"{len(random_states)} starts of {sum(rows) * K} elements at rank {rank} run faster one by one"
+        if reason is None:
+            return _pf2als_fused(matrices, rank, random_states, modes, kw) if random_states else []
+        if method == "fused":
+            raise NotImplementedError(f"parafac2_als_multistart(method=\"fused\"): {reason}")
+    return [parafac2_als(matrices, rank, random_state=rs, **parafac2_als_kwargs) for rs in random_states]
