@@ -1745,7 +1745,7 @@ __global__ __launch_bounds__(256) void k_rows_finish_fused(ModeView mv, RegSet r
                         const float nrm = (col < r) ? (float)sqrt(colsq[((long)k * mv.n_slabs + slab) * r + col]) : 1.f;
                         float y = f[h][v] + u[h][v];
                         if (regs.nonneg[k]) y = fmaxf(y, 0.f);
-                        z[h][v] = y * (bound / fmaxf(nrm, bound));
+                        z[h][v] = l2_scaled(y, bound / fmaxf(nrm, bound));
                         u[h][v] = f[h][v] - (z[h][v] - u[h][v]);
                     }
             } else {
@@ -1896,7 +1896,7 @@ __global__ __launch_bounds__(256) void k_rows_finish_solve_stats(ModeView mv, co
                     for (int v = 0; v < 4; ++v) {
                         float y = f[h][v] + u[h][v];
                         if (regs.nonneg[k]) y = fmaxf(y, 0.f);
-                        zg[h][v] = y * l2s[h][v];
+                        zg[h][v] = l2_scaled(y, l2s[h][v]);
                     }
             } else {
                 const float thr = regs.p0[k] / rho;

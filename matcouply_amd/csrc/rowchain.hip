@@ -12,9 +12,11 @@
 //   * loads are unconditional at clamped addresses and masked at use, stores are unconditional with the lanes outside the
 //     matrix writing to a per-lane sink;
 //   * a block is entered only from its predecessor (unrolled loop with an early exit).
-// Arithmetic, its order and every rounding are those of k_rows_finish_solve_stats: results are bit-identical
-// (tests/test_gpu_end_to_end.py::test_full_size_config4_properties compares the chained with the un-chained form, MCL_NO_ROW_PREFETCH=1
-// selects the old kernel for A/B runs).  Reference: the inner loop of admm_update_B, decomposition.py:259-285.
+// Arithmetic, its order and every rounding are those of k_rows_solve_stats / k_rows_finish_solve_stats / k_rows_finish_fused:
+// results are bit-identical.  MCL_NO_ROW_PREFETCH=1 selects those un-pipelined kernels for A/B runs; tests/test_gpu_rowchain.py
+// holds every instantiation below to them bit for bit and to the oracle at the stack, rank and tile edges (partial blocks,
+// slabs shorter than a block, padded column groups, shared sink slots), with the case table in tests/kernel_edge_cases.py.
+// Reference: the inner loop of admm_update_B, decomposition.py:259-285.
 #include <type_traits>
 
 #include "mcl_internal.h"
@@ -178,7 +180,7 @@ __global__ __launch_bounds__(256) void k_rows_chain_mid(ModeView mv, const float
                     for (int v = 0; v < 4; ++v) {
                         float y = f[h][v] + u[h][v];
                         if (regs.nonneg[k]) y = fmaxf(y, 0.f);
-                        zg[h][v] = y * l2s[h][v];
+                        zg[h][v] = l2_scaled(y, l2s[h][v]);
                     }
             } else {
                 const float thr = regs.p0[k] / rho;
@@ -584,7 +586,7 @@ __global__ __launch_bounds__(256) void k_rows_chain_last(ModeView mv, RegSet reg
                     for (int v = 0; v < 4; ++v) {
                         float y = f[h][v] + u[h][v];
                         if (regs.nonneg[k]) y = fmaxf(y, 0.f);
-                        z[h][v] = y * l2s[k][h][v];
+                        z[h][v] = l2_scaled(y, l2s[k][h][v]);
                         u[h][v] = f[h][v] - (z[h][v] - u[h][v]);
                     }
             } else {

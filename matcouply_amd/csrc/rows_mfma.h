@@ -18,6 +18,15 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 #endif
 
+// z = y * s of the L2-ball projection, rounded to fp32 before the dual update u = f - (z - u) uses it.  Left to the
+// compiler, the product is fused into that subtraction (v_fma_f32 with -u) in some kernels and not in others, which
+// broke the bit-identity of the software-pipelined row passes (rowchain.hip) with the kernels of generic.hip
+// (tests/test_gpu_rowchain.py); the reference, too, subtracts the stored auxiliary variable.
+static __device__ __forceinline__ float l2_scaled(float y, float s) {
+#pragma clang fp contract(off)
+    return y * s;
+}
+
 // Sum of a double over the 64 lanes, the total in every lane.  Four DPP steps inside each 16-lane row (quad_perm xor 1,
 // xor 2, row_half_mirror, row_mirror: a few cycles each), then the four row totals through v_readlane - a butterfly of
 // six ds_bpermute pairs costs ~1200 cycles of dependent latency, which bounded the Newton-Schulz iteration of the

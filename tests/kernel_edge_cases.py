@@ -141,3 +141,89 @@ class StepRecorder:
 
     def _note(self, G):
         self.kappa.append(float(np.linalg.cond(G)))
+
+
+# ---- the software-pipelined chained B row pass (csrc/rowchain.hip) ------------------------------------------------------------
+# k_rows_chain_{first,mid,last}<NBR, R64, SIG>: SIG = make_sig(n, class of each penalty) for the three stacks the parser builds in
+# this order - 10 = PARAFAC2 + a row-separable kind, 106 = PARAFAC2 + L2 ball, 459 = PARAFAC2 + unimodality + L2 ball; (1, true)
+# for rank 4..16 (fp64 row algebra, R64), (2, false) for rank 20..32 and (1, false) for rank <= 16 with MCL_NO_ROWS64=1.  Mode 1
+# runs on 64-row tiles inside one slab (four to a workgroup), each a chain of up to four 16-row blocks.  Modes 0 and 2 carry NN
+# and a small ridge, so that the X passes of the trajectory legs stay far from the 1e-5 bar.
+PF2 = {"kind": "parafac2"}
+_NN = {"kind": "nn"}
+_L2 = {"kind": "l2ball", "norm_bound": 1.0}
+_L2NN = {"kind": "l2ball", "norm_bound": 1.0, "non_negativity": True}
+_UNI = {"kind": "unimodal"}
+_UNINN = {"kind": "unimodal", "non_negativity": True}
+ROWCHAIN_RIDGE = 1e-2
+ROWCHAIN_CASES = {
+    # R64 (rank <= 16).  Slabs shorter than one block; last tiles of 1, 15, 16, 17, 63 and 64 rows; 10 tiles (% 4 = 2)
+    "pf2_l2_r4": dict(J=[4, 15, 16, 17, 64, 65, 129, 63, 128], K=48, rank=4, B=[PF2, _L2], inner=5, seed=0),
+    "pf2_l1_r4": dict(J=[4, 9, 16, 65, 80], K=32, rank=4, B=[PF2, {"kind": "l1", "reg_strength": 0.05}], inner=2, seed=1),
+    "pf2_uni_l2_r8": dict(J=[8, 15, 33, 64, 65, 200, 129], K=64, rank=8, B=[PF2, _UNINN, _L2], inner=2, seed=2),
+    # more than 64 tiles: waves 64 apart share their sink slots
+    "pf2_l2_many_r8": dict(J=("randint", 300, 8, 41), K=32, rank=8, B=[PF2, _L2], inner=5, seed=3),
+    # a box that excludes 0: the padding rows of a partial block are not 0 after the prox (prox(0) = 0.05), so the row masks of
+    # the statistics and of the stores matter
+    "pf2_box_r12": dict(J=[12, 79, 80, 63, 128, 17], K=64, rank=12, B=[PF2, {"kind": "box", "min_val": 0.05, "max_val": 0.6}],
+                        inner=2, seed=4),
+    "pf2_uni_l2_r12": dict(J=[12, 40, 81, 127, 64], K=48, rank=12, B=[PF2, _UNI, _L2NN], inner=5, seed=5),
+    # a slab of 18 tiles (more than 16): 23 tiles (% 4 = 3)
+    "pf2_l2_r16": dict(J=[16, 31, 127, 1100, 48], K=96, rank=16, B=[PF2, _L2NN], inner=5, seed=6),
+    "pf2_nn_r16": dict(J=[16, 100, 65, 200], K=64, rank=16, B=[PF2, _NN], inner=1, seed=7),
+    # NB = 2 (rank 20..32), J_i >= 3 r; rank 20 and 28 leave the second column block partial (three or one of its four groups
+    # on the sink)
+    "pf2_l2_r20": dict(J=[60, 64, 65, 100, 129, 250], K=96, rank=20, B=[PF2, _L2], inner=1, seed=8),
+    "pf2_nn_r24": dict(J=[72, 80, 150, 200], K=96, rank=24, B=[PF2, _NN], inner=5, seed=9, constant_B=True, l2B=0.05),
+    "pf2_l1nn_r28": dict(J=[84, 127, 200, 145], K=96, rank=28, B=[PF2, {"kind": "l1", "reg_strength": 0.05, "non_negativity": True}],
+                         inner=2, seed=10),
+    "pf2_uni_l2_r20": dict(J=[60, 64, 129, 193], K=80, rank=20, B=[PF2, _UNINN, _L2NN], inner=5, seed=11),
+    # 28 tiles (% 4 = 0), a slab of 18 tiles
+    "pf2_uni_l2_r32": dict(J=[96, 130, 300, 1100], K=128, rank=32, B=[PF2, _UNI, _L2NN], inner=2, seed=12),
+    "pf2_l2_r32": dict(J=[96, 191, 257], K=96, rank=32, B=[PF2, _L2NN], inner=5, seed=13),
+}
+# the fp32 NB = 1 forms <1, false, SIG>: rank <= 16 with MCL_NO_ROWS64=1 (one case per signature)
+ROWCHAIN_NB1_CASES = ["pf2_l2_r16", "pf2_uni_l2_r8", "pf2_box_r12"]
+# first + last in every inner iteration (MCL_NO_PASS_CHAIN=1): one case per signature x bucket, inner_n_iter_max >= 3
+ROWCHAIN_NO_PASS_CHAIN_CASES = {"pf2_l2_r4": 5, "pf2_l2_r20": 3, "pf2_uni_l2_r12": 5, "pf2_uni_l2_r32": 3, "pf2_box_r12": 4,
+                                "pf2_nn_r24": 5}
+# two full outer iterations through the public call against the oracle (every signature x bucket)
+ROWCHAIN_TRAJECTORY_CASES = ["pf2_l2_r4", "pf2_l2_r20", "pf2_uni_l2_r8", "pf2_uni_l2_r32", "pf2_box_r12", "pf2_l1nn_r28"]
+# stacks and shapes the chain does not serve: the kernels of generic.hip (or checked_inner_loop) must take them
+ROWCHAIN_OTHER_CASES = {
+    "r6_not_multiple_of_4": dict(J=[18, 40, 65, 100], K=48, rank=6, B=[PF2, _L2], inner=3, seed=20),
+    "pf2_l2_r36_nb4": dict(J=[108, 150, 200], K=96, rank=36, B=[PF2, _L2], inner=3, seed=21),
+    "pf2_nn_l2_three_members": dict(J=[16, 40, 65, 129], K=48, rank=8, B=[PF2, _NN, _L2], inner=3, seed=22),
+    "pf2_two_l2_balls": dict(J=[16, 40, 65, 129], K=48, rank=8, B=[PF2, _L2, {"kind": "l2ball", "norm_bound": 2.0}], inner=3,
+                             seed=23),
+    "uni_l2_without_pf2": dict(J=[16, 40, 65, 129], K=48, rank=8, B=[_UNINN, _L2], inner=3, seed=24),
+    "pf2_l2_inner_tol": dict(J=[16, 40, 65, 129], K=48, rank=8, B=[PF2, _L2], inner=3, seed=25, inner_tol=1e-12),
+}
+
+
+def rowchain_case(name):
+    return ROWCHAIN_CASES[name] if name in ROWCHAIN_CASES else ROWCHAIN_OTHER_CASES[name]
+
+
+def rowchain_J(case):
+    J = case["J"]
+    if isinstance(J, tuple):  # ("randint", I, lo, hi)
+        _, I, lo, hi = J
+        return np.random.RandomState(case["seed"]).randint(lo, hi, size=I).astype(np.int64)
+    return np.asarray(J, dtype=np.int64)
+
+
+def rowchain_state(name):
+    """orc.OracleState of a case (X rounded to fp32, as the engine stores it): uniform factors, aux and duals, P_i = eye"""
+    from oracle import aoadmm_oracle as orc
+
+    c = rowchain_case(name)
+    J, r = rowchain_J(c), c["rank"]
+    X, row_ptr = orc.synthetic_problem(len(J), J, c["K"], r, seed=c["seed"], dtype=np.float64)
+    X = X.astype(np.float32).astype(np.float64)
+    regs = [[_NN], [dict(d) for d in c["B"]], [_NN]]
+    st = orc.random_state_for(X, row_ptr, r, regs, seed=c["seed"] + 100, l2=(ROWCHAIN_RIDGE, c.get("l2B", 0.0), ROWCHAIN_RIDGE),
+                              inner_n_iter_max=c["inner"], constant_B=c.get("constant_B", False))
+    if c.get("inner_tol"):
+        st.inner_tol = c["inner_tol"]
+    return st
