@@ -13,6 +13,8 @@
 //         HALS for q = 0..r-1: F[:,q] <- max(0, F[:,q] + (M_F[:,q] - F G_F[:,q]) / G_F[q,q])  (skipped where G_F[q,q] = 0).
 // M_C needs the A and B of the same sweep, so two reads of X per sweep is the floor.  Every reduction has a fixed order and no
 // float atomics are used: two runs are bitwise equal.
+// The two X passes, the fragment layout of C, the r x r inverse, the row update and the fixed-order sum are cp_passes.h's, shared
+// with parafac2als.hip; this file keeps the epilogues, the weights of pass 2 and the sweep.
 // Start: C0 = the C of mcl_svd_init (the stack's right singular vectors), B0 = the leading eigenvectors of the padded-row Gram
 // matrix sum_i X~_i X~_i^T (Jmax x Jmax, fp64), both with the entry of largest magnitude positive (HALS: clipped at 0); A0 = 1.
 #include <algorithm>
@@ -20,15 +22,11 @@
 #include <string>
 #include <vector>
 
-#include "mcl_internal.h"
-#include "rows_mfma.h"
-#include "symeig_lds.h"
-#include "xload.h"
+#include "cp_passes.h"
 
 namespace {
 
 static std::string g_als_error;
-constexpr int ALS_SEG = 64;          // rows of one slab per segment (one wave of pass 1)
 constexpr int ALS_TARGET_WG = 1024;  // workgroups of pass 2 (row chunks x 64-column blocks)
 enum { OP_LOAD = 0, OP_ALS = 1, OP_HALS = 2 };
 
@@ -43,78 +41,20 @@ static __device__ __forceinline__ double row16_sum(double v) {
     return v;
 }
 
-// four consecutive elements of X as fp32, zero past column K (VEC: K % 4 == 0 and an aligned base)
-template <class XL, bool VEC>
-static __device__ __forceinline__ f32x4 als_ld4(const typename XL::T *p, int col, int K) {
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if constexpr (VEC) {
-        if (col < K) v = XL::cvt(XL::template ld4<false>(p));
-    } else {
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            if (col + q < K) v[q] = XL::ld1(p + q);
-    }
-    return v;
-}
-
 // ---- pass 1: XC = X C, M_A partials ---------------------------------------------------------------------------------------
-// One wave per segment (<= 64 rows of one slab; seg = {slab, first packed row, rows, first row within the slab}), walking
-// 64-column chunks H and, inside each, its 4 row blocks rb of 16 rows:
-//   global -> registers: lane (rr = l >> 4, cc = l & 15), t < 4: X[16 rb + 4 t + rr][64 H + 4 cc .. +3]  (256-B row segments)
-//   registers -> LDS   : wave-private 16 x 64 fp32 tile, 16-B slot index XORed with the row (conflict-free)
-//   LDS -> fragments   : lane (row16 = l & 15, g = l >> 4), h < 4: X[16 rb + row16][64 H + 16 h + 4 g .. +3]
-//   MFMA on the transposed problem (rows_mfma.h) with Cfrag[4H + h][hp][lane][kq] = C[64H + 16h + 4g + kq][16hp + (l & 15)]:
-//   accumulator (rb, hp), lane l, reg v = XC[16 rb + row16][16 hp + 4 g + v].
-// The next step's global loads are in flight while the current tile is multiplied (rows clamped into the segment, columns
-// past K zero).  LDS operations of one wave complete in order, so the tile needs no barrier.
+// One wave per segment (xc_segment, cp_passes.h); the epilogue stores the X C rows and the segment's partial of M_A.
 template <class XL, int NB, bool VEC>
-static __device__ __forceinline__ void k_als_xc_body(const typename XL::T *X, const int4 *segs, int nseg, int K, int r, const float *Cfrag,
-                                                     const double *B64, float *XC, double *Pa) {
+__global__ __launch_bounds__(256) void k_als_xc(const typename XL::T *__restrict__ X, const int4 *__restrict__ segs, int nseg, int K, int r,
+                                                const float *__restrict__ Cfrag, const double *__restrict__ B64, float *__restrict__ XC,
+                                                double *__restrict__ Pa) {
     __shared__ f32x4 tiles[4][16 * 16];
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, seg = blockIdx.x * 4 + w;
     if (seg >= nseg) return;  // whole waves; no barrier below
-    f32x4 *T = tiles[w];
     const int4 sg = segs[seg];
     const int row0 = sg.y, n = sg.z, j0 = sg.w;
-    const int row16 = lane & 15, g = lane >> 4, rr = lane >> 4, cc = lane & 15;
+    const int row16 = lane & 15, g = lane >> 4;
     f32x4 acc[4][NB];
-#pragma unroll
-    for (int rb = 0; rb < 4; ++rb)
-#pragma unroll
-        for (int hp = 0; hp < NB; ++hp) acc[rb][hp] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int KC = (K + 63) >> 6;
-    f32x4 xn[4];
-    auto load = [&](int H, int rb) {
-        const int col = 64 * H + 4 * cc;
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-            xn[t] = als_ld4<XL, VEC>(X + (long)(row0 + min(16 * rb + 4 * t + rr, n - 1)) * K + col, col, K);
-    };
-    load(0, 0);
-    for (int H = 0; H < KC; ++H) {
-        f32x4 cf[4][NB];
-#pragma unroll
-        for (int h = 0; h < 4; ++h)
-#pragma unroll
-            for (int hp = 0; hp < NB; ++hp)
-                cf[h][hp] = *reinterpret_cast<const f32x4 *>(Cfrag + (((long)(4 * H + h) * NB + hp) * 64 + lane) * 4);
-#pragma unroll
-        for (int rb = 0; rb < 4; ++rb) {
-#pragma unroll
-            for (int t = 0; t < 4; ++t) T[(4 * t + rr) * 16 + (cc ^ (4 * t + rr))] = xn[t];
-            if (rb < 3) load(H, rb + 1);
-            else if (H + 1 < KC) load(H + 1, 0);
-            f32x4 x[4];
-#pragma unroll
-            for (int h = 0; h < 4; ++h) x[h] = T[row16 * 16 + ((4 * h + g) ^ row16)];
-#pragma unroll
-            for (int h = 0; h < 4; ++h)
-#pragma unroll
-                for (int hp = 0; hp < NB; ++hp)
-#pragma unroll
-                    for (int kq = 0; kq < 4; ++kq) acc[rb][hp] = MFMA16(cf[h][hp][kq], x[h][kq], acc[rb][hp]);
-        }
-    }
+    xc_segment<XL, NB, VEC>(X, sg, K, Cfrag, tiles[w], acc);
     double pa[NB][4];
 #pragma unroll
     for (int hp = 0; hp < NB; ++hp)
@@ -144,116 +84,40 @@ static __device__ __forceinline__ void k_als_xc_body(const typename XL::T *X, co
             if (row16 == 0 && q < r) Pa[(long)seg * r + q] = s;
         }
 }
-template <int NB, bool VEC>
-__global__ __launch_bounds__(256) void k_als_xc(const float *__restrict__ X, const int4 *__restrict__ segs, int nseg, int K, int r,
-                                                const float *__restrict__ Cfrag, const double *__restrict__ B64, float *__restrict__ XC,
-                                                double *__restrict__ Pa) {
-    k_als_xc_body<XF32, NB, VEC>(X, segs, nseg, K, r, Cfrag, B64, XC, Pa);
-}
-// the 16-bit twin (xload.h): the same template arguments after the element type
-template <class XL, int NB, bool VEC>
-__global__ __launch_bounds__(256) void k_als_xc_h(const typename XL::T *__restrict__ X, const int4 *__restrict__ segs, int nseg, int K, int r,
-                                                  const float *__restrict__ Cfrag, const double *__restrict__ B64, float *__restrict__ XC,
-                                                  double *__restrict__ Pa) {
-    k_als_xc_body<XL, NB, VEC>(X, segs, nseg, K, r, Cfrag, B64, XC, Pa);
-}
 
 // ---- pass 2: M_C partials = sum over the rows of a chunk of X^T (B[j] o a_i) ----------------------------------------------------
-// Workgroup (chunk c = consecutive segments, 64-column block kb); wave w takes the 4-row groups w, w + 4, w + 8, w + 12 of every
-// segment.  Lane (rsub = l >> 4, c16 = l & 15) loads X[row0 + 4 gi + rsub][64 kb + 4 c16 .. +3]; MFMA (m, nb): A = component m
-// (output row i = c16 <-> k = 64 kb + 4 i + m), B = W[row][16 nb + c16], reduction index = the 4 rows of the group.
-// Accumulator (m, nb), lane l, reg v = R[64 kb + 4 (4 (l >> 4) + v) + m][16 nb + (l & 15)].  The four waves are summed in fp64 in a
-// fixed order and written as the chunk's partial Pc[c][k][q].
+// Workgroup (chunk c = consecutive segments, 64-column block kb): xtw_segments (cp_passes.h) with the weights B[j][q] a_i[q],
+// formed in fp64 and rounded to fp32; the four waves' fixed-order fp64 sum is the chunk's partial Pc[c][k][q].
 template <class XL, int NB, bool VEC>
-static __device__ __forceinline__ void k_als_xtw_body(const typename XL::T *X, const int4 *segs, const int *chunk_seg, int K, int r,
-                                                      const double *A64, const double *B64, double *Pc) {
+__global__ __launch_bounds__(256) void k_als_xtw(const typename XL::T *__restrict__ X, const int4 *__restrict__ segs,
+                                                 const int *__restrict__ chunk_seg, int K, int r, const double *__restrict__ A64,
+                                                 const double *__restrict__ B64, double *__restrict__ Pc) {
     __shared__ float red[3][NB * 16][64];
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int rsub = lane >> 4, c16 = lane & 15;
-    const int c = blockIdx.x, kb = blockIdx.y, col = 64 * kb + 4 * c16;
+    const int c16 = threadIdx.x & 15, c = blockIdx.x, kb = blockIdx.y;
     f32x4 acc[4][NB];
-#pragma unroll
-    for (int m = 0; m < 4; ++m)
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb) acc[m][nb] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int s_beg = chunk_seg[c], s_end = chunk_seg[c + 1];
-    // the next segment's X rows and B / a values are in flight while the current one is multiplied (loads unconditional:
-    // rows clamped into the segment, invalid rows and columns get a zero weight)
-    f32x4 xn[4];
     double bn[4][NB], an[NB];
-    int nn = 0;
-    auto load = [&](int s) {
-        const int4 sg = segs[s];
-        const int row0 = sg.y, j0 = sg.w;
-        nn = sg.z;
+    auto wload = [&](const int4 sg, const int(&loc)[4]) {
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int loc = min(4 * (w + 4 * u) + rsub, nn - 1);
-            xn[u] = als_ld4<XL, VEC>(X + (long)(row0 + loc) * K + col, col, K);
+        for (int nb = 0; nb < NB; ++nb) {
+            const int q = min(16 * nb + c16, r - 1);
 #pragma unroll
-            for (int nb = 0; nb < NB; ++nb) bn[u][nb] = B64[(long)(j0 + loc) * r + min(16 * nb + c16, r - 1)];
+            for (int u = 0; u < 4; ++u) bn[u][nb] = B64[(long)(sg.w + loc[u]) * r + q];
+            an[nb] = A64[(long)sg.x * r + q];
         }
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb) an[nb] = A64[(long)sg.x * r + min(16 * nb + c16, r - 1)];
     };
-    if (s_beg < s_end) load(s_beg);
-    for (int s = s_beg; s < s_end; ++s) {
-        f32x4 x[4];
-        float wv[4][NB];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const bool ok = 4 * (w + 4 * u) + rsub < nn;
-            x[u] = xn[u];
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb) wv[u][nb] = (ok && 16 * nb + c16 < r) ? (float)(bn[u][nb] * an[nb]) : 0.f;
-        }
-        if (s + 1 < s_end) load(s + 1);
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-#pragma unroll
-            for (int m = 0; m < 4; ++m)
-#pragma unroll
-                for (int nb = 0; nb < NB; ++nb) acc[m][nb] = MFMA16(x[u][m], wv[u][nb], acc[m][nb]);
-    }
-    if (w > 0)
-#pragma unroll
-        for (int m = 0; m < 4; ++m)
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-                for (int v = 0; v < 4; ++v) red[w - 1][(m * NB + nb) * 4 + v][lane] = acc[m][nb][v];
-    __syncthreads();
-    if (w > 0) return;
-#pragma unroll
-    for (int m = 0; m < 4; ++m)
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-            for (int v = 0; v < 4; ++v) {
-                const int e = (m * NB + nb) * 4 + v;
-                const double s = ((double)acc[m][nb][v] + (double)red[0][e][lane]) + ((double)red[1][e][lane] + (double)red[2][e][lane]);
-                const int k = 64 * kb + 4 * (4 * (lane >> 4) + v) + m, q = 16 * nb + (lane & 15);
-                if (k < K && q < r) Pc[((long)c * K + k) * r + q] = s;
-            }
-}
-template <int NB, bool VEC>
-__global__ __launch_bounds__(256) void k_als_xtw(const float *__restrict__ X, const int4 *__restrict__ segs, const int *__restrict__ chunk_seg,
-                                                 int K, int r, const double *__restrict__ A64, const double *__restrict__ B64,
-                                                 double *__restrict__ Pc) {
-    k_als_xtw_body<XF32, NB, VEC>(X, segs, chunk_seg, K, r, A64, B64, Pc);
-}
-// the 16-bit twin (xload.h): the same template arguments after the element type
-template <class XL, int NB, bool VEC>
-__global__ __launch_bounds__(256) void k_als_xtw_h(const typename XL::T *__restrict__ X, const int4 *__restrict__ segs,
-                                                   const int *__restrict__ chunk_seg, int K, int r, const double *__restrict__ A64,
-                                                   const double *__restrict__ B64, double *__restrict__ Pc) {
-    k_als_xtw_body<XL, NB, VEC>(X, segs, chunk_seg, K, r, A64, B64, Pc);
+    xtw_segments<XL, NB, VEC>(X, segs, chunk_seg[c], chunk_seg[c + 1], K, r, kb, wload,
+                              [&](int u, int nb) { return (float)(bn[u][nb] * an[nb]); }, acc);
+    xtw_wave_sum<NB>(acc, red, [&](int kl, int q, double s) {
+        const int k = 64 * kb + kl;
+        if (k < K && q < r) Pc[((long)c * K + k) * r + q] = s;
+    });
 }
 
 // ---- start: the padded-row Gram matrix P = sum_i X~_i X~_i^T [Jmax, Jmax] (fp64 sums of exact products) ----------------------
 // 32 x 32 output tile per workgroup, upper triangle of tiles (mirrored); slabs in ascending order, then columns.
 template <class XL>
-static __device__ __forceinline__ void k_als_rowgram_body(const typename XL::T *X, const int *ext, int I, int K, int Jm, double *P) {
+__global__ __launch_bounds__(256) void k_als_rowgram(const typename XL::T *__restrict__ X, const int *__restrict__ ext, int I, int K, int Jm,
+                                                     double *__restrict__ P) {
     if (blockIdx.y < blockIdx.x) return;
     __shared__ float As[32][33], Bs[32][33];
     const int a0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
@@ -288,16 +152,6 @@ static __device__ __forceinline__ void k_als_rowgram_body(const typename XL::T *
             const int a = a0 + 2 * ty + u, c = c0 + 2 * tx + v;
             if (a < Jm && c < Jm) P[(long)a * Jm + c] = acc[u][v], P[(long)c * Jm + a] = acc[u][v];
         }
-}
-__global__ __launch_bounds__(256) void k_als_rowgram(const float *__restrict__ X, const int *__restrict__ ext, int I, int K, int Jm,
-                                                     double *__restrict__ P) {
-    k_als_rowgram_body<XF32>(X, ext, I, K, Jm, P);
-}
-// the 16-bit twin (xload.h): the same template arguments after the element type
-template <class XL>
-__global__ __launch_bounds__(256) void k_als_rowgram_h(const typename XL::T *__restrict__ X, const int *__restrict__ ext, int I, int K,
-                                                       int Jm, double *__restrict__ P) {
-    k_als_rowgram_body<XL>(X, ext, I, K, Jm, P);
 }
 
 // |X|^2 = trace(P), in row order
@@ -336,20 +190,11 @@ __global__ __launch_bounds__(256) void k_als_segsum(const double *__restrict__ P
     Ma[e] = s;
 }
 
-// out[e] = sum_p part[p][e].  64 elements per workgroup; thread quarter w sums the parts p = w (mod 4) in ascending order, the
-// quarters are combined as (s0 + s1) + (s2 + s3)
+// out[e] = sum_p part[p][e] in the order of fixed_order_sum (cp_passes.h), 64 elements per workgroup
 __global__ __launch_bounds__(256) void k_als_reduce(const double *__restrict__ part, int np, long E, double *__restrict__ out) {
-    __shared__ double red[4][64];
-    const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-    const long e = (long)blockIdx.x * 64 + l;
-    double s = 0.0;
-    if (e < E) {
-#pragma unroll 8
-        for (int p = w; p < np; p += 4) s += part[(long)p * E + e];
-    }
-    red[w][l] = s;
-    __syncthreads();
-    if (w == 0 && e < E) out[e] = (red[0][l] + red[1][l]) + (red[2][l] + red[3][l]);
+    __shared__ double red[256];
+    const long e0 = (long)blockIdx.x * 64;
+    fixed_order_sum<256>(part + e0, np, E, (int)min(64L, E - e0), out + e0, red);
 }
 
 // ---- the row update of one mode (one thread per row of F, 64 rows per workgroup) -------------------------------------------------
@@ -387,38 +232,20 @@ __global__ __launch_bounds__(64) void k_als_update(AlsUpd u) {
             for (int q = 0; q < RMAX; ++q)
                 if (q < r) f[q] = u.F32 ? (double)u.F32[(long)row * r + q] : 1.0;
         } else if (u.op == OP_ALS) {
-#pragma unroll
-            for (int q = 0; q < RMAX; ++q) {
-                double s = 0.0;
-#pragma unroll
-                for (int p = 0; p < RMAX; ++p)
-                    if (p < r && q < r) s = fma(m[p], Gs[p * r + q], s);
-                f[q] = s;
-            }
+            factor_row_update<RMAX>(m, f, Gs, r, 0);
         } else {
 #pragma unroll
             for (int q = 0; q < RMAX; ++q)
                 if (q < r) f[q] = u.F64[(long)row * r + q];
-#pragma unroll
-            for (int q = 0; q < RMAX; ++q) {
-                if (q >= r) continue;
-                const double gqq = Gs[q * r + q];
-                if (gqq == 0.0) continue;
-                double s = m[q];
-#pragma unroll
-                for (int p = 0; p < RMAX; ++p)
-                    if (p < r) s = fma(-f[p], Gs[p * r + q], s);
-                f[q] = fmax(0.0, f[q] + s / gqq);
-            }
+            factor_row_update<RMAX>(m, f, Gs, r, 1);
         }
 #pragma unroll
         for (int q = 0; q < RMAX; ++q)
             if (q < r) u.F64[(long)row * r + q] = f[q];
         if (u.mode == 2) {
-            const int h = row >> 4, g = (row >> 2) & 3, kq = row & 3;
 #pragma unroll
             for (int q = 0; q < RMAX; ++q)
-                if (q < r) u.Cfrag[(((long)h * u.NB + (q >> 4)) * 64 + g * 16 + (q & 15)) * 4 + kq] = (float)f[q];
+                if (q < r) u.Cfrag[cfrag_index(row, q, u.NB)] = (float)f[q];
         }
     }
     __syncthreads();  // (G is no longer read)
@@ -450,7 +277,7 @@ __global__ __launch_bounds__(64) void k_als_update(AlsUpd u) {
 // ---- r x r work between the updates (one workgroup) ------------------------------------------------------------------------
 // prev >= 0: Gram[prev] = the sum of the partial Gram matrices of the factor just updated.  t >= 0 (after mode C): the error
 // e_t.  next >= 0: G_next = the Hadamard product of the other two Gram matrices; ALS: its inverse (pseudo-inverse when it is
-// not positive definite), HALS: G itself, into Gm.
+// not positive definite: spd_inverse_lds, cp_passes.h), HALS: G itself, into Gm.
 struct AlsPrep {
     int prev, nprev, next, method, t, r, nEp;
     const double *Gp;
@@ -464,7 +291,6 @@ __global__ __launch_bounds__(256) void k_als_prep(AlsPrep p) {
     extern __shared__ double sm[];
     const int r = p.r, rr = r * r, tid = threadIdx.x;
     double *S = sm, *W = S + rr, *cs = W + rr;
-    __shared__ int fail_sh;
     if (p.prev >= 0)
         for (int e = tid; e < rr; e += 256) {
             double s = 0.0;
@@ -493,58 +319,10 @@ __global__ __launch_bounds__(256) void k_als_prep(AlsPrep p) {
     }
     if (p.next < 0) return;
     const int o1 = p.next == 0 ? 1 : 0, o2 = p.next == 2 ? 1 : 2;
-    for (int e = tid; e < rr; e += 256) S[e] = p.Gram[o1 * rr + e] * p.Gram[o2 * rr + e];
-    if (tid == 0) fail_sh = 0;
+    auto G = [&](int e) { return p.Gram[o1 * rr + e] * p.Gram[o2 * rr + e]; };
+    for (int e = tid; e < rr; e += 256) S[e] = G(e);
     __syncthreads();
-    if (p.method == 1) {
-        for (int e = tid; e < rr; e += 256) p.Gm[e] = S[e];
-        return;
-    }
-    // in-place Gauss-Jordan without pivoting (SPD: every pivot is positive), in the first wave only: its LDS operations complete
-    // in order, so the two phases of a pivot need no workgroup barrier
-    if (tid < 64)
-        for (int q = 0; q < r; ++q) {
-            const double piv = S[q * r + q];
-            if (!(piv > 0.0) || !isfinite(piv)) {
-                if (tid == 0) fail_sh = 1;
-                break;
-            }
-            const double d = 1.0 / piv;
-            for (int e = tid; e < rr; e += 64) {
-                const int a = e / r, c = e - a * r;
-                if (a != q && c != q) S[e] = fma(-S[a * r + q] * d, S[q * r + c], S[e]);
-            }
-            __builtin_amdgcn_wave_barrier();
-            for (int e = tid; e < 2 * r; e += 64) {
-                const int k = e < r ? e : e - r;
-                if (k == q) {
-                    if (e == q) S[q * r + q] = d;
-                } else if (e < r) {
-                    S[q * r + k] *= d;
-                } else {
-                    S[k * r + q] *= -d;
-                }
-            }
-            __builtin_amdgcn_wave_barrier();
-        }
-    __syncthreads();
-    if (fail_sh) {  // pseudo-inverse: G = W diag(lam) W^T, 1 / lam for lam > 1e-12 lam_max
-        for (int e = tid; e < rr; e += 256) S[e] = p.Gram[o1 * rr + e] * p.Gram[o2 * rr + e];
-        __syncthreads();
-        jacobi_lds(S, W, cs, r);
-        double lmax = 0.0;
-        for (int k = 0; k < r; ++k) lmax = fmax(lmax, S[k * r + k]);
-        for (int e = tid; e < rr; e += 256) {
-            const int a = e / r, c = e - a * r;
-            double s = 0.0;
-            for (int k = 0; k < r; ++k) {
-                const double l = S[k * r + k];
-                if (l > 1e-12 * lmax) s += W[a * r + k] * W[c * r + k] / l;
-            }
-            p.Gm[e] = s;
-        }
-        return;
-    }
+    if (p.method == 0) spd_inverse_lds<256>(S, W, cs, r, G);
     for (int e = tid; e < rr; e += 256) p.Gm[e] = S[e];
 }
 
@@ -556,13 +334,7 @@ __global__ __launch_bounds__(256) void k_als_out(const double *__restrict__ A64,
     if (blockIdx.y == 0) {
         if (e >= (long)N * r) return;
         const int row = (int)(e / r), q = (int)(e - (long)row * r);
-        int lo = 0, hi = I;  // the slab of the row: ext[lo] <= row < ext[lo + 1]
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (ext[mid] <= row) lo = mid;
-            else hi = mid;
-        }
-        B[e] = (float)B64[(long)(row - ext[lo]) * r + q];
+        B[e] = (float)B64[(long)(row - ext[slab_of_row(ext, I, row)]) * r + q];
     } else if (blockIdx.y == 1) {
         if (e < (long)I * r) A[e] = (float)A64[e];
     } else {
@@ -582,12 +354,8 @@ AlsPlan als_plan(const int64_t *row_ptr, int64_t I, int64_t K, int rank) {
     AlsPlan p{};
     p.N = row_ptr[I];
     p.Jm = 0;
-    int64_t nseg = 0;
-    for (int64_t i = 0; i < I; ++i) {
-        const int64_t J = row_ptr[i + 1] - row_ptr[i];
-        p.Jm = std::max(p.Jm, J);
-        nseg += (J + ALS_SEG - 1) / ALS_SEG;
-    }
+    for (int64_t i = 0; i < I; ++i) p.Jm = std::max(p.Jm, row_ptr[i + 1] - row_ptr[i]);
+    const int64_t nseg = seg_count(row_ptr, I);
     const int64_t r = rank;
     p.nseg = (int)nseg;
     p.nkb = (int)((K + 63) / 64);
@@ -597,42 +365,37 @@ AlsPlan als_plan(const int64_t *row_ptr, int64_t I, int64_t K, int rank) {
     p.KH = 4 * (int)((K + 63) / 64);  // 16-row blocks of the C fragments, whole 64-column chunks (zero past K)
     p.wgA = (int)((I + 63) / 64), p.wgB = (int)((p.Jm + 63) / 64), p.wgC = (int)((K + 63) / 64);
     const int wgmax = std::max(p.wgA, std::max(p.wgB, p.wgC));
-    int64_t off = 0;
-    auto take = [&](int64_t bytes) {
-        const int64_t o = off;
-        off = (off + std::max<int64_t>(bytes, 1) + 255) & ~int64_t(255);
-        return o;
-    };
-    p.off_segs = take(std::max<int64_t>(nseg, 1) * 16);
-    p.off_slab_seg = take((I + 1) * 4);
-    p.off_chunk_seg = take((int64_t)(p.nchunk + 1) * 4);
-    p.off_ext = take((I + 1) * 4);
-    p.off_bgrp = take((int64_t)(p.ngrp + 1) * 4);
-    p.off_A = take(I * r * 8);
-    p.off_B = take(p.Jm * r * 8);
-    p.off_C = take(K * r * 8);
-    p.off_Cfrag = take((int64_t)p.KH * p.NB * 64 * 4 * 4);
-    p.off_XC = take(p.N * r * 4);
-    p.off_Pa = take(std::max<int64_t>(nseg, 1) * r * 8);
-    p.off_Pb = take((int64_t)p.ngrp * p.Jm * r * 8);
-    p.off_Mb = take(p.Jm * r * 8);
-    p.off_Pc = take((int64_t)p.nchunk * K * r * 8);
-    p.off_Mc = take(K * r * 8);
-    p.off_Ma = take(I * r * 8);
-    p.off_Gp = take((int64_t)3 * wgmax * r * r * 8);
-    p.off_Ep = take((int64_t)p.wgC * 8);
-    p.off_Gram = take(3 * r * r * 8);
-    p.off_Gm = take(r * r * 8);
-    p.off_small = take(4 * 8);  // |X|^2, e_t
-    p.off_info = take((I + 2) * 4);
-    p.off_scratch = off;
+    WsCursor ws;
+    p.off_segs = ws.take(std::max<int64_t>(nseg, 1) * 16);
+    p.off_slab_seg = ws.take((I + 1) * 4);
+    p.off_chunk_seg = ws.take((int64_t)(p.nchunk + 1) * 4);
+    p.off_ext = ws.take((I + 1) * 4);
+    p.off_bgrp = ws.take((int64_t)(p.ngrp + 1) * 4);
+    p.off_A = ws.take(I * r * 8);
+    p.off_B = ws.take(p.Jm * r * 8);
+    p.off_C = ws.take(K * r * 8);
+    p.off_Cfrag = ws.take((int64_t)p.KH * p.NB * 64 * 4 * 4);
+    p.off_XC = ws.take(p.N * r * 4);
+    p.off_Pa = ws.take(std::max<int64_t>(nseg, 1) * r * 8);
+    p.off_Pb = ws.take((int64_t)p.ngrp * p.Jm * r * 8);
+    p.off_Mb = ws.take(p.Jm * r * 8);
+    p.off_Pc = ws.take((int64_t)p.nchunk * K * r * 8);
+    p.off_Mc = ws.take(K * r * 8);
+    p.off_Ma = ws.take(I * r * 8);
+    p.off_Gp = ws.take((int64_t)3 * wgmax * r * r * 8);
+    p.off_Ep = ws.take((int64_t)p.wgC * 8);
+    p.off_Gram = ws.take(3 * r * r * 8);
+    p.off_Gm = ws.take(r * r * 8);
+    p.off_small = ws.take(4 * 8);  // |X|^2, e_t
+    p.off_info = ws.take((I + 2) * 4);
+    p.off_scratch = ws.off;
     // the start: mcl_svd_init's workspace + C0 (fp32), then P [Jmax, Jmax] + the subspace iteration's + B0 (fp32)
     p.svd_ws = (mcl_svd_stack_workspace_bytes(row_ptr, I, K, rank) + 255) & ~int64_t(255);
     p.gv_ws = (mcl_gram_vectors_workspace_bytes(p.Jm, rank) + 255) & ~int64_t(255);
     const int64_t s1 = p.svd_ws + ((K * r * 4 + 255) & ~int64_t(255));
     const int64_t s2 = ((p.Jm * p.Jm * 8 + 255) & ~int64_t(255)) + p.gv_ws + ((p.Jm * r * 4 + 255) & ~int64_t(255));
     p.scratch = std::max(s1, s2);
-    p.total = off + p.scratch;
+    p.total = ws.off + p.scratch;
     return p;
 }
 
@@ -651,10 +414,10 @@ template <class XL, int NB, bool VEC>
 void launch_passes(bool second, const typename XL::T *X, const AlsPlan &p, const int4 *segs, const int *chunk_seg, int K, int r,
                    const float *Cfrag, const double *A64, const double *B64, float *XC, double *Pa, double *Pc, hipStream_t s) {
     if (!second)
-        hipLaunchKernelGGL((MCL_XKERNEL(k_als_xc, NB, VEC)), dim3((unsigned)((p.nseg + 3) / 4)), dim3(256), 0, s, X, segs, p.nseg, K, r, Cfrag,
+        hipLaunchKernelGGL((k_als_xc<XL, NB, VEC>), dim3((unsigned)((p.nseg + 3) / 4)), dim3(256), 0, s, X, segs, p.nseg, K, r, Cfrag,
                            B64, XC, Pa);
     else
-        hipLaunchKernelGGL((MCL_XKERNEL(k_als_xtw, NB, VEC)), dim3((unsigned)p.nchunk, (unsigned)p.nkb), dim3(256), 0, s, X, segs, chunk_seg, K,
+        hipLaunchKernelGGL((k_als_xtw<XL, NB, VEC>), dim3((unsigned)p.nchunk, (unsigned)p.nkb), dim3(256), 0, s, X, segs, chunk_seg, K,
                            r, A64, B64, Pc);
 }
 
@@ -697,29 +460,18 @@ int als_init(const typename XL::T *X, int32_t x_type, const int64_t *row_ptr, in
     const int nwg[3] = {p.wgA, p.wgB, p.wgC};
 
     // host-built tables: segments, per-slab segment ranges, row chunks of pass 2, slab groups of M_B
-    std::vector<int4> h_segs;
-    std::vector<int> h_slab_seg(1, 0), h_ext((size_t)I + 1), h_chunk((size_t)p.nchunk + 1), h_bgrp((size_t)p.ngrp + 1);
-    for (int64_t i = 0; i < I; ++i) {
-        const int J = (int)(row_ptr[i + 1] - row_ptr[i]);
-        for (int j0 = 0; j0 < J; j0 += ALS_SEG) h_segs.push_back(int4{(int)i, (int)row_ptr[i] + j0, std::min(ALS_SEG, J - j0), j0});
-        h_slab_seg.push_back((int)h_segs.size());
-    }
-    if (h_segs.empty()) h_segs.push_back(int4{0, 0, 0, 0});
-    for (int64_t i = 0; i <= I; ++i) h_ext[(size_t)i] = (int)row_ptr[i];
+    SegTables h = seg_tables(row_ptr, I);
+    std::vector<int> h_chunk((size_t)p.nchunk + 1), h_bgrp((size_t)p.ngrp + 1);
+    if (h.segs.empty()) h.segs.push_back(int4{0, 0, 0, 0});
     for (int c = 0; c <= p.nchunk; ++c) h_chunk[(size_t)c] = (int)((int64_t)p.nseg * c / p.nchunk);
     for (int g = 0; g <= p.ngrp; ++g) h_bgrp[(size_t)g] = (int)(I * g / p.ngrp);
-#define ALS_HIP(expr)                                                                   \
-    do {                                                                                \
-        const hipError_t e_ = (expr);                                                   \
-        if (e_ != hipSuccess) return fail(std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-    ALS_HIP(hipMemcpyAsync(segs, h_segs.data(), sizeof(int4) * h_segs.size(), hipMemcpyHostToDevice, s));
-    ALS_HIP(hipMemcpyAsync(slab_seg, h_slab_seg.data(), sizeof(int) * h_slab_seg.size(), hipMemcpyHostToDevice, s));
-    ALS_HIP(hipMemcpyAsync(ext, h_ext.data(), sizeof(int) * h_ext.size(), hipMemcpyHostToDevice, s));
-    ALS_HIP(hipMemcpyAsync(chunk_seg, h_chunk.data(), sizeof(int) * h_chunk.size(), hipMemcpyHostToDevice, s));
-    ALS_HIP(hipMemcpyAsync(bgrp, h_bgrp.data(), sizeof(int) * h_bgrp.size(), hipMemcpyHostToDevice, s));
-    ALS_HIP(hipMemsetAsync(Cfrag, 0, (size_t)p.KH * p.NB * 64 * 4 * 4, s));
-    ALS_HIP(hipStreamSynchronize(s));  // (the tables are locals)
+    CP_HIP(hipMemcpyAsync(segs, h.segs.data(), sizeof(int4) * h.segs.size(), hipMemcpyHostToDevice, s));
+    CP_HIP(hipMemcpyAsync(slab_seg, h.slab_seg.data(), sizeof(int) * h.slab_seg.size(), hipMemcpyHostToDevice, s));
+    CP_HIP(hipMemcpyAsync(ext, h.ext.data(), sizeof(int) * h.ext.size(), hipMemcpyHostToDevice, s));
+    CP_HIP(hipMemcpyAsync(chunk_seg, h_chunk.data(), sizeof(int) * h_chunk.size(), hipMemcpyHostToDevice, s));
+    CP_HIP(hipMemcpyAsync(bgrp, h_bgrp.data(), sizeof(int) * h_bgrp.size(), hipMemcpyHostToDevice, s));
+    CP_HIP(hipMemsetAsync(Cfrag, 0, (size_t)p.KH * p.NB * 64 * 4 * 4, s));
+    CP_HIP(hipStreamSynchronize(s));  // (the tables are locals)
 
     const int hals = method == MCL_ALS_CP_HALS;
     // ---- start.  C0: the C of mcl_svd_init
@@ -735,7 +487,7 @@ int als_init(const typename XL::T *X, int32_t x_type, const int64_t *row_ptr, in
     char *gv = scr + ((p.Jm * p.Jm * 8 + 255) & ~int64_t(255));
     float *B32 = reinterpret_cast<float *>(gv + p.gv_ws);
     const unsigned tj = (unsigned)((Jm + 31) / 32);
-    hipLaunchKernelGGL((MCL_XKERNEL0(k_als_rowgram)), dim3(tj, tj), dim3(256), 0, s, X, (const int *)ext, (int)I, (int)K, Jm, P);
+    hipLaunchKernelGGL(k_als_rowgram<XL>, dim3(tj, tj), dim3(256), 0, s, X, (const int *)ext, (int)I, (int)K, Jm, P);
     hipLaunchKernelGGL(k_als_trace, dim3(1), dim3(64), 0, s, (const double *)P, Jm, nx2);
     if (mcl_gram_vectors(P, p.Jm, rank, hals, B32, gv, sinfo, (int)I + 1, s, err)) return fail(err);
     u.mode = 1, u.n = Jm, u.F32 = B32, u.F64 = B64, u.Gp = GpM[1];
@@ -745,7 +497,7 @@ int als_init(const typename XL::T *X, int32_t x_type, const int64_t *row_ptr, in
 
     const int rr = r * r;
     const size_t psm = sizeof(double) * (size_t)(2 * rr + 2 * (r / 2 + 2)) + 64;
-    ALS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_als_prep), hipFuncAttributeMaxDynamicSharedMemorySize, (int)psm));
+    CP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_als_prep), hipFuncAttributeMaxDynamicSharedMemorySize, (int)psm));
     auto prep = [&](int prev, int next, int t) {
         AlsPrep q{};
         q.prev = prev, q.nprev = prev >= 0 ? nwg[prev] : 0, q.next = next, q.method = hals, q.t = t, q.r = r, q.nEp = p.wgC;
@@ -755,9 +507,9 @@ int als_init(const typename XL::T *X, int32_t x_type, const int64_t *row_ptr, in
     prep(1, -1, -1);
     prep(0, -1, -1);
     prep(2, 0, -1);
-    ALS_HIP(hipGetLastError());
+    CP_HIP(hipGetLastError());
 
-    const bool vec = (K % 4 == 0) && (reinterpret_cast<uintptr_t>(X) & (x_type == MCL_X_F32 ? 15 : 7)) == 0;
+    const bool vec = K % 4 == 0 && mcl_x_vec_aligned(X, x_type);
     auto pass = [&](bool second) {
         if (p.NB == 1) passes_nb<XL, 1>(second, vec, X, p, segs, chunk_seg, (int)K, r, Cfrag, A64, B64, XC, Pa, Pc, s);
         else if (p.NB == 2) passes_nb<XL, 2>(second, vec, X, p, segs, chunk_seg, (int)K, r, Cfrag, A64, B64, XC, Pa, Pc, s);
@@ -788,12 +540,12 @@ int als_init(const typename XL::T *X, int32_t x_type, const int64_t *row_ptr, in
         u.mode = 2, u.n = (int)K, u.M = Mc, u.F64 = C64, u.Gp = GpM[2];
         update(u, s);
         prep(2, 0, t);
-        ALS_HIP(hipGetLastError());
+        CP_HIP(hipGetLastError());
         used = t + 1;
         if (tol > 0.0) {  // TensorLy's abs_rec_error rule: one 8-byte read per sweep
             double e_t = 0.0;
-            ALS_HIP(hipMemcpyAsync(&e_t, ews, sizeof(double), hipMemcpyDeviceToHost, s));
-            ALS_HIP(hipStreamSynchronize(s));
+            CP_HIP(hipMemcpyAsync(&e_t, ews, sizeof(double), hipMemcpyDeviceToHost, s));
+            CP_HIP(hipStreamSynchronize(s));
             if (t >= 1 && std::fabs(e_prev - e_t) < tol) break;
             e_prev = e_t;
         }
@@ -801,10 +553,9 @@ int als_init(const typename XL::T *X, int32_t x_type, const int64_t *row_ptr, in
     const long big = std::max<long>((long)N, std::max<long>((long)I, (long)K)) * r;
     hipLaunchKernelGGL(k_als_out, dim3((unsigned)((big + 255) / 256), 3), dim3(256), 0, s, (const double *)A64, (const double *)B64,
                        (const double *)C64, (const int *)ext, (int)I, N, (int)K, r, A, B, C);
-    ALS_HIP(hipGetLastError());
-    ALS_HIP(hipMemcpyAsync(info, &used, sizeof(int32_t), hipMemcpyHostToDevice, s));
-    ALS_HIP(hipStreamSynchronize(s));  // (`used` is a local)
-#undef ALS_HIP
+    CP_HIP(hipGetLastError());
+    CP_HIP(hipMemcpyAsync(info, &used, sizeof(int32_t), hipMemcpyHostToDevice, s));
+    CP_HIP(hipStreamSynchronize(s));  // (`used` is a local)
     return 0;
 }
 
@@ -846,8 +597,8 @@ int mcl_als_init_typed(const void *X, int32_t x_type, const int64_t *row_ptr, in
         g_als_error = "mcl_als_init: NULL argument";
         return 1;
     }
-    if (x_type != MCL_X_F32 && x_type != MCL_X_BF16 && x_type != MCL_X_F16) {
-        g_als_error = "mcl_als_init: unknown x_type " + std::to_string(x_type) + " (MCL_X_F32 = 0, MCL_X_BF16 = 1, MCL_X_F16 = 2)";
+    if (!x_type_error(x_type).empty()) {
+        g_als_error = "mcl_als_init: " + x_type_error(x_type);
         return 1;
     }
     if (method != MCL_ALS_CP && method != MCL_ALS_CP_HALS) {

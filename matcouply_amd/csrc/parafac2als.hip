@@ -2,10 +2,11 @@
 // for data resident in HBM.  Model X_i ~ P_i B diag(a_i) C^T with P_i^T P_i = I; A [I, r], B [r, r], C [K, r] kept in fp64.
 //
 // One iteration:
-//   pass 1 (X):  W = X C on the fp32 MFMA (k_pf2als_xc, the X C pass of alsinit.hip without its epilogue)
+//   pass 1 (X):  W = X C on the fp32 MFMA (k_pf2als_xc: xc_segment of cp_passes.h, which alsinit.hip runs too)
 //   per slab:    WtW_i = W_i^T W_i, G_i = B D_i WtW_i D_i B^T, T_i = D_i B^T G_i^-1/2 (cyclic Jacobi, eigenvalues <= 1e-12 lam_max
 //                dropped), P_i^T P_i = T_i^T WtW_i T_i, all fp64 (k_pf2als_polar); the projection is P_i = W_i T_i
-//   pass 2 (X):  Y_i = T_i^T (W_i^T X_i) [r, K], W_i^T X_i on the fp32 MFMA, the rest fp64 (k_pf2als_y); Y is stored [I][K][r]
+//   pass 2 (X):  Y_i = T_i^T (W_i^T X_i) [r, K], W_i^T X_i on the fp32 MFMA (xtw_segments of cp_passes.h), the rest fp64
+//                (k_pf2als_y); Y is stored [I][K][r]
 //   n_iter_parafac CP sweeps on the I x r x K tensor Y, modes A, B, C (ALS normal equations, or one HALS column pass for the
 //   modes in nn_modes), five launches per sweep:
 //     k_pf2als_ab    V_i = Y_i C, M_A[i] = diag(B^T V_i), A[i] <- update; partials of A^T A and M_B = sum_i V_i diag(a_i)
@@ -15,37 +16,20 @@
 //     k_pf2als_prep  (one workgroup) C^T C, <M_C, C>; the next system G_A = B^T B o C^T C
 //   error (tol > 0): e^2 = (|X|^2 - 2 <M_C, C> + sum_i sum((D_i B^T P_i^T P_i B D_i) o C^T C)) / |X|^2 (k_pf2als_fit, k_pf2als_err);
 //   k_pf2als_err also evaluates the stopping rule and raises the device stop flag that gates every launch of the iteration.
-// Every reduction has a fixed order and no float atomics are used: two runs are bitwise equal.
+// Every reduction has a fixed order and no float atomics are used: two runs are bitwise equal.  The r x r inverse, the row update
+// and the fixed-order sum of partials are cp_passes.h's as well.
 #include <algorithm>
 #include <cmath>
 #include <string>
 #include <vector>
 
-#include "mcl_internal.h"
-#include "rows_mfma.h"
-#include "symeig_lds.h"
-#include "xload.h"
+#include "cp_passes.h"
 
 namespace {
 
 static std::string g_pf2als_error;
-constexpr int PA_SEG = 64;     // rows of one slab per segment (one wave of the X C pass)
 constexpr int PA_BLOCK = 16;   // iterations enqueued between two reads of the stop flag
 constexpr int PA_MAX_RANK = 32;
-
-// four consecutive elements of X as fp32, zero past column K (VEC: K % 4 == 0 and an aligned base)
-template <class XL, bool VEC>
-static __device__ __forceinline__ f32x4 pa_ld4(const typename XL::T *p, int col, int K) {
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if constexpr (VEC) {
-        if (col < K) v = XL::cvt(XL::template ld4<false>(p));
-    } else {
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            if (col + q < K) v[q] = XL::ld1(p + q);
-    }
-    return v;
-}
 
 // ---- |X|^2: per-slab partials (threads strided over the slab's elements, then a fixed tree) --------------------------------------
 template <class XL>
@@ -69,8 +53,7 @@ __global__ __launch_bounds__(256) void k_pf2als_norm(const typename XL::T *__res
 }
 
 // ---- pass 1: W = X C -------------------------------------------------------------------------------------------------------
-// alsinit.hip's pass 1 (k_als_xc) without its M_A epilogue: one wave per segment, 64-column chunks through a wave-private LDS tile,
-// MFMA on the transposed problem with Cfrag[4H + h][hp][lane][kq] = C[64H + 16h + 4g + kq][16hp + (l & 15)].
+// One wave per segment (xc_segment, cp_passes.h); the epilogue stores the rows of W.
 template <class XL, int NB, bool VEC>
 __global__ __launch_bounds__(256) void k_pf2als_xc(const typename XL::T *__restrict__ X, const int4 *__restrict__ segs, int nseg, int K, int r,
                                                    const float *__restrict__ Cfrag, float *__restrict__ W, const int *__restrict__ gate) {
@@ -78,48 +61,11 @@ __global__ __launch_bounds__(256) void k_pf2als_xc(const typename XL::T *__restr
     __shared__ f32x4 tiles[4][16 * 16];
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, seg = blockIdx.x * 4 + w;
     if (seg >= nseg) return;  // whole waves; no barrier below
-    f32x4 *T = tiles[w];
     const int4 sg = segs[seg];
     const int row0 = sg.y, n = sg.z;
-    const int row16 = lane & 15, g = lane >> 4, rr = lane >> 4, cc = lane & 15;
+    const int row16 = lane & 15, g = lane >> 4;
     f32x4 acc[4][NB];
-#pragma unroll
-    for (int rb = 0; rb < 4; ++rb)
-#pragma unroll
-        for (int hp = 0; hp < NB; ++hp) acc[rb][hp] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int KC = (K + 63) >> 6;
-    f32x4 xn[4];
-    auto load = [&](int H, int rb) {
-        const int col = 64 * H + 4 * cc;
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-            xn[t] = pa_ld4<XL, VEC>(X + (long)(row0 + min(16 * rb + 4 * t + rr, n - 1)) * K + col, col, K);
-    };
-    load(0, 0);
-    for (int H = 0; H < KC; ++H) {
-        f32x4 cf[4][NB];
-#pragma unroll
-        for (int h = 0; h < 4; ++h)
-#pragma unroll
-            for (int hp = 0; hp < NB; ++hp)
-                cf[h][hp] = *reinterpret_cast<const f32x4 *>(Cfrag + (((long)(4 * H + h) * NB + hp) * 64 + lane) * 4);
-#pragma unroll
-        for (int rb = 0; rb < 4; ++rb) {
-#pragma unroll
-            for (int t = 0; t < 4; ++t) T[(4 * t + rr) * 16 + (cc ^ (4 * t + rr))] = xn[t];
-            if (rb < 3) load(H, rb + 1);
-            else if (H + 1 < KC) load(H + 1, 0);
-            f32x4 x[4];
-#pragma unroll
-            for (int h = 0; h < 4; ++h) x[h] = T[row16 * 16 + ((4 * h + g) ^ row16)];
-#pragma unroll
-            for (int h = 0; h < 4; ++h)
-#pragma unroll
-                for (int hp = 0; hp < NB; ++hp)
-#pragma unroll
-                    for (int kq = 0; kq < 4; ++kq) acc[rb][hp] = MFMA16(cf[h][hp][kq], x[h][kq], acc[rb][hp]);
-        }
-    }
+    xc_segment<XL, NB, VEC>(X, sg, K, Cfrag, tiles[w], acc);
 #pragma unroll
     for (int rb = 0; rb < 4; ++rb) {
         const int loc = 16 * rb + row16;
@@ -233,8 +179,8 @@ __global__ __launch_bounds__(256) void k_pf2als_polar(const float *__restrict__ 
 }
 
 // ---- pass 2: Y_i = T_i^T (W_i^T X_i), one workgroup per (slab, 64-column block) ---------------------------------------------------
-// The MFMA layout of alsinit.hip's pass 2 (k_als_xtw) with the weights W[row][q] (fp32, exact) and the slab's segments as the
-// chunk.  The four waves are summed in fp64 in a fixed order into Z [64][r] (LDS); then Y[i][k][q] = sum_p T_i[p][q] Z[k][p].
+// xtw_segments (cp_passes.h) over the slab's segments with the weights W[row][q] (fp32, exact).  The four waves' fixed-order fp64
+// sum fills Z [64][r] (LDS); then Y[i][k][q] = sum_p T_i[p][q] Z[k][p].
 template <class XL, int NB, bool VEC>
 __global__ __launch_bounds__(256) void k_pf2als_y(const typename XL::T *__restrict__ X, const int4 *__restrict__ segs,
                                                   const int *__restrict__ slab_seg, int K, int r, const float *__restrict__ W,
@@ -243,69 +189,18 @@ __global__ __launch_bounds__(256) void k_pf2als_y(const typename XL::T *__restri
     constexpr int RMAX = 16 * NB;
     __shared__ float red[3][NB * 16][64];
     __shared__ double Zs[64][RMAX + 1], Ts[RMAX * RMAX];
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, tid = threadIdx.x;
-    const int rsub = lane >> 4, c16 = lane & 15;
-    const int i = blockIdx.x, kb = blockIdx.y, col = 64 * kb + 4 * c16;
+    const int tid = threadIdx.x, c16 = tid & 15, i = blockIdx.x, kb = blockIdx.y;
     for (int e = tid; e < r * r; e += 256) Ts[e] = Tm[(long)i * r * r + e];
     f32x4 acc[4][NB];
-#pragma unroll
-    for (int m = 0; m < 4; ++m)
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb) acc[m][nb] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int s_beg = slab_seg[i], s_end = slab_seg[i + 1];
-    f32x4 xn[4];
     float wn[4][NB];
-    int nn = 0;
-    auto load = [&](int s) {
-        const int4 sg = segs[s];
-        const int row0 = sg.y;
-        nn = sg.z;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int loc = min(4 * (w + 4 * u) + rsub, nn - 1);
-            xn[u] = pa_ld4<XL, VEC>(X + (long)(row0 + loc) * K + col, col, K);
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb) wn[u][nb] = W[(long)(row0 + loc) * r + min(16 * nb + c16, r - 1)];
-        }
-    };
-    if (s_beg < s_end) load(s_beg);
-    for (int s = s_beg; s < s_end; ++s) {
-        f32x4 x[4];
-        float wv[4][NB];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const bool ok = 4 * (w + 4 * u) + rsub < nn;
-            x[u] = xn[u];
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb) wv[u][nb] = (ok && 16 * nb + c16 < r) ? wn[u][nb] : 0.f;
-        }
-        if (s + 1 < s_end) load(s + 1);
+    auto wload = [&](const int4 sg, const int(&loc)[4]) {
 #pragma unroll
         for (int u = 0; u < 4; ++u)
 #pragma unroll
-            for (int m = 0; m < 4; ++m)
-#pragma unroll
-                for (int nb = 0; nb < NB; ++nb) acc[m][nb] = MFMA16(x[u][m], wv[u][nb], acc[m][nb]);
-    }
-    if (w > 0)
-#pragma unroll
-        for (int m = 0; m < 4; ++m)
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-                for (int v = 0; v < 4; ++v) red[w - 1][(m * NB + nb) * 4 + v][lane] = acc[m][nb][v];
-    __syncthreads();
-    if (w == 0)
-#pragma unroll
-        for (int m = 0; m < 4; ++m)
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-                for (int v = 0; v < 4; ++v) {
-                    const int e = (m * NB + nb) * 4 + v;
-                    const double s = ((double)acc[m][nb][v] + (double)red[0][e][lane]) + ((double)red[1][e][lane] + (double)red[2][e][lane]);
-                    Zs[4 * (4 * (lane >> 4) + v) + m][16 * nb + (lane & 15)] = s;
-                }
+            for (int nb = 0; nb < NB; ++nb) wn[u][nb] = W[(long)(sg.y + loc[u]) * r + min(16 * nb + c16, r - 1)];
+    };
+    xtw_segments<XL, NB, VEC>(X, segs, slab_seg[i], slab_seg[i + 1], K, r, kb, wload, [&](int u, int nb) { return wn[u][nb]; }, acc);
+    xtw_wave_sum<NB>(acc, red, [&](int kl, int q, double s) { Zs[kl][q] = s; });
     __syncthreads();
     for (int e = tid; e < 64 * r; e += 256) {
         const int kl = e / r, q = e - kl * r, k = 64 * kb + kl;
@@ -313,94 +208,6 @@ __global__ __launch_bounds__(256) void k_pf2als_y(const typename XL::T *__restri
         double s = 0.0;
         for (int p = 0; p < r; ++p) s = fma(Ts[p * r + q], Zs[kl][p], s);
         Y[((long)i * K + k) * r + q] = s;
-    }
-}
-
-// ---- r x r systems in LDS -------------------------------------------------------------------------------------------------
-// S (r x r, LDS) = G on entry.  hals: left as G.  Otherwise S <- G^-1 by Gauss-Jordan without pivoting (SPD); when a pivot is
-// not positive, S <- the pseudo-inverse from a Jacobi eigen-decomposition of G (eigenvalues <= 1e-12 lam_max dropped).
-// Gsave keeps G for that case; W, cs: Jacobi work space.  All NT threads call it.
-template <int NT>
-static __device__ void pa_system(double *S, double *Gsave, double *W, double *cs, int r, int hals) {
-    __shared__ int fail_sh;
-    const int tid = threadIdx.x, rr = r * r;
-    if (hals) return;
-    for (int e = tid; e < rr; e += NT) Gsave[e] = S[e];
-    if (tid == 0) fail_sh = 0;
-    __syncthreads();
-    if (tid < 64)
-        for (int q = 0; q < r; ++q) {
-            const double piv = S[q * r + q];
-            if (!(piv > 0.0) || !isfinite(piv)) {
-                if (tid == 0) fail_sh = 1;
-                break;
-            }
-            const double d = 1.0 / piv;
-            for (int e = tid; e < rr; e += 64) {
-                const int a = e / r, c = e - a * r;
-                if (a != q && c != q) S[e] = fma(-S[a * r + q] * d, S[q * r + c], S[e]);
-            }
-            __builtin_amdgcn_wave_barrier();
-            for (int e = tid; e < 2 * r; e += 64) {
-                const int k = e < r ? e : e - r;
-                if (k == q) {
-                    if (e == q) S[q * r + q] = d;
-                } else if (e < r) {
-                    S[q * r + k] *= d;
-                } else {
-                    S[k * r + q] *= -d;
-                }
-            }
-            __builtin_amdgcn_wave_barrier();
-        }
-    __syncthreads();
-    if (!fail_sh) return;
-    for (int e = tid; e < rr; e += NT) S[e] = Gsave[e];
-    __syncthreads();
-    jacobi_lds_nt<NT>(S, W, cs, r);
-    double lmax = 0.0;
-    for (int k = 0; k < r; ++k) lmax = fmax(lmax, S[k * r + k]);
-    for (int e = tid; e < rr; e += NT) {
-        const int a = e / r, c = e - a * r;
-        double s = 0.0;
-        for (int k = 0; k < r; ++k) {
-            const double l = S[k * r + k];
-            if (l > 1e-12 * lmax) s += W[a * r + k] * W[c * r + k] / l;
-        }
-        Gsave[e] = s;
-    }
-    __syncthreads();
-    for (int e = tid; e < rr; e += NT) S[e] = Gsave[e];
-    __syncthreads();
-}
-
-// one row f of a factor from its right-hand side m: ALS f = m Gm (Gm = G^-1), HALS one pass over the columns (Gm = G)
-template <int RMAX>
-static __device__ __forceinline__ void pa_row_update(const double *m, double *f, const double *Gm, int r, int hals) {
-    if (!hals) {
-        double o[RMAX];
-#pragma unroll
-        for (int q = 0; q < RMAX; ++q) {
-            double s = 0.0;
-#pragma unroll
-            for (int p = 0; p < RMAX; ++p)
-                if (p < r && q < r) s = fma(m[p], Gm[p * r + q], s);
-            o[q] = s;
-        }
-#pragma unroll
-        for (int q = 0; q < RMAX; ++q) f[q] = o[q];
-        return;
-    }
-#pragma unroll
-    for (int q = 0; q < RMAX; ++q) {
-        if (q >= r) continue;
-        const double gqq = Gm[q * r + q];
-        if (gqq == 0.0) continue;
-        double s = m[q];
-#pragma unroll
-        for (int p = 0; p < RMAX; ++p)
-            if (p < r) s = fma(-f[p], Gm[p * r + q], s);
-        f[q] = fmax(0.0, f[q] + s / gqq);
     }
 }
 
@@ -466,7 +273,7 @@ __global__ __launch_bounds__(256) void k_pf2als_ab(const double *__restrict__ Y,
             double m[RMAX], f[RMAX];
 #pragma unroll
             for (int q = 0; q < RMAX; ++q) m[q] = q < r ? ms[w][q] : 0.0, f[q] = q < r ? A64[(long)i * r + q] : 0.0;
-            pa_row_update<RMAX>(m, f, Gs, r, hals);
+            factor_row_update<RMAX>(m, f, Gs, r, hals);
             if (hals) {
 #pragma unroll
                 for (int q = 0; q < RMAX; ++q)
@@ -510,26 +317,6 @@ __global__ __launch_bounds__(256) void k_pf2als_ab(const double *__restrict__ Y,
     }
 }
 
-// out[e] = sum over np parts of part[p * stride + e], e < E; NT threads: quarter u of the threads sums the parts p = u (mod 4) of
-// entry e in ascending order, quarters combined as (s0 + s1) + (s2 + s3).  red: NT doubles of LDS.  All NT threads call it.
-template <int NT>
-static __device__ void pa_reduce(const double *part, int np, long stride, int E, double *out, double *red) {
-    constexpr int Q = NT / 4;
-    const int tid = threadIdx.x, u = tid / Q, l = tid - u * Q;
-    for (int e0 = 0; e0 < E; e0 += Q) {
-        const int e = e0 + l;
-        double s = 0.0;
-        if (e < E) {
-#pragma unroll 8
-            for (int p = u; p < np; p += 4) s += part[(long)p * stride + e];
-        }
-        red[tid] = s;
-        __syncthreads();
-        if (u == 0 && e < E) out[e] = (red[l] + red[Q + l]) + (red[2 * Q + l] + red[3 * Q + l]);
-        __syncthreads();
-    }
-}
-
 // ---- mode B (one workgroup): A^T A and M_B from the partials, B <- update, B^T B, the system of mode C ------------------------------
 template <int RMAX>
 __global__ __launch_bounds__(1024) void k_pf2als_b(const double *__restrict__ Pab, int ngrp, int r, int hals_c,
@@ -537,15 +324,15 @@ __global__ __launch_bounds__(1024) void k_pf2als_b(const double *__restrict__ Pa
                                                    const int *__restrict__ gate) {
     if (*gate) return;
     constexpr int RR = RMAX * RMAX;
-    __shared__ double sums[2 * RR], S[RR], Gsave[RR], Wj[RR], cs[RMAX + 2], Bn[RR], red[1024];
+    __shared__ double sums[2 * RR], S[RR], Wj[RR], cs[RMAX + 2], Bn[RR], red[1024];
     const int tid = threadIdx.x, rr = r * r;
-    pa_reduce<1024>(Pab, ngrp, 2 * rr, 2 * rr, sums, red);  // sums = [A^T A | M_B]
+    fixed_order_sum<1024>(Pab, ngrp, 2 * rr, 2 * rr, sums, red);  // sums = [A^T A | M_B]
     for (int e = tid; e < rr; e += 1024) {
         Gram[e] = sums[e];
         S[e] = sums[e] * Gram[2 * rr + e];  // G_B = A^T A o C^T C
     }
     __syncthreads();
-    pa_system<1024>(S, Gsave, Wj, cs, r, 0);  // (mode B is never non-negative: ALS)
+    spd_inverse_lds<1024>(S, Wj, cs, r, [&](int e) { return sums[e] * Gram[2 * rr + e]; });  // (mode B is never non-negative: ALS)
     for (int e = tid; e < rr; e += 1024) {  // B[q][s] = sum_p M_B[q][p] G_B^-1[p][s]
         const int q = e / r, c = e - q * r;
         double t = 0.0;
@@ -562,7 +349,7 @@ __global__ __launch_bounds__(1024) void k_pf2als_b(const double *__restrict__ Pa
         S[e] = sums[e] * s;  // G_C = A^T A o B^T B
     }
     __syncthreads();
-    pa_system<1024>(S, Gsave, Wj, cs, r, hals_c);
+    if (!hals_c) spd_inverse_lds<1024>(S, Wj, cs, r, [&](int e) { return sums[e] * Gram[rr + e]; });
     for (int e = tid; e < rr; e += 1024) Gm[e] = S[e];
 }
 
@@ -628,7 +415,7 @@ __global__ __launch_bounds__(256) void k_pf2als_c(const double *__restrict__ Pc,
         double mv[RMAX], f[RMAX];
 #pragma unroll
         for (int q = 0; q < RMAX; ++q) mv[q] = Ms[row][q], f[q] = Fs[row][q];
-        pa_row_update<RMAX>(mv, f, Gs, r, hals);
+        factor_row_update<RMAX>(mv, f, Gs, r, hals);
         if (hals) {
 #pragma unroll
             for (int q = 0; q < RMAX; ++q)
@@ -646,8 +433,7 @@ __global__ __launch_bounds__(256) void k_pf2als_c(const double *__restrict__ Pc,
     if (ok) {
         const double f = Fs[row][s];
         C64[(long)k * r + s] = f;
-        const int h = k >> 4, gg = (k >> 2) & 3, kq = k & 3;
-        Cfrag[(((long)h * NB + (s >> 4)) * 64 + gg * 16 + (s & 15)) * 4 + kq] = (float)f;
+        Cfrag[cfrag_index(k, s, NB)] = (float)f;
     }
     __syncthreads();
     for (int e = tid; e < rr; e += 256) {
@@ -671,9 +457,9 @@ __global__ __launch_bounds__(1024) void k_pf2als_prep(const double *__restrict__
                                                       double *__restrict__ small, const int *__restrict__ gate) {
     if (*gate) return;
     constexpr int RR = RMAX * RMAX;
-    __shared__ double ctc[RR], S[RR], Gsave[RR], Wj[RR], cs[RMAX + 2], red[1024];
+    __shared__ double ctc[RR], S[RR], Wj[RR], cs[RMAX + 2], red[1024];
     const int tid = threadIdx.x, rr = r * r;
-    pa_reduce<1024>(Pcc, nwg, rr, rr, ctc, red);
+    fixed_order_sum<1024>(Pcc, nwg, rr, rr, ctc, red);
     if (tid == 0) {
         double t = 0.0;
         for (int w = 0; w < nwg; ++w) t += Pdot[w];
@@ -684,7 +470,7 @@ __global__ __launch_bounds__(1024) void k_pf2als_prep(const double *__restrict__
         S[e] = Gram[rr + e] * ctc[e];  // G_A = B^T B o C^T C
     }
     __syncthreads();
-    pa_system<1024>(S, Gsave, Wj, cs, r, hals_a);
+    if (!hals_a) spd_inverse_lds<1024>(S, Wj, cs, r, [&](int e) { return Gram[rr + e] * ctc[e]; });
     for (int e = tid; e < rr; e += 1024) Gm[e] = S[e];
 }
 
@@ -695,7 +481,7 @@ __global__ __launch_bounds__(1024) void k_pf2als_start(const double *__restrict_
                                                        float *__restrict__ Cfrag, double *__restrict__ Gram, double *__restrict__ Gm,
                                                        double *__restrict__ small, int *__restrict__ gate) {
     constexpr int RR = RMAX * RMAX;
-    __shared__ double S[RR], Gsave[RR], Wj[RR], cs[RMAX + 2];
+    __shared__ double S[RR], Wj[RR], cs[RMAX + 2];
     const int tid = threadIdx.x, rr = r * r;
     if (tid == 0) {
         double t = 0.0;
@@ -705,8 +491,7 @@ __global__ __launch_bounds__(1024) void k_pf2als_start(const double *__restrict_
     }
     for (long e = tid; e < (long)K * r; e += 1024) {
         const int k = (int)(e / r), s = (int)(e - (long)k * r);
-        const int h = k >> 4, gg = (k >> 2) & 3, kq = k & 3;
-        Cfrag[(((long)h * NB + (s >> 4)) * 64 + gg * 16 + (s & 15)) * 4 + kq] = (float)C64[e];
+        Cfrag[cfrag_index(k, s, NB)] = (float)C64[e];
     }
     for (int e = tid; e < rr; e += 1024) {
         const int a = e / r, c = e - a * r;
@@ -717,7 +502,7 @@ __global__ __launch_bounds__(1024) void k_pf2als_start(const double *__restrict_
         S[e] = sb * sc;
     }
     __syncthreads();
-    pa_system<1024>(S, Gsave, Wj, cs, r, hals_a);
+    if (!hals_a) spd_inverse_lds<1024>(S, Wj, cs, r, [&](int e) { return Gram[rr + e] * Gram[2 * rr + e]; });
     for (int e = tid; e < rr; e += 1024) Gm[e] = S[e];
 }
 
@@ -782,13 +567,7 @@ __global__ __launch_bounds__(256) void k_pf2als_out(const float *__restrict__ W,
     if (blockIdx.y == 0) {
         if (e >= (long)N * r) return;
         const int row = (int)(e / r), q = (int)(e - (long)row * r);
-        int lo = 0, hi = I;  // the slab of the row: ext[lo] <= row < ext[lo + 1]
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (ext[mid] <= row) lo = mid;
-            else hi = mid;
-        }
-        const double *T = Tm + (long)lo * r * r;
+        const double *T = Tm + (long)slab_of_row(ext, I, row) * r * r;
         double s = 0.0;
         for (int p = 0; p < r; ++p) s = fma((double)W[(long)row * r + p], T[p * r + q], s);
         P[e] = (float)s;
@@ -812,8 +591,7 @@ struct PaPlan {
 PaPlan pa_plan(const int64_t *row_ptr, int64_t I, int64_t K, int rank) {
     PaPlan p{};
     p.N = row_ptr[I];
-    int64_t nseg = 0;
-    for (int64_t i = 0; i < I; ++i) nseg += (row_ptr[i + 1] - row_ptr[i] + PA_SEG - 1) / PA_SEG;
+    const int64_t nseg = seg_count(row_ptr, I);
     const int64_t r = rank;
     p.nseg = (int)nseg;
     p.nkb = (int)((K + 63) / 64);
@@ -823,39 +601,34 @@ PaPlan pa_plan(const int64_t *row_ptr, int64_t I, int64_t K, int rank) {
     p.ngrp_ab = (int)std::max<int64_t>(1, std::min<int64_t>(128, (I + 7) / 8));
     p.ngrp_mc = (int)std::max<int64_t>(1, std::min<int64_t>(I, std::max<int64_t>(1, 256 / p.nkb)));
     p.wgC = (int)((K + (256 / p.RMAX) - 1) / (256 / p.RMAX));
-    int64_t off = 0;
-    auto take = [&](int64_t bytes) {
-        const int64_t o = off;
-        off = (off + std::max<int64_t>(bytes, 1) + 255) & ~int64_t(255);
-        return o;
-    };
-    p.off_segs = take(std::max<int64_t>(nseg, 1) * 16);
-    p.off_slab_seg = take((I + 1) * 4);
-    p.off_ext = take((I + 1) * 4);
-    p.off_A = take(I * r * 8);
-    p.off_B = take(r * r * 8);
-    p.off_C = take(K * r * 8);
-    p.off_Cfrag = take((int64_t)p.KH * p.NB * 64 * 4 * 4);
-    p.off_W = take(p.N * r * 4);
-    p.off_T = take(I * r * r * 8);
-    p.off_PtP = take(I * r * r * 8);
-    p.off_Y = take(I * K * r * 8);
-    p.off_Pab = take((int64_t)p.ngrp_ab * 2 * r * r * 8);
-    p.off_Pc = take((int64_t)p.ngrp_mc * K * r * 8);
-    p.off_Pcc = take((int64_t)p.wgC * r * r * 8);
-    p.off_Pdot = take((int64_t)p.wgC * 8);
-    p.off_Pfit = take((int64_t)p.ngrp_ab * 8);
-    p.off_nxp = take(I * 8);
-    p.off_Gram = take(3 * r * r * 8);
-    p.off_Gm = take(r * r * 8);
-    p.off_small = take(4 * 8);  // |X|^2, <M_C, C>, e_{t-1}^2
-    p.off_gate = take(4 * 4);   // stop flag, iterations used
-    p.off_info = take((I + 2) * 4);
-    p.off_scratch = off;
+    WsCursor ws;
+    p.off_segs = ws.take(std::max<int64_t>(nseg, 1) * 16);
+    p.off_slab_seg = ws.take((I + 1) * 4);
+    p.off_ext = ws.take((I + 1) * 4);
+    p.off_A = ws.take(I * r * 8);
+    p.off_B = ws.take(r * r * 8);
+    p.off_C = ws.take(K * r * 8);
+    p.off_Cfrag = ws.take((int64_t)p.KH * p.NB * 64 * 4 * 4);
+    p.off_W = ws.take(p.N * r * 4);
+    p.off_T = ws.take(I * r * r * 8);
+    p.off_PtP = ws.take(I * r * r * 8);
+    p.off_Y = ws.take(I * K * r * 8);
+    p.off_Pab = ws.take((int64_t)p.ngrp_ab * 2 * r * r * 8);
+    p.off_Pc = ws.take((int64_t)p.ngrp_mc * K * r * 8);
+    p.off_Pcc = ws.take((int64_t)p.wgC * r * r * 8);
+    p.off_Pdot = ws.take((int64_t)p.wgC * 8);
+    p.off_Pfit = ws.take((int64_t)p.ngrp_ab * 8);
+    p.off_nxp = ws.take(I * 8);
+    p.off_Gram = ws.take(3 * r * r * 8);
+    p.off_Gm = ws.take(r * r * 8);
+    p.off_small = ws.take(4 * 8);  // |X|^2, <M_C, C>, e_{t-1}^2
+    p.off_gate = ws.take(4 * 4);   // stop flag, iterations used
+    p.off_info = ws.take((I + 2) * 4);
+    p.off_scratch = ws.off;
     // the svd start: mcl_svd_init's workspace + C0 (fp32)
     p.svd_ws = (mcl_svd_stack_workspace_bytes(row_ptr, I, K, rank) + 255) & ~int64_t(255);
     p.scratch = p.svd_ws + ((K * r * 4 + 255) & ~int64_t(255));
-    p.total = off + p.scratch;
+    p.total = ws.off + p.scratch;
     return p;
 }
 
@@ -902,53 +675,41 @@ int pf2als_run(const typename XL::T *X, int32_t x_type, const int64_t *row_ptr, 
     const int r = rank, N = (int)p.N;
     const bool hals_a = nn_modes & 1, hals_c = (nn_modes >> 2) & 1;
 
-    std::vector<int4> h_segs;
-    std::vector<int> h_slab_seg(1, 0), h_ext((size_t)I + 1);
-    for (int64_t i = 0; i < I; ++i) {
-        const int J = (int)(row_ptr[i + 1] - row_ptr[i]);
-        for (int j0 = 0; j0 < J; j0 += PA_SEG) h_segs.push_back(int4{(int)i, (int)row_ptr[i] + j0, std::min(PA_SEG, J - j0), j0});
-        h_slab_seg.push_back((int)h_segs.size());
-    }
-    for (int64_t i = 0; i <= I; ++i) h_ext[(size_t)i] = (int)row_ptr[i];
-#define PA_HIP(expr)                                                                    \
-    do {                                                                                \
-        const hipError_t e_ = (expr);                                                   \
-        if (e_ != hipSuccess) return fail(std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-    PA_HIP(hipMemcpyAsync(segs, h_segs.data(), sizeof(int4) * h_segs.size(), hipMemcpyHostToDevice, s));
-    PA_HIP(hipMemcpyAsync(slab_seg, h_slab_seg.data(), sizeof(int) * h_slab_seg.size(), hipMemcpyHostToDevice, s));
-    PA_HIP(hipMemcpyAsync(ext, h_ext.data(), sizeof(int) * h_ext.size(), hipMemcpyHostToDevice, s));
-    PA_HIP(hipMemsetAsync(Cfrag, 0, (size_t)p.KH * p.NB * 64 * 4 * 4, s));
-    PA_HIP(hipMemsetAsync(gate, 0, 4 * sizeof(int), s));
-    PA_HIP(hipStreamSynchronize(s));  // (the tables are locals)
+    const SegTables h = seg_tables(row_ptr, I);
+    CP_HIP(hipMemcpyAsync(segs, h.segs.data(), sizeof(int4) * h.segs.size(), hipMemcpyHostToDevice, s));
+    CP_HIP(hipMemcpyAsync(slab_seg, h.slab_seg.data(), sizeof(int) * h.slab_seg.size(), hipMemcpyHostToDevice, s));
+    CP_HIP(hipMemcpyAsync(ext, h.ext.data(), sizeof(int) * h.ext.size(), hipMemcpyHostToDevice, s));
+    CP_HIP(hipMemsetAsync(Cfrag, 0, (size_t)p.KH * p.NB * 64 * 4 * 4, s));
+    CP_HIP(hipMemsetAsync(gate, 0, 4 * sizeof(int), s));
+    CP_HIP(hipStreamSynchronize(s));  // (the tables are locals)
 
     // ---- start: the given factors, or A = 1, B = I, C = the C of mcl_svd_init
     if (A0) {
-        PA_HIP(hipMemcpyAsync(A64, A0, sizeof(double) * I * r, hipMemcpyDeviceToDevice, s));
-        PA_HIP(hipMemcpyAsync(B64, B0, sizeof(double) * r * r, hipMemcpyDeviceToDevice, s));
-        PA_HIP(hipMemcpyAsync(C64, C0, sizeof(double) * K * r, hipMemcpyDeviceToDevice, s));
+        CP_HIP(hipMemcpyAsync(A64, A0, sizeof(double) * I * r, hipMemcpyDeviceToDevice, s));
+        CP_HIP(hipMemcpyAsync(B64, B0, sizeof(double) * r * r, hipMemcpyDeviceToDevice, s));
+        CP_HIP(hipMemcpyAsync(C64, C0, sizeof(double) * K * r, hipMemcpyDeviceToDevice, s));
     } else {
         float *C32 = reinterpret_cast<float *>(scr + p.svd_ws);
         std::string err;
         if (mcl_svd_stack_right(X, x_type, row_ptr, I, K, rank, 0, C32, scr, p.svd_ws, sinfo, s, err)) return fail(err);
         std::vector<double> h_A((size_t)I * r, 1.0), h_B((size_t)r * r, 0.0);
         for (int q = 0; q < r; ++q) h_B[(size_t)q * r + q] = 1.0;
-        PA_HIP(hipMemcpyAsync(A64, h_A.data(), sizeof(double) * h_A.size(), hipMemcpyHostToDevice, s));
-        PA_HIP(hipMemcpyAsync(B64, h_B.data(), sizeof(double) * h_B.size(), hipMemcpyHostToDevice, s));
+        CP_HIP(hipMemcpyAsync(A64, h_A.data(), sizeof(double) * h_A.size(), hipMemcpyHostToDevice, s));
+        CP_HIP(hipMemcpyAsync(B64, h_B.data(), sizeof(double) * h_B.size(), hipMemcpyHostToDevice, s));
         std::vector<float> h_C((size_t)K * r);
         std::vector<double> h_C64((size_t)K * r);
-        PA_HIP(hipMemcpyAsync(h_C.data(), C32, sizeof(float) * h_C.size(), hipMemcpyDeviceToHost, s));
-        PA_HIP(hipStreamSynchronize(s));
+        CP_HIP(hipMemcpyAsync(h_C.data(), C32, sizeof(float) * h_C.size(), hipMemcpyDeviceToHost, s));
+        CP_HIP(hipStreamSynchronize(s));
         for (size_t e = 0; e < h_C.size(); ++e) h_C64[e] = (double)h_C[e];
-        PA_HIP(hipMemcpyAsync(C64, h_C64.data(), sizeof(double) * h_C64.size(), hipMemcpyHostToDevice, s));
-        PA_HIP(hipStreamSynchronize(s));  // (the host copies are locals)
+        CP_HIP(hipMemcpyAsync(C64, h_C64.data(), sizeof(double) * h_C64.size(), hipMemcpyHostToDevice, s));
+        CP_HIP(hipStreamSynchronize(s));  // (the host copies are locals)
     }
     hipLaunchKernelGGL(k_pf2als_norm<XL>, dim3((unsigned)I), dim3(256), 0, s, X, (const int *)ext, (int)K, nxp);
     hipLaunchKernelGGL(k_pf2als_start<RMAX>, dim3(1), dim3(1024), 0, s, (const double *)nxp, (int)I, (int)K, r, NB, (int)hals_a,
                        (const double *)B64, (const double *)C64, Cfrag, Gram, Gm, small, gate);
-    PA_HIP(hipGetLastError());
+    CP_HIP(hipGetLastError());
 
-    const bool vec = (K % 4 == 0) && (reinterpret_cast<uintptr_t>(X) & (x_type == MCL_X_F32 ? 15 : 7)) == 0;
+    const bool vec = K % 4 == 0 && mcl_x_vec_aligned(X, x_type);
     auto pass = [&](bool second) {
         if (vec) PaLaunch<XL, NB>::template passes<true>(second, X, p, segs, slab_seg, (int)I, (int)K, r, Cfrag, W, Tm, Y, gate, s);
         else PaLaunch<XL, NB>::template passes<false>(second, X, p, segs, slab_seg, (int)I, (int)K, r, Cfrag, W, Tm, Y, gate, s);
@@ -977,11 +738,11 @@ int pf2als_run(const typename XL::T *X, int32_t x_type, const int64_t *row_ptr, 
                                (const double *)B64, (const double *)Gram, (int)I, r, p.ngrp_ab, Pfit, (const int *)gate);
             hipLaunchKernelGGL(k_pf2als_err, dim3(1), dim3(64), 0, s, (const double *)Pfit, p.ngrp_ab, t, tol, absolute_tol, small, errors, gate);
         }
-        PA_HIP(hipGetLastError());
+        CP_HIP(hipGetLastError());
         if (check && ((t + 1) % PA_BLOCK == 0 || t + 1 == n_iter_max)) {  // the verdict, read in blocks: later launches are gated
             int g[2] = {0, 0};
-            PA_HIP(hipMemcpyAsync(g, gate, sizeof(g), hipMemcpyDeviceToHost, s));
-            PA_HIP(hipStreamSynchronize(s));
+            CP_HIP(hipMemcpyAsync(g, gate, sizeof(g), hipMemcpyDeviceToHost, s));
+            CP_HIP(hipStreamSynchronize(s));
             used = g[1];
             if (g[0]) break;
         }
@@ -989,10 +750,9 @@ int pf2als_run(const typename XL::T *X, int32_t x_type, const int64_t *row_ptr, 
     const long big = std::max<long>((long)N, std::max<long>((long)I, (long)K)) * r;
     hipLaunchKernelGGL(k_pf2als_out, dim3((unsigned)((big + 255) / 256), 4), dim3(256), 0, s, (const float *)W, (const double *)Tm,
                        (const double *)A64, (const double *)B64, (const double *)C64, (const int *)ext, (int)I, N, (int)K, r, P, A, B, C);
-    PA_HIP(hipGetLastError());
-    PA_HIP(hipMemcpyAsync(info, &used, sizeof(int32_t), hipMemcpyHostToDevice, s));
-    PA_HIP(hipStreamSynchronize(s));  // (`used` is a local)
-#undef PA_HIP
+    CP_HIP(hipGetLastError());
+    CP_HIP(hipMemcpyAsync(info, &used, sizeof(int32_t), hipMemcpyHostToDevice, s));
+    CP_HIP(hipStreamSynchronize(s));  // (`used` is a local)
     return 0;
 }
 
@@ -1040,8 +800,8 @@ int mcl_parafac2_als_typed(const void *X, int32_t x_type, const int64_t *row_ptr
         g_pf2als_error = "mcl_parafac2_als: the svd start needs K <= 2048";
         return 1;
     }
-    if (x_type != MCL_X_F32 && x_type != MCL_X_BF16 && x_type != MCL_X_F16) {
-        g_pf2als_error = "mcl_parafac2_als: unknown x_type " + std::to_string(x_type) + " (MCL_X_F32 = 0, MCL_X_BF16 = 1, MCL_X_F16 = 2)";
+    if (!x_type_error(x_type).empty()) {
+        g_pf2als_error = "mcl_parafac2_als: " + x_type_error(x_type);
         return 1;
     }
     if (nn_modes & ~5) {

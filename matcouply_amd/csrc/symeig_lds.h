@@ -1,5 +1,6 @@
 // Symmetric eigen-decomposition of a small matrix held in LDS (cyclic Jacobi), shared by the SVD initialiser (svdinit.hip:
-// Rayleigh-Ritz step of the subspace iteration) and the CP initialiser (alsinit.hip: pseudo-inverse of a singular r x r Gram).
+// Rayleigh-Ritz step of the subspace iteration), the pseudo-inverse of a singular r x r Gram matrix (cp_passes.h: the CP
+// initialisers and parafac2_als) and parafac2_als's polar step (parafac2als.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -88,9 +88,10 @@ static inline auto mcl_x_dispatch(int x_type, F &&f) {
 template <class XL>
 static inline const typename XL::T *mcl_x(const mcl_context *c) { return static_cast<const typename XL::T *>(c->X); }
 // X's base allows the vector loads: 16 bytes for a float4, 8 for four 16-bit elements
-static inline bool mcl_x_vec_aligned(const mcl_context *c) {
-    return (reinterpret_cast<uintptr_t>(c->X) & (c->x_type == MCL_X_F32 ? 15 : 7)) == 0;
+static inline bool mcl_x_vec_aligned(const void *X, int x_type) {
+    return (reinterpret_cast<uintptr_t>(X) & (x_type == MCL_X_F32 ? 15 : 7)) == 0;
 }
+static inline bool mcl_x_vec_aligned(const mcl_context *c) { return mcl_x_vec_aligned(c->X, c->x_type); }
 // kernel_variant strings: "k_name<ARGS>" for fp32, "k_name_h<bf16,ARGS>" / "k_name_h<f16,ARGS>" for the twins
 template <class XL>
 static inline const char *mcl_x_kname() { return std::is_same_v<XL, XF32> ? "" : "_h"; }
