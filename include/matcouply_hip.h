@@ -351,6 +351,18 @@ int mcl_multistart_run(const void *X, int32_t x_type, const int64_t *row_ptr, in
                        const mcl_multistart_options *opt, int32_t n_starts, double *state, double *diag, int32_t *n_iter, int32_t *stop,
                        void *workspace, int64_t workspace_bytes, void *hip_stream);
 const char *mcl_multistart_last_error(void);
+/* A grid of penalty strengths x random starts in the same launch (cmf_aoadmm_grid): options is a HOST array of n_jobs entries,
+ * uploaded to the workspace; job s = workgroup s runs with options[s] on state slice s and writes diag slice s, n_iter[s] and
+ * stop[s] as a start of mcl_multistart_run does.  All jobs share X, row_ptr, rank and ONE state layout: n_regs, the kind and
+ * non_negativity of every penalty, constant_A/B and update_A/B/C must be equal in all jobs (else an error); p0 / p1,
+ * l2_penalty, feasibility_penalty_scale, the tolerances, inner_n_iter_max, n_iter_max and evaluate_loss_always may differ.
+ * diag: fp64 [n_jobs, max_s options[s].n_iter_max + 1, MCL_MS_DIAG]; job s fills its first options[s].n_iter_max + 1 rows.
+ * A job's result does not depend on n_jobs, on its neighbours or on their options. */
+int64_t mcl_multistart_grid_workspace_bytes(const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank,
+                                            const mcl_multistart_options *options, int32_t n_jobs);
+int mcl_multistart_run_grid(const void *X, int32_t x_type, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank,
+                            const mcl_multistart_options *options, int32_t n_jobs, double *state, double *diag, int32_t *n_iter,
+                            int32_t *stop, void *workspace, int64_t workspace_bytes, void *hip_stream);
 
 /* ---- many random starts of parafac2_als at once (parafac2_als_multistart, csrc/pf2als_multistart.hip) ---------------------- */
 /* One workgroup per start runs the whole unconstrained PARAFAC2-ALS fit of mcl_parafac2_als_typed (projections from the polar

@@ -61,6 +61,7 @@ EXPORTED_SYMBOLS = [
     "mcl_set_problem_typed", "mcl_svd_init_typed",
     "mcl_als_init_workspace_bytes", "mcl_als_init_typed", "mcl_als_init_last_error",
     "mcl_multistart_workspace_bytes", "mcl_multistart_run", "mcl_multistart_last_error",
+    "mcl_multistart_grid_workspace_bytes", "mcl_multistart_run_grid",
     "mcl_parafac2_als_workspace_bytes", "mcl_parafac2_als_typed", "mcl_parafac2_als_last_error",
     "mcl_pf2als_multistart_workspace_bytes", "mcl_pf2als_multistart_run", "mcl_pf2als_multistart_last_error",
 ]
@@ -103,6 +104,7 @@ class MultistartOptions(ctypes.Structure):
 
 MS_DIAG = 4 + 3 * MCL_MAX_REGS  # MCL_MS_DIAG: {rec_error, loss, flags, regularisation, gaps[3][MCL_MAX_REGS]}
 MS_MAX_RANK = 16
+MS_OPTIONS_BYTES = ctypes.sizeof(MultistartOptions)
 
 STOP_RELATIVE, STOP_ABSOLUTE = 1, 2
 VERDICT_FEASIBLE, VERDICT_LOSS_EVALUATED = 1, 2  # flag bits of a verdict row; the stop code sits above them (>> 2)
@@ -190,6 +192,9 @@ def load_library():
         "mcl_multistart_run": (ctypes.c_int, [P, I32, ctypes.POINTER(I64), I64, I64, I32, ctypes.POINTER(MultistartOptions), I32, P, P,
                                               P, P, P, I64, P]),
         "mcl_multistart_last_error": (ctypes.c_char_p, []),
+        "mcl_multistart_grid_workspace_bytes": (I64, [ctypes.POINTER(I64), I64, I64, I32, ctypes.POINTER(MultistartOptions), I32]),
+        "mcl_multistart_run_grid": (ctypes.c_int, [P, I32, ctypes.POINTER(I64), I64, I64, I32, ctypes.POINTER(MultistartOptions), I32,
+                                                   P, P, P, P, P, I64, P]),
         "mcl_parafac2_als_workspace_bytes": (I64, [ctypes.POINTER(I64), I64, I64, I32]),
         "mcl_parafac2_als_typed": (ctypes.c_int, [P, I32, ctypes.POINTER(I64), I64, I64, I32, P, P, P, I32, I32, ctypes.c_double,
                                                   ctypes.c_double, I32, P, P, P, P, P, P, P, I64, P]),
@@ -438,14 +443,15 @@ def multistart_state_len(I, N, K, rank, kinds):
     return n
 
 
-def multistart_run(X, row_ptr, rank, options, state):
-    """Fit state.shape[0] starts of one problem at once (mcl_multistart_run), one workgroup per start.  X packed [sum J_i, K]
-    float32 / bfloat16 / float16 CUDA tensor; options a MultistartOptions; state float64 [n_starts, state_len] CUDA tensor (the
-    layout of matcouply_hip.h), updated in place -> (diag float64 [n_starts, n_iter_max + 1, MS_DIAG], n_iter int32 [n_starts],
-    stop int32 [n_starts]) on the device."""
+def multistart_scratch_len(I, N, K, rank):
+    """doubles of one job's scratch slice in mcl_multistart_run / mcl_multistart_run_grid (csrc/multistart.hip, ms_scratch)"""
+    r, al = rank, lambda n: (n + 31) & ~31
+    return (2 * al(N * r) + al(K * r) + 4 * al(I * r * r) + 2 * al(I) + 2 * al(I * r) + al(8 * r * r + 64))
+
+
+def _multistart_launch(X, row_ptr, rank, options, n_options, state, workspace_bytes, run):
     import torch
 
-    lib = load_library()
     xt = x_type_of(X.dtype)
     if not (X.is_cuda and X.is_contiguous()):
         raise EngineError("X must be a contiguous CUDA tensor")
@@ -454,24 +460,46 @@ def multistart_run(X, row_ptr, rank, options, state):
     row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int64)
     I, K = len(row_ptr) - 1, int(X.shape[1])
     S = int(state.shape[0])
+    if n_options is not None and n_options != S:
+        raise EngineError(f"{n_options} options for {S} state slices")
+    opt = options if n_options is not None else ctypes.byref(options)
     rp = row_ptr.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
-    nbytes = lib.mcl_multistart_workspace_bytes(rp, I, K, int(rank), ctypes.byref(options), S)
+    nbytes = workspace_bytes(rp, I, K, int(rank), opt, S)
     if nbytes < 0:
-        lib.mcl_multistart_run(None, xt, rp, I, K, int(rank), ctypes.byref(options), S, None, None, None, None, None, 0, None)
-        raise EngineError(lib.mcl_multistart_last_error().decode())
+        run(None, xt, rp, I, K, int(rank), opt, S, None, None, None, None, None, 0, None)
+        raise EngineError(load_library().mcl_multistart_last_error().decode())
     ws = torch.empty(int(nbytes) + 256, dtype=torch.uint8, device=X.device)
     off = (-ws.data_ptr()) % 256
-    diag = torch.zeros((S, int(options.n_iter_max) + 1, MS_DIAG), dtype=torch.float64, device=X.device)
+    n_iter_most = int(options.n_iter_max) if n_options is None else max(int(o.n_iter_max) for o in options)
+    diag = torch.zeros((S, n_iter_most + 1, MS_DIAG), dtype=torch.float64, device=X.device)
     n_iter = torch.zeros(S, dtype=torch.int32, device=X.device)
     stop = torch.zeros(S, dtype=torch.int32, device=X.device)
     with torch.cuda.device(X.device):
         stream = torch.cuda.current_stream(X.device).cuda_stream
-        rc = lib.mcl_multistart_run(X.data_ptr(), xt, rp, I, K, int(rank), ctypes.byref(options), S, state.data_ptr(),
-                                    diag.data_ptr(), n_iter.data_ptr(), stop.data_ptr(), ws.data_ptr() + off, nbytes,
-                                    ctypes.c_void_p(stream))
+        rc = run(X.data_ptr(), xt, rp, I, K, int(rank), opt, S, state.data_ptr(), diag.data_ptr(), n_iter.data_ptr(),
+                 stop.data_ptr(), ws.data_ptr() + off, nbytes, ctypes.c_void_p(stream))
     if rc != 0:
-        raise EngineError(lib.mcl_multistart_last_error().decode())
+        raise EngineError(load_library().mcl_multistart_last_error().decode())
     return diag, n_iter, stop
+
+
+def multistart_run(X, row_ptr, rank, options, state):
+    """Fit state.shape[0] starts of one problem at once (mcl_multistart_run), one workgroup per start.  X packed [sum J_i, K]
+    float32 / bfloat16 / float16 CUDA tensor; options a MultistartOptions; state float64 [n_starts, state_len] CUDA tensor (the
+    layout of matcouply_hip.h), updated in place -> (diag float64 [n_starts, n_iter_max + 1, MS_DIAG], n_iter int32 [n_starts],
+    stop int32 [n_starts]) on the device."""
+    lib = load_library()
+    return _multistart_launch(X, row_ptr, rank, options, None, state, lib.mcl_multistart_workspace_bytes, lib.mcl_multistart_run)
+
+
+def multistart_run_grid(X, row_ptr, rank, options, state):
+    """multistart_run with options of its own for every state slice (mcl_multistart_run_grid): `options` is a sequence of
+    state.shape[0] MultistartOptions that agree in everything the state layout follows from (matcouply_hip.h) -> (diag float64
+    [n_jobs, max n_iter_max + 1, MS_DIAG], n_iter, stop); job s fills the first options[s].n_iter_max + 1 rows of diag[s]."""
+    lib = load_library()
+    array = (MultistartOptions * len(options))(*options)
+    return _multistart_launch(X, row_ptr, rank, array, len(options), state, lib.mcl_multistart_grid_workspace_bytes,
+                              lib.mcl_multistart_run_grid)
 
 
 class NativeReg:

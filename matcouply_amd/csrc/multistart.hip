@@ -21,6 +21,10 @@
 // Memory: X, row_ptr and the row -> slab map are shared.  Each start owns a slice of `state` (factors, aux, duals: the caller's
 // layout, matcouply_hip.h) and a slice of the scratch workspace (right-hand sides, inverses, X C, ...), all fp64.  At the sizes
 // this serves, the slices stay in L2 / MALL.
+//
+// cmf_aoadmm_grid: the same launch with options of its own for every workgroup (mcl_multistart_run_grid).  The workgroup copies
+// jobs[blockIdx.x] over the options of its LDS copy of the arguments, which is where every helper reads them; the jobs share X
+// and one state layout (ms_check_grid), everything else - strengths, tolerances, iteration limits - is per job.
 #include <algorithm>
 #include <cmath>
 #include <string>
@@ -46,7 +50,9 @@ struct MsArgs {
     int32_t *n_iter, *stop;
     int64_t off_aux[3][MCL_MAX_REGS], off_dual[3][MCL_MAX_REGS], off_delta[3][MCL_MAX_REGS];
     mcl_multistart_options o;
+    const mcl_multistart_options *jobs;  // mcl_multistart_run_grid: options of workgroup s at jobs[s]; NULL: `o` for all
 };
+static_assert(sizeof(mcl_multistart_options) % sizeof(int32_t) == 0, "the options are copied to LDS word by word");
 
 // scratch of one start, in doubles
 struct MsScratch {
@@ -593,8 +599,14 @@ __global__ __launch_bounds__(MS_THREADS) void k_multistart(MsArgs a0) {
     __shared__ MsArgs sa;  // the arguments in LDS: the helpers keep a reference to them (no private copy of the kernarg)
     if (threadIdx.x == 0) sa = a0;
     __syncthreads();
-    const MsArgs &a = sa;
     const int64_t s = blockIdx.x;
+    if (a0.jobs) {  // a grid: this workgroup's own options replace the shared ones (uniform branch: a0 is the kernarg)
+        const int32_t *src = reinterpret_cast<const int32_t *>(a0.jobs + s);
+        int32_t *dst = reinterpret_cast<int32_t *>(&sa.o);
+        for (int e = threadIdx.x; e < (int)(sizeof(mcl_multistart_options) / sizeof(int32_t)); e += MS_THREADS) dst[e] = src[e];
+        __syncthreads();
+    }
+    const MsArgs &a = sa;
     Start<R, XL> st{a, static_cast<const typename XL::T *>(a.X), a.row_ptr, a.slab_of_row, a.I, a.N, a.K};
     st.A = a.state + s * a.state_len;
     st.B = st.A + a.I * R;
@@ -716,6 +728,87 @@ void launch_rank(int rank, const MsArgs &a, int n_starts, hipStream_t s) {
     }
 }
 
+// the options of a grid's jobs in the workspace, behind the plan of mcl_multistart_run
+int64_t ms_jobs_bytes(int32_t n_jobs) { return (int64_t(n_jobs) * (int64_t)sizeof(mcl_multistart_options) + 255) & ~int64_t(255); }
+
+// a grid: every job passes ms_check, and all jobs have ONE state layout and one set of phases (what ms_plan and the kernel's
+// uniform branches follow): the number, kind and non-negativity flag of the penalties, constant_A / B and update_A / B / C
+std::string ms_check_grid(const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank, const mcl_multistart_options *o, int32_t n_jobs) {
+    if (!o || n_jobs < 1) return "need options and n_jobs >= 1";
+    for (int32_t s = 0; s < n_jobs; ++s) {
+        const std::string bad = ms_check(row_ptr, I, K, rank, o + s, n_jobs);
+        if (!bad.empty()) return "job " + std::to_string(s) + ": " + bad;
+        const mcl_multistart_options &a = o[0], &b = o[s];
+        bool same = a.constant_A == b.constant_A && a.constant_B == b.constant_B && a.update_A == b.update_A &&
+                    a.update_B == b.update_B && a.update_C == b.update_C;
+        for (int m = 0; m < 3 && same; ++m) {
+            same = a.n_regs[m] == b.n_regs[m];
+            for (int k = 0; same && k < a.n_regs[m]; ++k)
+                same = a.regs[m][k].kind == b.regs[m][k].kind && a.regs[m][k].non_negativity == b.regs[m][k].non_negativity;
+        }
+        if (!same)
+            return "job " + std::to_string(s) + " differs from job 0 in n_regs, a penalty's kind or non_negativity, constant_A/B or "
+                   "update_A/B/C: the jobs of a grid share one state layout";
+    }
+    return "";
+}
+
+// mcl_multistart_run (per_job false: *opt for every workgroup, passed in the kernarg) and mcl_multistart_run_grid (per_job true:
+// opt[s] for workgroup s, uploaded to the workspace)
+int ms_run(const char *who, const void *X, int32_t x_type, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank,
+           const mcl_multistart_options *opt, int32_t n_starts, bool per_job, double *state, double *diag, int32_t *n_iter,
+           int32_t *stop, void *workspace, int64_t workspace_bytes, void *hip_stream) {
+    auto fail = [who](const std::string &m) {
+        g_ms_error = who + m;
+        return 1;
+    };
+    const std::string bad = per_job ? ms_check_grid(row_ptr, I, K, rank, opt, n_starts) : ms_check(row_ptr, I, K, rank, opt, n_starts);
+    if (!bad.empty()) return fail(bad);
+    if (!X || !state || !diag || !n_iter || !stop || !workspace) return fail("NULL argument");
+    if (x_type != MCL_X_F32 && x_type != MCL_X_BF16 && x_type != MCL_X_F16)
+        return fail("unknown x_type " + std::to_string(x_type) + " (MCL_X_F32 = 0, MCL_X_BF16 = 1, MCL_X_F16 = 2)");
+    const MsPlan p = ms_plan(row_ptr, I, K, rank, opt, n_starts);
+    const int64_t jobs_bytes = per_job ? ms_jobs_bytes(n_starts) : 0;
+    if (workspace_bytes < p.total + jobs_bytes)
+        return fail(per_job ? "workspace too small (mcl_multistart_grid_workspace_bytes)" : "workspace too small (mcl_multistart_workspace_bytes)");
+    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail("workspace must be 256-byte aligned");
+    hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+    char *ws = static_cast<char *>(workspace);
+    std::vector<int32_t> slab(p.N);
+    for (int64_t i = 0; i < I; ++i)
+        for (int64_t j = row_ptr[i]; j < row_ptr[i + 1]; ++j) slab[j] = (int32_t)i;
+    if (hipMemcpyAsync(ws + p.off_rowptr, row_ptr, (I + 1) * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
+        (p.N && hipMemcpyAsync(ws + p.off_slab, slab.data(), p.N * 4, hipMemcpyHostToDevice, s) != hipSuccess) ||
+        (per_job && hipMemcpyAsync(ws + p.total, opt, int64_t(n_starts) * sizeof(mcl_multistart_options), hipMemcpyHostToDevice, s) !=
+                        hipSuccess) ||
+        hipStreamSynchronize(s) != hipSuccess)
+        return fail(per_job ? "upload of row_ptr and the options failed" : "upload of row_ptr failed");
+    int32_t n_iter_most = opt->n_iter_max;  // the diagnostics stride: that of the longest job
+    for (int32_t j = 1; per_job && j < n_starts; ++j) n_iter_most = std::max(n_iter_most, opt[j].n_iter_max);
+    MsArgs a{};
+    a.X = X;
+    a.row_ptr = reinterpret_cast<const int64_t *>(ws + p.off_rowptr);
+    a.slab_of_row = reinterpret_cast<const int32_t *>(ws + p.off_slab);
+    a.I = I, a.N = p.N, a.K = K;
+    a.state_len = p.state_len, a.scratch_len = p.scratch_len;
+    a.diag_stride = int64_t(n_iter_most + 1) * MCL_MS_DIAG;
+    a.state = state, a.scratch = reinterpret_cast<double *>(ws + p.off_scratch), a.diag = diag;
+    a.n_iter = n_iter, a.stop = stop;
+    for (int m = 0; m < 3; ++m)
+        for (int k = 0; k < MCL_MAX_REGS; ++k)
+            a.off_aux[m][k] = p.off_aux[m][k], a.off_dual[m][k] = p.off_dual[m][k], a.off_delta[m][k] = p.off_delta[m][k];
+    a.o = *opt;
+    a.jobs = per_job ? reinterpret_cast<const mcl_multistart_options *>(ws + p.total) : nullptr;
+    mcl_x_dispatch(x_type, [&](auto xl) {
+        using XL = decltype(xl);
+        launch_rank<XL>(rank, a, n_starts, s);
+        return 0;
+    });
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(std::string("launch failed: ") + hipGetErrorString(e));
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -731,48 +824,21 @@ int64_t mcl_multistart_workspace_bytes(const int64_t *row_ptr, int64_t I, int64_
 int mcl_multistart_run(const void *X, int32_t x_type, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank,
                        const mcl_multistart_options *opt, int32_t n_starts, double *state, double *diag, int32_t *n_iter, int32_t *stop,
                        void *workspace, int64_t workspace_bytes, void *hip_stream) {
-    auto fail = [](const std::string &m) {
-        g_ms_error = "mcl_multistart_run: " + m;
-        return 1;
-    };
-    const std::string bad = ms_check(row_ptr, I, K, rank, opt, n_starts);
-    if (!bad.empty()) return fail(bad);
-    if (!X || !state || !diag || !n_iter || !stop || !workspace) return fail("NULL argument");
-    if (x_type != MCL_X_F32 && x_type != MCL_X_BF16 && x_type != MCL_X_F16)
-        return fail("unknown x_type " + std::to_string(x_type) + " (MCL_X_F32 = 0, MCL_X_BF16 = 1, MCL_X_F16 = 2)");
-    const MsPlan p = ms_plan(row_ptr, I, K, rank, opt, n_starts);
-    if (workspace_bytes < p.total) return fail("workspace too small (mcl_multistart_workspace_bytes)");
-    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail("workspace must be 256-byte aligned");
-    hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
-    char *ws = static_cast<char *>(workspace);
-    std::vector<int32_t> slab(p.N);
-    for (int64_t i = 0; i < I; ++i)
-        for (int64_t j = row_ptr[i]; j < row_ptr[i + 1]; ++j) slab[j] = (int32_t)i;
-    if (hipMemcpyAsync(ws + p.off_rowptr, row_ptr, (I + 1) * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
-        (p.N && hipMemcpyAsync(ws + p.off_slab, slab.data(), p.N * 4, hipMemcpyHostToDevice, s) != hipSuccess) ||
-        hipStreamSynchronize(s) != hipSuccess)
-        return fail("upload of row_ptr failed");
-    MsArgs a{};
-    a.X = X;
-    a.row_ptr = reinterpret_cast<const int64_t *>(ws + p.off_rowptr);
-    a.slab_of_row = reinterpret_cast<const int32_t *>(ws + p.off_slab);
-    a.I = I, a.N = p.N, a.K = K;
-    a.state_len = p.state_len, a.scratch_len = p.scratch_len;
-    a.diag_stride = int64_t(opt->n_iter_max + 1) * MCL_MS_DIAG;
-    a.state = state, a.scratch = reinterpret_cast<double *>(ws + p.off_scratch), a.diag = diag;
-    a.n_iter = n_iter, a.stop = stop;
-    for (int m = 0; m < 3; ++m)
-        for (int k = 0; k < MCL_MAX_REGS; ++k)
-            a.off_aux[m][k] = p.off_aux[m][k], a.off_dual[m][k] = p.off_dual[m][k], a.off_delta[m][k] = p.off_delta[m][k];
-    a.o = *opt;
-    mcl_x_dispatch(x_type, [&](auto xl) {
-        using XL = decltype(xl);
-        launch_rank<XL>(rank, a, n_starts, s);
-        return 0;
-    });
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(std::string("launch failed: ") + hipGetErrorString(e));
-    return 0;
+    return ms_run("mcl_multistart_run: ", X, x_type, row_ptr, I, K, rank, opt, n_starts, false, state, diag, n_iter, stop, workspace,
+                  workspace_bytes, hip_stream);
+}
+
+int64_t mcl_multistart_grid_workspace_bytes(const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank,
+                                            const mcl_multistart_options *options, int32_t n_jobs) {
+    if (!ms_check_grid(row_ptr, I, K, rank, options, n_jobs).empty()) return -1;
+    return ms_plan(row_ptr, I, K, rank, options, n_jobs).total + ms_jobs_bytes(n_jobs);
+}
+
+int mcl_multistart_run_grid(const void *X, int32_t x_type, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank,
+                            const mcl_multistart_options *options, int32_t n_jobs, double *state, double *diag, int32_t *n_iter,
+                            int32_t *stop, void *workspace, int64_t workspace_bytes, void *hip_stream) {
+    return ms_run("mcl_multistart_run_grid: ", X, x_type, row_ptr, I, K, rank, options, n_jobs, true, state, diag, n_iter, stop,
+                  workspace, workspace_bytes, hip_stream);
 }
 
 }  // extern "C"

@@ -23,7 +23,8 @@ from ._utils import check_random_state, get_svd, is_iterable, is_tensor, is_torc
 from .coupled_matrices import CoupledMatrixFactorization
 
 __all__ = ["compute_feasibility_gaps", "ADMMVars", "DiagnosticMetrics", "cmf_aoadmm", "parafac2_aoadmm",
-           "PackedMatrices", "partition_slabs", "parafac2_als", "parafac2_als_multistart"]
+           "PackedMatrices", "partition_slabs", "parafac2_als", "parafac2_als_multistart",
+           "cmf_aoadmm_grid", "parafac2_aoadmm_grid", "best_start"]
 
 # TEST-ONLY seam.  The CPU test-suite (tests/oracle_engine.py) substitutes a checker engine here to exercise the host and
 # multi-process logic without a GPU.  The substitution is honoured only under MATCOUPLY_AMD_TEST_ENGINE=1, which
@@ -1889,29 +1890,8 @@ def _multistart_unfused_reason(matrices, rank, kw):
     return None
 
 
-def _multistart_fused(matrices, rank, random_states, kw):
-    device = _device()
-    X, row_ptr = _pack(matrices, device)
-    I, N, K = len(row_ptr) - 1, int(row_ptr[-1]), int(X.shape[1])
-    f32 = lambda a: np.asarray(to_numpy(a), dtype=np.float32).astype(np.float64).ravel()  # cmf_aoadmm keeps its state in fp32
-    vectors, descs = [], None
-    for rs in random_states:
-        cmf, regs, auxes, duals = _start_penalties(kw, matrices, rank, check_random_state(rs))
-        _, (A0, B0_is, C0) = cmf
-        parts = [f32(A0), np.concatenate([f32(b) for b in B0_is]), f32(C0)]
-        for mode in range(3):
-            for aux, dual in zip(auxes[mode], duals[mode]):
-                if isinstance(aux, tuple):  # PARAFAC2: (P_i list, Delta)
-                    parts += [np.concatenate([f32(p) for p in aux[0]]), f32(aux[1])]
-                else:
-                    parts.append(np.concatenate([f32(a) for a in aux]) if mode == 1 else f32(aux))
-                parts.append(np.concatenate([f32(d) for d in dual]) if mode == 1 else f32(dual))
-        vectors.append(np.concatenate(parts))
-        descs = [[penalties.native_descriptor_of(r) for r in regs[m]] for m in range(3)]
-    kinds = [[d[0] for d in descs[m]] for m in range(3)]
-    L = _engine.multistart_state_len(I, N, K, rank, kinds)
-    assert all(v.size == L for v in vectors), "multistart: state layout mismatch"
-
+def _multistart_options(kw, descs):
+    """the mcl_multistart_options of one fit: `kw` the complete cmf_aoadmm keywords, `descs` the native descriptors per mode"""
     o = _engine.MultistartOptions()
     for mode in range(3):
         o.n_regs[mode] = len(descs[mode])
@@ -1924,15 +1904,52 @@ def _multistart_fused(matrices, rank, random_states, kw):
     o.feasibility_penalty_scale = float(kw["feasibility_penalty_scale"])
     o.inner_tol = float(kw["inner_tol"]) if kw["inner_tol"] and kw["inner_tol"] > 0 else 0.0
     o.inner_n_iter_max = int(kw["inner_n_iter_max"])
-    tol, absolute_tol, feasibility_tol = kw["tol"], kw["absolute_tol"], kw["feasibility_tol"]
-    o.tol, o.absolute_tol, o.feasibility_tol = float(tol or 0), float(absolute_tol or 0), float(feasibility_tol or 0)
+    o.tol, o.absolute_tol = float(kw["tol"] or 0), float(kw["absolute_tol"] or 0)
+    o.feasibility_tol = float(kw["feasibility_tol"] or 0)
     o.constant_A, o.constant_B = _constant_flags(kw["constant_feasibility_penalty"])
     o.update_A, o.update_B, o.update_C = bool(kw["update_A"]), bool(kw["update_B_is"]), bool(kw["update_C"])
     o.evaluate_loss_always = bool(kw["return_errors"])
     o.n_iter_max = max(int(kw["n_iter_max"]), 0)
+    return o
+
+
+def _multistart_fused(matrices, rank, random_states, kws, per_job_options=False):
+    """every keyword set of `kws` (complete cmf_aoadmm keywords with one state layout) from every start, in one launch: job
+    g * len(random_states) + s is kws[g] from random_states[s].  One set with per_job_options False is cmf_aoadmm_multistart
+    (mcl_multistart_run, the options in the kernel's arguments); cmf_aoadmm_grid gives every job options of its own
+    (mcl_multistart_run_grid).  `kws` and `random_states` are not empty."""
+    device = _device()
+    X, row_ptr = _pack(matrices, device)
+    I, N, K = len(row_ptr) - 1, int(row_ptr[-1]), int(X.shape[1])
+    f32 = lambda a: np.asarray(to_numpy(a), dtype=np.float32).astype(np.float64).ravel()  # cmf_aoadmm keeps its state in fp32
+    vectors, job_kw, job_options, kinds = [], [], [], None
+    for kw in kws:
+        for rs in random_states:
+            cmf, regs, auxes, duals = _start_penalties(kw, matrices, rank, check_random_state(rs))
+            _, (A0, B0_is, C0) = cmf
+            parts = [f32(A0), np.concatenate([f32(b) for b in B0_is]), f32(C0)]
+            for mode in range(3):
+                for aux, dual in zip(auxes[mode], duals[mode]):
+                    if isinstance(aux, tuple):  # PARAFAC2: (P_i list, Delta)
+                        parts += [np.concatenate([f32(p) for p in aux[0]]), f32(aux[1])]
+                    else:
+                        parts.append(np.concatenate([f32(a) for a in aux]) if mode == 1 else f32(aux))
+                    parts.append(np.concatenate([f32(d) for d in dual]) if mode == 1 else f32(dual))
+            vectors.append(np.concatenate(parts))
+            descs = [[penalties.native_descriptor_of(r) for r in regs[m]] for m in range(3)]
+            job_kw.append(kw)
+        job_options += [_multistart_options(kw, descs)] * len(random_states)
+        assert kinds in (None, [[d[0] for d in descs[m]] for m in range(3)]), "multistart: the jobs differ in their state layout"
+        kinds = [[d[0] for d in descs[m]] for m in range(3)]
+    L = _engine.multistart_state_len(I, N, K, rank, kinds)
+    assert all(v.size == L for v in vectors), "multistart: state layout mismatch"
 
     state = torch.from_numpy(np.stack(vectors)).to(device)
-    diag, n_iter, stop = _engine.multistart_run(X, row_ptr, rank, o, state)
+    if per_job_options:
+        diag, n_iter, stop = _engine.multistart_run_grid(X, row_ptr, rank, job_options, state)
+    else:
+        assert len(kws) == 1
+        diag, n_iter, stop = _engine.multistart_run(X, row_ptr, rank, job_options[0], state)
     diag, n_iter, stop = diag.cpu().numpy(), n_iter.cpu().numpy(), stop.cpu().numpy()
 
     out = _Out(matrices)
@@ -1940,6 +1957,8 @@ def _multistart_fused(matrices, rank, random_states, kw):
     results = []
     for s in range(len(vectors)):
         st = state[s]
+        kw = job_kw[s]
+        tol, absolute_tol, feasibility_tol = kw["tol"], kw["absolute_tol"], kw["feasibility_tol"]
         pos = 0
 
         def nxt(n_rows, cols=rank):
@@ -2011,7 +2030,7 @@ def cmf_aoadmm_multistart(matrices, rank, random_states, *, method="auto", **cmf
             if n_el > _MULTISTART_AUTO_ANY_N:
                 reason = f"{len(random_states)} starts of {n_el} elements run faster one by one"
         if reason is None:
-            return _multistart_fused(matrices, rank, random_states, kw) if random_states else []
+            return _multistart_fused(matrices, rank, random_states, [kw]) if random_states else []
         if method == "fused":
             raise NotImplementedError(f"cmf_aoadmm_multistart(method=\"fused\"): {reason}")
     return [cmf_aoadmm(matrices, rank, random_state=rs, **cmf_aoadmm_kwargs) for rs in random_states]
@@ -2025,6 +2044,166 @@ def parafac2_aoadmm_multistart(matrices, rank, random_states, *, method="auto", 
     kwargs = dict(parafac2_aoadmm_kwargs)
     kwargs.setdefault("l2_penalty", 0)
     return cmf_aoadmm_multistart(matrices, rank, random_states, method=method, parafac2=True, **kwargs)
+
+
+# ------------------------------------------------------------------------------------------------------------
+# a grid of penalty strengths x random starts: the loop users write around the multi-start one
+# ------------------------------------------------------------------------------------------------------------
+# keywords that decide the shape of the result or are not options of one fit: common to the whole grid only
+_GRID_COMMON_ONLY = ("return_errors", "return_admm_vars", "verbose", "group")
+# device memory a fused grid may ask for (state, scratch, diagnostics and options of all jobs).  A Cartesian product grows
+# quickly, and every job holds its slices for the whole launch although only a few hundred workgroups are resident at a time.
+# 8 GiB is 1 / 36 of the MI355X's 288 GB and leaves the rest to the process's other tensors; it holds ~50 000 jobs of the
+# examples' size with 1000 iterations of diagnostics (~165 kB each) and ~1300 of 64 x 64 x 64 at rank 16 with four penalties
+# per mode (~6.5 MB each).  A larger grid runs as several calls
+_GRID_MAX_BYTES = 1 << 33
+
+
+def _grid_keywords(name, param_grid, common):
+    """the grid's keyword sets: [(point, point merged into the common keywords as complete cmf_aoadmm keywords)], checked"""
+    def check(kwargs, where):
+        if "random_state" in kwargs:
+            raise TypeError(f"{name} takes random_states, not random_state{where}")
+        init = kwargs.get("init", "random")
+        if not (isinstance(init, str) and init == "random"):
+            raise ValueError(f"{name} needs init=\"random\" (init={init!r}{where} gives the same start every time)")
+
+    check(common, "")
+    points = []
+    for g, point in enumerate(param_grid):
+        if not isinstance(point, dict):
+            raise TypeError(f"{name}: param_grid[{g}] is a {type(point).__name__}, not a dict of cmf_aoadmm keywords")
+        check(point, f" in param_grid[{g}]")
+        for key in point:
+            if key in _GRID_COMMON_ONLY:
+                raise ValueError(f"{name}: {key!r} in param_grid[{g}] is not an option of one fit; pass it once for the whole grid")
+            if key in common:
+                raise TypeError(f"{name} got {key!r} both in param_grid[{g}] and as a common keyword")
+        points.append((point, _cmf_kwargs({**common, **point})))
+    return points
+
+
+def _multistart_layout(matrices, rank, kw):
+    """what the state layout and the phases of the fused kernel follow from, per mode: the (kind, non-negativity) of every
+    penalty in order and whether the mode is updated; plus the constant-feasibility-penalty flags"""
+    _, regs, _, _ = _start_penalties(kw, matrices, rank, np.random.RandomState(0))
+    names = {_engine.PEN_NN: "NonNegativity", _engine.PEN_BOX: "Box", _engine.PEN_L1: "L1Penalty", _engine.PEN_L2BALL: "L2Ball",
+             _engine.PEN_PARAFAC2: "Parafac2"}
+    modes = []
+    for mode, updated in enumerate((kw["update_A"], kw["update_B_is"], kw["update_C"])):
+        descs = [penalties.native_descriptor_of(reg) for reg in regs[mode]]
+        modes.append((tuple(names[d[0]] + ("(non_negativity)" if d[1] and d[0] != _engine.PEN_NN else "") for d in descs),
+                      "updated" if updated else "not updated"))
+    return modes, _constant_flags(kw["constant_feasibility_penalty"])
+
+
+def _grid_unfused_reason(matrices, rank, kws, n_starts):
+    """why the fused kernel cannot run this grid in one launch (a sentence), or None.  No device call."""
+    for g, kw in enumerate(kws):
+        reason = _multistart_unfused_reason(matrices, rank, kw)
+        if reason is not None:
+            return f"grid point {g}: {reason}"
+    first = _multistart_layout(matrices, rank, kws[0])
+    for g, kw in enumerate(kws[1:], 1):
+        modes, constant = _multistart_layout(matrices, rank, kw)
+        for mode in range(3):
+            if modes[mode] != first[0][mode]:
+                return (f"grid point {g} has the penalties {list(modes[mode][0])} ({modes[mode][1]}) on mode {mode}, grid point 0 "
+                        f"{list(first[0][mode][0])} ({first[0][mode][1]}): one launch holds one state layout (a strength of 0 or "
+                        "None drops its penalty)")
+        if constant != first[1]:
+            return f"grid point {g} differs from grid point 0 in constant_feasibility_penalty"
+    rows = [int(shape(matrices[i])[0]) for i in range(len(matrices))]
+    I, N, K = len(rows), sum(rows), int(shape(matrices[0])[1])
+    n_pen = [[2 * n + (rank if name == "Parafac2" else 0) for name in first[0][m][0]] for m, n in enumerate((I, N, K))]
+    state_len = (I + N + K + sum(sum(p) for p in n_pen)) * rank
+    diag_len = (max(max(int(kw["n_iter_max"]), 0) for kw in kws) + 1) * _engine.MS_DIAG
+    per_job = 8 * (state_len + _engine.multistart_scratch_len(I, N, K, rank) + diag_len) + _engine.MS_OPTIONS_BYTES
+    n_jobs = len(kws) * n_starts
+    if n_jobs * per_job > _GRID_MAX_BYTES or n_jobs >= 1 << 31:
+        return (f"{n_jobs} jobs of {per_job} bytes each (state, scratch, diagnostics) need more than the {_GRID_MAX_BYTES} bytes "
+                "a fused grid may take; split the grid")
+    return None
+
+
+def cmf_aoadmm_grid(matrices, rank, param_grid, random_states, *, method="auto", **cmf_aoadmm_kwargs):
+    """Fit the same data over a grid of option values, every grid point from several random starts: ``result[g][s]`` is what
+    ``cmf_aoadmm(matrices, rank, random_state=random_states[s], **cmf_aoadmm_kwargs, **param_grid[g])`` returns (same tuple
+    structure, array types and dtypes, as for a start of :func:`cmf_aoadmm_multistart`).  ``param_grid`` is a sequence of dicts
+    of ``cmf_aoadmm`` keywords, one per grid point (``itertools.product`` builds a Cartesian one); a keyword stands either in
+    the grid points or among the common ones (``TypeError`` for both), and ``return_errors``, ``return_admm_vars``,
+    ``verbose`` and ``group`` are common only (``ValueError``).  An empty grid gives ``[]``.  :func:`best_start` picks a grid
+    point's start by the examples' rule.  Random-state objects among ``random_states`` (rather than seeds) are drawn from
+    grid point by grid point, in the order of the sequential method.
+
+    ``method="sequential"`` calls ``cmf_aoadmm`` once per grid point and start (every option).  ``method="fused"`` fits all
+    ``len(param_grid) * len(random_states)`` jobs in one launch of the kernel of :func:`cmf_aoadmm_multistart`, one workgroup
+    per job with options of its own (mcl_multistart_run_grid).  It serves what ``cmf_aoadmm_multistart(method="fused")`` serves
+    for every grid point, and needs all grid points to parse to the same penalty classes, non-negativity flags and order on
+    every mode, the same ``update_*`` and the same ``constant_feasibility_penalty``: the jobs share one state layout.  The
+    strengths, bounds, ``l2_penalty``, ``feasibility_penalty_scale``, tolerances and iteration limits may differ.  A strength of
+    0 or ``None`` drops its penalty when the keywords are parsed, so ``l1_penalty=0`` beside ``0.1`` is two layouts.  A grid
+    whose jobs need more than ``_GRID_MAX_BYTES`` of device memory is not served either.  Each of these raises
+    ``NotImplementedError`` naming the grid point, before the device is touched.  ``method="auto"`` takes the fused kernel when
+    it serves the call and the jobs are many or small enough (the rule of ``cmf_aoadmm_multistart`` on the number of jobs),
+    else the sequential loop.  A job's result does not depend on the grid it is part of.
+    """
+    return _aoadmm_grid("cmf_aoadmm_grid", matrices, rank, param_grid, random_states, method, cmf_aoadmm_kwargs)
+
+
+def _aoadmm_grid(name, matrices, rank, param_grid, random_states, method, common):
+    if method not in ("auto", "fused", "sequential"):
+        raise ValueError(f'method must be "auto", "fused" or "sequential", not {method!r}')
+    points = _grid_keywords(name, list(param_grid), common)
+    random_states = list(random_states)
+    if not points:
+        return []
+    if not random_states:
+        return [[] for _ in points]
+    if method != "sequential":
+        kws = [kw for _, kw in points]
+        n_jobs = len(kws) * len(random_states)
+        reason = _grid_unfused_reason(matrices, rank, kws, len(random_states))
+        if reason is None and method == "auto" and n_jobs < _MULTISTART_AUTO_MIN_N:
+            n_el = sum(int(shape(matrices[i])[0]) for i in range(len(matrices))) * int(shape(matrices[0])[1])
+            if n_el > _MULTISTART_AUTO_ANY_N:
+                reason = f"{n_jobs} jobs of {n_el} elements run faster one by one"
+        if reason is None:
+            flat = _multistart_fused(matrices, rank, random_states, kws, per_job_options=True)
+            n = len(random_states)
+            return [flat[g * n: (g + 1) * n] for g in range(len(kws))]
+        if method == "fused":
+            raise NotImplementedError(f"{name}(method=\"fused\"): {reason}")
+    return [[cmf_aoadmm(matrices, rank, random_state=rs, **common, **point) for rs in random_states] for point, _ in points]
+
+
+def parafac2_aoadmm_grid(matrices, rank, param_grid, random_states, *, method="auto", **parafac2_aoadmm_kwargs):
+    """:func:`cmf_aoadmm_grid` with the PARAFAC2 constraint on mode 1: ``result[g][s]`` is what ``parafac2_aoadmm(matrices, rank,
+    random_state=random_states[s], **parafac2_aoadmm_kwargs, **param_grid[g])`` returns."""
+    param_grid = list(param_grid)
+    if "parafac2" in parafac2_aoadmm_kwargs or any(isinstance(p, dict) and "parafac2" in p for p in param_grid):
+        raise TypeError("parafac2_aoadmm_grid() got an unexpected keyword argument 'parafac2'")
+    common = dict(parafac2_aoadmm_kwargs, parafac2=True)
+    if not any(isinstance(p, dict) and "l2_penalty" in p for p in param_grid):
+        common.setdefault("l2_penalty", 0)  # the default of parafac2_aoadmm
+    else:
+        param_grid = [p if not isinstance(p, dict) or "l2_penalty" in p or "l2_penalty" in common else dict(p, l2_penalty=0)
+                      for p in param_grid]
+    return _aoadmm_grid("parafac2_aoadmm_grid", matrices, rank, param_grid, random_states, method, common)
+
+
+def best_start(results):
+    """The examples' selection among the starts of one grid point (or of :func:`cmf_aoadmm_multistart`), fitted with
+    ``return_errors=True``: the index of the lowest ``regularized_loss[-1]`` among the starts with
+    ``satisfied_stopping_condition`` (the first of equal ones), or ``None`` when no start satisfied it."""
+    best, best_loss = None, None
+    for s, result in enumerate(results):
+        diag = next((x for x in result if isinstance(x, DiagnosticMetrics)), None) if isinstance(result, tuple) else None
+        if diag is None:
+            raise ValueError("best_start needs results fitted with return_errors=True")
+        if diag.satisfied_stopping_condition and (best is None or diag.regularized_loss[-1] < best_loss):
+            best, best_loss = s, diag.regularized_loss[-1]
+    return best
 
 
 # ------------------------------------------------------------------------------------------------------------
