@@ -14,7 +14,9 @@ all-reduced over the group (RCCL on MI355X, gloo in the CPU tests).
 from copy import copy
 import inspect
 import os
+from types import SimpleNamespace
 from typing import NamedTuple, Optional
+import warnings
 
 import numpy as np
 
@@ -202,24 +204,18 @@ def initialize_cmf(matrices, rank, init, svd_fun, random_state=None, init_params
         B, C, info = _engine.svd_init(X, row_ptr, rank, threshold=(init == "threshold_svd"))
         info_min = int(info.min().item())
         if info_min <= -1000:
-            import warnings
-
             warnings.warn("svd initialisation on the device: a matrix has numerical rank below `rank` (its trailing singular "
                           "vectors are not determined by the data); taking the host (LAPACK) path, which completes the basis",
                           RuntimeWarning)
         else:
             if info_min < 0:
-                import warnings
-
-                warnings.warn("svd initialisation on the device: the subspace iteration of some matrices had not settled after 400 "
+                    warnings.warn("svd initialisation on the device: the subspace iteration of some matrices had not settled after 400 "
                               "iterations (no gap behind the leading singular values); the vectors are approximate", RuntimeWarning)
             A = torch.ones((len(row_ptr) - 1, rank), dtype=torch.float32, device=X.device)
             B_is = [B[int(row_ptr[i]): int(row_ptr[i + 1])] for i in range(len(row_ptr) - 1)]
             return CoupledMatrixFactorization((None, [A, B_is, C]))
     if init == "svd" or init == "threshold_svd":
         # one-off set-up on the host (decomposition.py:42-53)
-        from ._utils import to_numpy
-
         if svd_fun is None:
             svd_fun = get_svd("truncated_svd")
         mats = [np.asarray(to_numpy(m.float() if is_torch(m) and m.dtype == torch.bfloat16 else m), dtype=np.float64)
@@ -467,6 +463,13 @@ class _StopRule:
 
     def feasible(self, gaps):
         return self.feasibility_tol and _check_feasibility(gaps, self.feasibility_tol)
+
+    @classmethod
+    def message_of(cls, code):
+        """the message of a stop code of the device rules (0: no criterion fired)"""
+        if not code:
+            return cls.EXHAUSTED
+        return cls.RELATIVE if code == _engine.STOP_RELATIVE else cls.ABSOLUTE
 
     def verdict(self, feasible, losses):
         """message of the criterion that fires on the last two losses, or None"""
@@ -778,8 +781,743 @@ def _direct_comm(group, device=None):
 
 
 # ------------------------------------------------------------------------------------------------------------
-# the solver
+# the solver in parts (collectives, penalties on the device, phases and diagnostics, arithmetic rule, outer loops) and whole
 # ------------------------------------------------------------------------------------------------------------
+class _Group:
+    """The ranks of one run and their collectives.  `direct` is the cached RCCL communicator of the group (_direct_comm: the
+    collectives go straight onto the engine's stream, no stream hand-over), set by the caller once the engine exists; None - any
+    other backend (gloo in the CPU tests), or a failed self-test - takes torch.distributed's.  A run without `group=` is the
+    same object with one rank, whose all_reduce returns at once."""
+
+    def __init__(self, group=None):
+        self.group, self.dist, self.direct, self.world, self.rank = group, None, None, 1, 0
+        if group is not None:
+            import torch.distributed as dist
+
+            self.dist, self.world, self.rank = dist, dist.get_world_size(group), dist.get_rank(group)
+        # the sharded code path (step calls with the reductions in between): taken with more than one rank - and, for
+        # rehearsals of that path on a single-GPU box, with a one-rank group when MCL_FORCE_SHARDED_PATH=1
+        self.sharded = self.world > 1 or (group is not None and os.environ.get("MCL_FORCE_SHARDED_PATH") == "1")
+        self.counts = {}  # rows per rank of every gathered array, by name (exchanged at the first gather of that name)
+
+    def all_reduce(self, t, op="sum"):
+        if not self.sharded:
+            return
+        if (self.direct is not None and is_torch(t) and t.is_cuda and t.device == self.direct.device
+                and t.dtype in (torch.float32, torch.float64) and t.is_contiguous()):
+            self.direct.all_reduce(t, op)
+        else:
+            self.dist.all_reduce(t, op=(self.dist.ReduceOp.MAX if op == "max" else self.dist.ReduceOp.SUM), group=self.group)
+
+    def gather_rows(self, t, key):
+        """every rank's rows of `t` (a vector or a matrix), in rank order, as a list.  The shares are uneven: the counts are
+        exchanged once per `key`, the rows padded to the largest share for the collective and trimmed after."""
+        counts = self.counts.get(key)
+        if counts is None:
+            n_loc = torch.tensor([t.shape[0]], dtype=torch.int64, device=t.device)
+            cnt = [torch.zeros_like(n_loc) for _ in range(self.world)]
+            self.dist.all_gather(cnt, n_loc, group=self.group)
+            counts = self.counts[key] = [int(c.item()) for c in cnt]
+        padded = torch.zeros((max(counts),) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
+        padded[: t.shape[0]] = t
+        parts = [torch.empty_like(padded) for _ in range(self.world)]
+        self.dist.all_gather(parts, padded, group=self.group)
+        return [p[:c] for p, c in zip(parts, counts)]
+
+    def own_rows(self, key):
+        """(lo, hi): where this rank's rows lie among the gathered rows of `key`"""
+        lo = sum(self.counts[key][:self.rank])
+        return lo, lo + self.counts[key][self.rank]
+
+
+def _native_penalties(regs, auxes, duals, matrices, device, host_only, has_group):
+    """The penalties as the engine sees them: (native, ext_aux), native[mode][k] an _engine.NativeReg with the auxiliary and dual
+    variable on the device.  Host-evaluated penalties (no native kernel; all of them with `host_only`; a generalised L2 norm
+    matrix that does not fit the mode) are PEN_EXTERNAL: the Python object keeps the auxiliary variable in ITS parametrisation
+    (on the device) in ext_aux[(mode, k)], the engine sees `aux_as_matrix` of it (reference penalties.py:311-343)."""
+    native, ext_aux = [[], [], []], {}
+    for mode in range(3):
+        for k, (reg, aux, dual) in enumerate(zip(regs[mode], auxes[mode], duals[mode])):
+            desc = None if host_only else penalties.native_descriptor_of(reg)
+            gl2_matrix = None
+            if desc is not None and desc[0] == _engine.PEN_GL2:
+                # every matrix of the mode must have as many rows as the norm matrix (anything else fails in the reference's
+                # product too: left to the penalty's own method); a sharded A holds only this rank's rows of the I x I problem
+                gl2_matrix, n_gl2 = reg._native_matrix()
+                rows_m = [shape(m_)[0] for m_ in matrices] if mode == 1 else [len(matrices) if mode == 0 else shape(matrices[0])[1]]
+                if any(rw != n_gl2 for rw in rows_m) or (has_group and mode == 0):
+                    desc = None
+            dual_t = _pack_rows(dual, device) if mode == 1 else _to_dev(dual, device)
+            if desc is None:
+                obj = _aux_to_device(aux, device)
+                mat = _pack_rows(reg.auxes_as_matrices(obj), device) if mode == 1 else _to_dev(reg.aux_as_matrix(obj), device)
+                ext_aux[(mode, k)] = obj
+                native[mode].append(_engine.NativeReg(_engine.PEN_EXTERNAL, mat, dual_t))
+                continue
+            kind, nonneg, p0, p1 = desc
+            if kind == _engine.PEN_PARAFAC2:
+                P_is, Delta = aux
+                native[mode].append(_engine.NativeReg(kind, _pack_rows(P_is, device), dual_t, aux2=_to_dev(Delta, device)))
+            else:
+                aux_t = _pack_rows(aux, device) if mode == 1 else _to_dev(aux, device)
+                extra = {}
+                if kind == _engine.PEN_GL2:
+                    extra = dict(matrix=torch.as_tensor(gl2_matrix, dtype=torch.float64, device=device).contiguous(), matrix_rows=n_gl2)
+                native[mode].append(_engine.NativeReg(kind, aux_t, dual_t, non_negativity=nonneg, p0=p0, p1=p1, **extra))
+    return native, ext_aux
+
+
+def _diag_slot(mode, k):
+    """where penalty k of a mode sits in the diagnostics vector: its squared feasibility gap there, its value in the next slot"""
+    return _engine.DIAG_REG + (mode * _engine.MCL_MAX_REGS + k) * 2
+
+
+def _local_on_A(nat, reg):
+    """a penalty on mode 0 that acts on each row of A by itself: needs nothing from the other ranks"""
+    return nat.kind in (_engine.PEN_NN, _engine.PEN_BOX, _engine.PEN_L1) or (
+        nat.kind == _engine.PEN_EXTERNAL and isinstance(reg, penalties.RowVectorPenalty))
+
+
+class _Run:
+    """One fit on its engine: the B, C and A phase of an outer iteration - native calls where the engine serves the whole phase,
+    stepped ones with the reductions and the host-evaluated proxes in between where it does not - and the diagnostics.
+    `opt`: the scalar options of the cmf_aoadmm call."""
+
+    def __init__(self, eng, regs, native, ext_aux, grp, row_ptr, device, opt):
+        self.eng, self.regs, self.native, self.ext_aux, self.grp, self.device, self.opt = eng, regs, native, ext_aux, grp, device, opt
+        self.updates = (opt.update_A, opt.update_B_is, opt.update_C)
+        # inner_tol > 0 (early exit of the inner ADMM loops, decomposition.py:90-117) needs a convergence test after every
+        # inner iteration.  Single-device runs: the ENGINE evaluates it (mcl_options.inner_tol: one launch per step, a device-side
+        # flag the remaining inner launches test; native prox kernels stay native, no host synchronisation).  Sharded runs (the
+        # norms must be all-reduced over the ranks) and the CPU checker keep the step path: native solves, every prox through
+        # the penalty objects' own methods on device tensors, the test on the host
+        self.check_inner = bool(opt.inner_tol) and opt.inner_tol > 0
+        sharded = grp.sharded
+        self.has_ext = [any(r.kind == _engine.PEN_EXTERNAL for r in native[m]) for m in range(3)]
+        self.needs_B_steps = (sharded and (opt.constant_B or any(r.kind == _engine.PEN_PARAFAC2 for r in native[1]))) or self.has_ext[1]
+        # mode 0 under sharding: the rows of A live on different ranks.  Row-separable penalties need nothing; an L2 ball
+        # (the README case: l2_norm_bound on A with a constant feasibility penalty) needs the r column sums of squares of
+        # A + U all-reduced in every inner iteration (SURVEY.md 8e item 3)
+        self.sharded_ball_A = sharded and any(r.kind == _engine.PEN_L2BALL for r in native[0])
+        # ... any other matrix penalty (unimodality, total variation along the rows of A, a user's MatrixPenalty) is evaluated by
+        # EVERY rank on the all-gathered matrix A + U (I x r floats: small) through the penalty's own prox, each rank keeping its
+        # rows - the reference's arithmetic, replicated; row-separable kinds stay rank-local
+        self.gathered_A = [sharded and nat.kind != _engine.PEN_L2BALL and not _local_on_A(nat, reg)
+                           for nat, reg in zip(native[0], regs[0])]
+        if (self.sharded_ball_A or any(self.gathered_A)) and not opt.constant_A:
+            raise NotImplementedError("a matrix penalty on mode 0 needs constant_feasibility_penalty (as in the reference, "
+                                      "which has no row update for it)")
+        # the A phase in steps: a prox between the ranks or on the host; else its rho max alone is reduced, or nothing
+        self.stepped_A = self.sharded_ball_A or any(self.gathered_A) or self.has_ext[0]
+        self.needs_A_steps = sharded and opt.constant_A
+        # host-evaluated penalties on mode 1 that act on ALL matrices at once (a user's MatricesPenalty) under group=: like PARAFAC2
+        # they may couple the B_i of different ranks, so every rank evaluates the prox on the all-gathered matrices and keeps its own
+        self.gathered_B = [sharded and nat.kind == _engine.PEN_EXTERNAL and not isinstance(reg, penalties.MatrixPenalty)
+                           for reg, nat in zip(regs[1], native[1])]
+        self.row_slices = [slice(int(row_ptr[i]), int(row_ptr[i + 1])) for i in range(len(row_ptr) - 1)]
+        self.b_layout = None  # row counts of every rank's matrices, in rank order (gathered once)
+
+    # ---- an outer iteration -------------------------------------------------------------------------------------------
+    def iteration(self):
+        if self.opt.update_B_is:
+            self.update_B()
+        if self.opt.update_C:
+            self.update_C()
+        if self.opt.update_A:
+            self.update_A()
+
+    def plain_iterations(self, n):
+        if self.grp.sharded:  # n outer iterations without diagnostics, on whichever path this run takes
+            for _ in range(n):
+                self.iteration()
+        else:
+            self.eng.iterate(n, update_A=self.opt.update_A, update_B=self.opt.update_B_is, update_C=self.opt.update_C)
+
+    def _inner_loop(self, mode, solve, proxes, before_test=None):
+        """the inner ADMM loop of a stepped phase: solve, the prox of every penalty, the convergence test - at most
+        inner_n_iter_max times, once without penalties"""
+        n_it = self.opt.inner_n_iter_max if self.native[mode] else min(1, self.opt.inner_n_iter_max)
+        for _ in range(n_it):
+            F_old = getattr(self.eng, "ABC"[mode]).clone() if self.check_inner else None
+            solve()
+            proxes()
+            if self.check_inner and before_test is not None:
+                before_test()
+            if self.inner_converged(mode, F_old):
+                break
+
+    def update_B(self):
+        eng = self.eng
+        if not self.needs_B_steps:
+            eng.update_B()
+            return
+        eng.B_begin()
+        if self.opt.constant_B:
+            self.grp.all_reduce(eng.B_rho_max(), "max")
+        eng.B_factor()
+        self._inner_loop(1, eng.B_solve, self._proxes_B, before_test=eng.B_end)  # (the test reads B / aux on the host side)
+        eng.B_end()
+
+    def update_C(self):
+        eng = self.eng
+        self.grp.all_reduce(eng.update_C_local())
+        if not self.has_ext[2]:
+            eng.update_C_finish()
+            return
+        eng.C_begin()
+        self._inner_loop(2, eng.C_solve, self._proxes_C)
+        eng.C_end()
+
+    def update_A(self):
+        eng = self.eng
+        if not (self.stepped_A or self.needs_A_steps):
+            eng.update_A()
+            return
+        eng.A_begin()
+        if self.opt.constant_A:
+            self.grp.all_reduce(eng.A_rho_max(), "max")
+        if not self.stepped_A:
+            eng.A_finish()
+            return
+        eng.A_factor()
+        rho_a = eng.rho(0).cpu().numpy()
+        self._inner_loop(0, eng.A_solve, lambda: self._proxes_A(rho_a))
+        eng.A_end()
+
+    def inner_converged(self, mode, F_old):
+        """decomposition.py:90-117 on device tensors: relative change and every feasibility gap of the mode below inner_tol"""
+        if not self.check_inner:  # (host-driven modes - host-evaluated penalties - run the test here even when the engine has it too)
+            return False
+        # squared norms in fp64: [ |F|^2, |F - F_old|^2, |F - aux_k|^2 ... ].  With group= the rows of modes 0 and 1 live on
+        # different ranks: the sums are all-reduced, so that every rank leaves the inner loop at the same iteration and the
+        # test is the reference's (over ALL B_i); C is replicated and needs nothing
+        F64 = getattr(self.eng, "ABC"[mode]).double()
+        sq = torch.stack([(F64 ** 2).sum(), ((F64 - F_old.double()) ** 2).sum()]
+                         + [((F64 - nat.aux.double()) ** 2).sum() for nat in self.native[mode]])
+        if mode != 2:
+            self.grp.all_reduce(sq)
+        sq = sq.cpu().numpy()
+        nrm = float(np.sqrt(sq[0]))
+        if float(np.sqrt(sq[1])) > self.opt.inner_tol * nrm:
+            return False
+        if not self.native[mode]:
+            return True
+        return max(float(np.sqrt(v)) / nrm for v in sq[2:]) < self.opt.inner_tol
+
+    def _proxes_B(self):
+        eng = self.eng
+        for k, nat in enumerate(self.native[1]):
+            if nat.kind != _engine.PEN_EXTERNAL:
+                eng.B_prox_local(k)
+                if nat.kind == _engine.PEN_PARAFAC2:
+                    self.grp.all_reduce(eng.B_prox_reduce_buffer(k))
+                eng.B_prox_finish(k)
+            elif self.gathered_B[k]:
+                self.sharded_gathered_prox_B(k)
+            else:  # a MatrixPenalty's prox acts on one matrix at a time: every rank evaluates it on its own matrices
+                self.host_prox_B(k)
+
+    def _proxes_C(self):
+        rho_c = self.eng.rho(2).cpu().numpy()
+        for k in range(len(self.native[2])):
+            self.host_prox_matrix(2, k, self.eng.C, rho_c, True)
+
+    def _proxes_A(self, rho_a):
+        for k, nat in enumerate(self.native[0]):
+            if self.sharded_ball_A and nat.kind == _engine.PEN_L2BALL:
+                self.sharded_ball_prox_A(k)
+            elif self.gathered_A[k]:
+                self.sharded_gathered_prox_A(k, rho_a)
+            else:
+                self.host_prox_matrix(0, k, self.eng.A, rho_a, self.opt.constant_A)
+
+    def host_prox_B(self, k):
+        """user prox of penalty k on mode 1 (decomposition.py:276-285), evaluated on device tensors"""
+        eng, reg, nat = self.eng, self.regs[1][k], self.native[1][k]
+        rhos = [float(v) for v in eng.rho(1).cpu().numpy()]
+        shifted = [eng.B[sl] + nat.dual[sl] for sl in self.row_slices]
+        obj = reg.factor_matrices_update(shifted, rhos, self.ext_aux[(1, k)])
+        self.ext_aux[(1, k)] = obj
+        nat.aux.copy_(torch.cat([m.to(nat.aux.dtype) for m in reg.auxes_as_matrices(obj)], 0))
+        nat.dual.copy_(eng.B - (nat.aux - nat.dual))
+
+    def gather_matrices_B(self, t):
+        """all ranks' matrices of a packed mode-1 array [rows of this rank, r], in rank order, as a list"""
+        grp = self.grp
+        if self.b_layout is None:
+            mine = torch.tensor([sl.stop - sl.start for sl in self.row_slices], dtype=torch.int64, device=t.device)
+            self.b_layout = [[int(v) for v in p.cpu().numpy()] for p in grp.gather_rows(mine, "B matrices")]
+            grp.counts["B rows"] = [sum(js) for js in self.b_layout]
+        out = []
+        for p, js in zip(grp.gather_rows(t, "B rows"), self.b_layout):
+            o = 0
+            for j in js:
+                out.append(p[o:o + j])
+                o += j
+        return out
+
+    def sharded_gathered_prox_B(self, k):
+        """a MatricesPenalty on the sharded B_i (decomposition.py:276-285): its prox on ALL matrices, this rank's kept"""
+        eng, grp, row_slices = self.eng, self.grp, self.row_slices
+        reg, nat = self.regs[1][k], self.native[1][k]
+        obj = self.ext_aux[(1, k)]
+        # the object the penalty keeps must be the list of matrices itself to be split over ranks by matrix
+        if not (isinstance(obj, (list, tuple)) and len(obj) == len(row_slices)
+                and all(is_torch(o) and tuple(o.shape) == (sl.stop - sl.start, nat.aux.shape[1]) for o, sl in zip(obj, row_slices))):
+            raise NotImplementedError("a host-evaluated MatricesPenalty on mode 1 whose auxiliary variable is not the list of "
+                                      "matrices itself is not supported with group=")
+        shifted = self.gather_matrices_B(eng.B + nat.dual)
+        auxes = self.gather_matrices_B(torch.cat([o.to(nat.aux.dtype) for o in obj], 0))
+        # the feasibility penalties of all matrices (one per matrix, fp64), in the same order
+        rho_parts = grp.gather_rows(eng.rho(1).to(device=nat.aux.device, dtype=torch.float64), "B matrices")
+        rho_all = [float(v) for p in rho_parts for v in p.cpu().numpy()]
+        full = reg.factor_matrices_update(shifted, rho_all, auxes)
+        lo, hi = grp.own_rows("B matrices")
+        own = [m.clone() for m in full[lo:hi]]
+        self.ext_aux[(1, k)] = own
+        nat.aux.copy_(torch.cat([m.to(nat.aux.dtype) for m in reg.auxes_as_matrices(own)], 0))
+        nat.dual.copy_(eng.B - (nat.aux - nat.dual))
+
+    def host_prox_matrix(self, mode, k, F, rho_rows, constant):
+        """user prox of penalty k on mode 0 / 2 (decomposition.py:197-213 / 333-338)"""
+        reg, nat = self.regs[mode][k], self.native[mode][k]
+        shifted = F + nat.dual
+        obj = self.ext_aux.get((mode, k))
+        if obj is None:  # native kind evaluated through its host method inside a host-driven mode
+            obj = nat.aux.clone()
+        if constant:
+            obj = reg.factor_matrix_update(shifted, float(rho_rows[0]), obj)
+        else:
+            obj = obj.clone() if is_torch(obj) else obj
+            for i in range(F.shape[0]):
+                obj[i] = reg.factor_matrix_row_update(shifted[i], float(rho_rows[i]), obj[i])
+        if (mode, k) in self.ext_aux:
+            self.ext_aux[(mode, k)] = obj
+        nat.aux.copy_(reg.aux_as_matrix(obj).to(nat.aux.dtype))
+        nat.dual.copy_(F - (nat.aux - nat.dual))
+
+    def sharded_ball_prox_A(self, k):
+        """L2-ball prox on the sharded A (penalties.py:920-925): column norms over ALL rows = all-reduced partial sums"""
+        eng, nat = self.eng, self.native[0][k]
+        y = eng.A + nat.dual
+        if nat.non_negativity:
+            y = torch.clamp(y, min=0)
+        sq = (y.double() ** 2).sum(0)
+        self.grp.all_reduce(sq)
+        nrm = torch.sqrt(sq).to(y.dtype)
+        bound = torch.as_tensor(nat.p0, dtype=y.dtype, device=y.device)
+        z = y * (bound / torch.maximum(nrm, bound))
+        nat.dual.copy_(eng.A - (z - nat.dual))
+        nat.aux.copy_(z)
+
+    def gather_rows_A(self, t):
+        return torch.cat(self.grp.gather_rows(t, "A rows"), 0)  # all ranks' rows of a mode-0 matrix, in rank order
+
+    def sharded_gathered_prox_A(self, k, rho_a):
+        """matrix penalty on the sharded A (decomposition.py:203): the penalty's prox on the gathered A + U, own rows kept"""
+        eng, reg, nat = self.eng, self.regs[0][k], self.native[0][k]
+        obj = self.ext_aux.get((0, k))
+        if obj is None:
+            aux_rows = nat.aux  # native kind evaluated through its host method: its aux IS the matrix
+        else:
+            # host-evaluated penalty (a user's MatrixPenalty; any matrix penalty while inner_tol is set): the object it keeps
+            # must be the matrix itself to be gathered by rows - another parametrisation cannot be split over ranks
+            aux_rows = reg.aux_as_matrix(obj)
+            if not (is_torch(obj) and is_torch(aux_rows) and tuple(obj.shape) == tuple(nat.aux.shape)
+                    and tuple(aux_rows.shape) == tuple(nat.aux.shape)):
+                raise NotImplementedError("a host-evaluated matrix penalty on mode 0 whose auxiliary variable is not the matrix "
+                                          "itself (aux_as_matrix is not the identity) is not supported with group=")
+        full = reg.factor_matrix_update(self.gather_rows_A(eng.A + nat.dual), float(rho_a[0]), self.gather_rows_A(aux_rows))
+        lo, hi = self.grp.own_rows("A rows")
+        z = reg.aux_as_matrix(full)[lo:hi].to(nat.aux.dtype)
+        if obj is not None:
+            self.ext_aux[(0, k)] = full[lo:hi].clone()  # this rank's rows of the object the penalty returned (what return_admm_vars hands out)
+        nat.dual.copy_(eng.A - (z - nat.dual))
+        nat.aux.copy_(z)
+
+    # ---- diagnostics ----------------------------------------------------------------------------------------------------
+    def l1_weights(self):
+        """per mode and penalty, what multiplies sum |factor| in the loss: the table of the device stopping rules"""
+        return [[(reg.reg_strength if isinstance(reg, penalties.L1Penalty) else 0.0) for reg in self.regs[m]] for m in range(3)]
+
+    def read_diag(self, vec):
+        """MCL_DIAG vector (already all-reduced) -> (rec_error, (A_gaps, B_gaps, C_gaps), reg_penalty + l2)"""
+        eng, sharded, l2_penalty = self.eng, self.grp.sharded, self.opt.l2_penalty
+        d = vec.detach().cpu().numpy() if is_torch(vec) else np.asarray(vec)
+        xsq, inner, model = d[_engine.DIAG_X_SQ], d[_engine.DIAG_INNER], d[_engine.DIAG_MODEL_SQ]
+        norm_matrices = np.sqrt(xsq)
+        rec_error = np.sqrt(max(0.0, xsq - 2 * inner + model)) / norm_matrices
+        gaps, reg_penalty = [], 0.0
+        for mode in range(3):
+            fnorm = np.sqrt(d[_engine.DIAG_NORM_SQ + mode])
+            mode_gaps = []
+            for k, reg in enumerate(self.regs[mode]):
+                base, kind = _diag_slot(mode, k), self.native[mode][k].kind
+                mode_gaps.append(np.sqrt(d[base]) / fnorm)
+                if isinstance(reg, penalties.L1Penalty):
+                    reg_penalty += reg.reg_strength * d[base + 1]
+                elif sharded and mode == 1 and kind in (_engine.PEN_EXTERNAL, _engine.PEN_TV, _engine.PEN_GL2):
+                    reg_penalty += d[base + 1]  # this rank's matrices only: summed over the ranks with the vector (diagnostics())
+                elif kind == _engine.PEN_GL2:
+                    reg_penalty += float(eng.penalty_value(mode, k))  # trace(F^T M F), evaluated by the engine
+                elif kind in (_engine.PEN_EXTERNAL, _engine.PEN_TV) or (mode == 0 and sharded and self.gathered_A[k]):
+                    # value computed on device tensors; a sharded A is gathered first (every rank adds the same, whole value)
+                    factor = [eng.B[sl] for sl in self.row_slices] if mode == 1 else (
+                        (self.gather_rows_A(eng.A) if sharded else eng.A) if mode == 0 else eng.C)
+                    reg_penalty += float(reg.penalty(factor))
+            gaps.append(mode_gaps)
+            if l2_penalty[mode]:
+                reg_penalty += 0.5 * l2_penalty[mode] * d[_engine.DIAG_NORM_SQ + mode]
+        return rec_error, tuple(gaps), reg_penalty
+
+    def read_diag_rows(self, rows):
+        """read_diag for a whole ring of iterations at once (the same elementwise arithmetic in the same order, vectorised:
+        the per-iteration Python of read_diag costs as much as 7 % of a config-3 iteration): (rec_errors, gaps per iteration,
+        reg_penalties).  Only for stacks whose penalty values come out of the diagnostics vector (no host-evaluated value).
+        (Kept beside read_diag, not under it: on a NaN sum `max(0.0, x)` there gives 0 where `np.maximum` here gives NaN.)"""
+        l2_penalty = self.opt.l2_penalty
+        d = np.asarray(rows, dtype=np.float64).reshape(-1, _engine.DIAG_LEN)
+        xsq, inner, model = d[:, _engine.DIAG_X_SQ], d[:, _engine.DIAG_INNER], d[:, _engine.DIAG_MODEL_SQ]
+        rec = np.sqrt(np.maximum(0.0, xsq - 2 * inner + model)) / np.sqrt(xsq)
+        reg_pen = np.zeros(len(d))
+        per_mode = []
+        for mode in range(3):
+            fnorm = np.sqrt(d[:, _engine.DIAG_NORM_SQ + mode])
+            cols = []
+            for k, reg in enumerate(self.regs[mode]):
+                base = _diag_slot(mode, k)
+                cols.append(np.sqrt(d[:, base]) / fnorm)
+                if isinstance(reg, penalties.L1Penalty):
+                    reg_pen = reg_pen + reg.reg_strength * d[:, base + 1]
+                elif self.native[mode][k].kind in (_engine.PEN_EXTERNAL, _engine.PEN_TV, _engine.PEN_GL2):
+                    raise AssertionError("read_diag_rows: host-evaluated penalty value")
+            per_mode.append(np.stack(cols, axis=1) if cols else np.zeros((len(d), 0)))
+            if l2_penalty[mode]:
+                reg_pen = reg_pen + 0.5 * l2_penalty[mode] * d[:, _engine.DIAG_NORM_SQ + mode]
+        gaps = [tuple(list(per_mode[m][i]) for m in range(3)) for i in range(len(d))]
+        return rec, gaps, reg_pen
+
+    def diagnostics(self):
+        eng, grp = self.eng, self.grp
+        vec = eng.diagnostics(include_replicated=(grp.rank == 0))
+        if grp.sharded:
+            # penalties on the B_i whose value is summed on the host (total variation, host-evaluated MatrixPenalty classes):
+            # the value over THIS rank's matrices travels in the penalty-value slot of the vector and is summed over the
+            # ranks with it
+            for k, reg in enumerate(self.regs[1]):
+                if isinstance(reg, penalties.L1Penalty):
+                    continue  # read_diag takes reg_strength * sum|B| from the native slot, which is summed over the ranks already
+                if self.native[1][k].kind == _engine.PEN_GL2:
+                    vec[_diag_slot(1, k) + 1] = float(eng.penalty_value(1, k))
+                elif self.gathered_B[k]:  # a value over ALL matrices (need not be a sum over them): counted once, by rank 0
+                    value = float(reg.penalty(self.gather_matrices_B(eng.B)))
+                    vec[_diag_slot(1, k) + 1] = value if grp.rank == 0 else 0.0
+                elif self.native[1][k].kind in (_engine.PEN_EXTERNAL, _engine.PEN_TV):
+                    vec[_diag_slot(1, k) + 1] = float(reg.penalty([eng.B[sl] for sl in self.row_slices]))
+        grp.all_reduce(vec)
+        return self.read_diag(vec)
+
+
+class _ArithmeticRule:
+    """arithmetic="auto" above the small-problem limit: decided by CONDITIONING, not by size alone.
+
+    A mode without any penalty solves un-shifted normal equations (the reference: an fp64 SVD, decomposition.py:172, 252-256,
+    319-321) and multiplies whatever the fp32 kernels left in its inputs (1e-8 .. 4e-7 relative) by the condition number of
+    its system.  On large problems those roundings average out over 1e5 .. 1e7 rows (BASELINE config 4: C to 8e-8 at
+    condition 600) and the exact arithmetic would cost passes over X; below _AUTO_EXACT_MAX_ELEMENTS elements neither
+    holds.  The condition numbers that matter are those AT THE START OF EACH PHASE (Gauss-Seidel: the A-phase of an
+    iteration solves systems built from the B_i and C of the same iteration - a random start has kappa ~30 where the first
+    A-phase meets 3e4), so they are measured there: a TRIAL of _AUTO_EXACT_TRIAL_ITERATIONS iterations runs under the engine's
+    condition monitor (mcl_condition_monitor: per phase of a penalty-free mode, kappa = ||M||_F ||M^-1||_F of its system, from
+    the factors, no pass over X), the initial state is restored, and with a kappa above _AUTO_EXACT_KAPPA the run takes the
+    exact arithmetic (fp64 sums of exact products, fp64 inner loops) from its first iteration - the result is that of one
+    arithmetic from start to end.  Long runs look again every _AUTO_EXACT_PROBE_EVERY iterations (one monitored iteration) and
+    switch forward.  Under `group=` the maxima are all-reduced (every rank switches, or none).  Larger problems keep the fast
+    kernels; a badly conditioned one is told about `arithmetic="exact"`.
+
+    `candidate`: the rule still has something to decide.  `with rule.watching(due):` runs its body under the monitor when the
+    rule is a candidate and `due`, and decides on what the monitor saw."""
+
+    def __init__(self, run, arithmetic, n_el_total, rank):
+        self.run, self.n_el_total, self._mon = run, n_el_total, None
+        native, opt = run.native, run.opt
+        free_modes = [m for m in range(3) if run.updates[m] and len(run.regs[m]) == 0]
+        all_native = not any(r.kind == _engine.PEN_EXTERNAL for m in range(3) for r in native[m])
+        has_pf2 = opt.update_B_is and any(r_.kind == _engine.PEN_PARAFAC2 for r_ in native[1]) and rank <= 32
+        self.candidate = (arithmetic == "auto" and (bool(free_modes) or (has_pf2 and n_el_total <= _AUTO_EXACT_MAX_ELEMENTS))
+                          and n_el_total > float(1 << 20) and opt.n_iter_max > 0 and all_native
+                          and hasattr(run.eng, "condition_monitor"))
+
+    def trial(self, n):
+        """n iterations under the monitor from the initial state, which is restored; then the decision"""
+        eng = self.run.eng
+        state = [eng.A, eng.B, eng.C] + [t for m in range(3) for r_ in self.run.native[m] for t in (r_.aux, r_.dual, r_.aux2)
+                                         if t is not None]
+        saved = [t.clone() for t in state]
+        mon = eng.condition_monitor(True, *self.run.updates)
+        try:
+            self.run.plain_iterations(n)
+        finally:
+            eng.condition_monitor(False)
+        self.run.grp.all_reduce(mon, "max")
+        worst = self.kappa_of(mon)
+        for t, t0 in zip(state, saved):
+            t.copy_(t0)
+        del saved
+        eng.invalidate()  # the factors changed behind the engine's back
+        self.decide(worst, stacklevel=5)
+
+    def watching(self, due=True):
+        self._due = self.candidate and due
+        return self
+
+    def __enter__(self):
+        self._mon = self.run.eng.condition_monitor(True, *self.run.updates) if self._due else None
+
+    def __exit__(self, exc_type, exc, tb):
+        mon, self._mon = self._mon, None
+        if mon is None:
+            return
+        self.run.eng.condition_monitor(False)
+        if exc_type is None:
+            self.run.grp.all_reduce(mon, "max")
+            self.decide(self.kappa_of(mon), stacklevel=6)
+
+    @staticmethod
+    def kappa_of(mon):
+        """monitor vector -> the number the rule looks at: the worst kappa of a penalty-free mode's system, or - on the same
+        footing, _AUTO_EXACT_KAPPA / _AUTO_EXACT_POLAR apart - the worst conditioning of a PARAFAC2 polar factor (the Gram route of
+        the fast kernels squares it: a factor of condition 1e5 sits at the edge of what fp32 statistics resolve)"""
+        m = mon.cpu().numpy()
+        return max(float(m[:3].max()), float(m[3]) * (_AUTO_EXACT_KAPPA / _AUTO_EXACT_POLAR))
+
+    def decide(self, worst, stacklevel):
+        """`stacklevel`: of the warning, counted from here to the caller of cmf_aoadmm's caller"""
+        if self.n_el_total > _AUTO_EXACT_MAX_ELEMENTS:
+            self.candidate = False  # (large problems are looked at once, for the warning only)
+            if worst > _AUTO_EXACT_WARN_KAPPA:
+                warnings.warn(
+                    f"cmf_aoadmm: a mode without penalties has normal equations of condition ~{worst:.1e}; the fp32 kernels this "
+                    f"problem size takes by default carry about 1e-8 x that in the factors. Pass arithmetic=\"exact\" for the "
+                    "reference's fp64 solve (slower: fp64 passes over the matrices).", RuntimeWarning, stacklevel=stacklevel)
+        elif worst > _AUTO_EXACT_KAPPA:
+            self.run.eng.set_exact(True)
+            self.candidate = False
+            if self.run.opt.verbose:
+                print(f"matcouply_amd: penalty-free mode with condition ~{worst:.1e}: the exact arithmetic from here on")
+
+
+class _Record:
+    """What the outer loop of one fit leaves behind: the diagnostics per iteration (the initial state first) and how it ended."""
+
+    def __init__(self, initial):
+        rec_error, gaps, reg_penalty = initial
+        self.rec_errors, self.feasibility_gaps, self.losses = [rec_error], [gaps], [0.5 * rec_error ** 2 + reg_penalty]
+        self.it = -1  # Needed if n_iter_max <= 0
+        self.satisfied, self.message = False, _StopRule.EXHAUSTED
+        self.feasible = None  # the feasibility verdict on the last iterate looked at
+        self.final_gaps_known = False  # feasibility_gaps[-1] is of the state the fit returns
+
+    def add_rows(self, rec, gaps, reg):
+        """a ring of iterations as read_diag_rows reads it"""
+        self.feasibility_gaps.extend(gaps)
+        self.rec_errors.extend(rec)
+        self.losses.extend(0.5 * rec ** 2 + reg)
+
+    def add_verdicts(self, gaps, verdicts, feasibility_tol):
+        """a chunk of a device stopping rule: its gaps and its verdict ring [rec_error, loss, worst gap, flags] per iteration"""
+        self.feasibility_gaps.extend(gaps)
+        if len(verdicts):
+            flags = verdicts[:, 3].astype(np.int64)
+            self.feasible = bool(flags[-1] & _engine.VERDICT_FEASIBLE) if feasibility_tol else feasibility_tol
+            evaluated = (flags & _engine.VERDICT_LOSS_EVALUATED) != 0  # not on infeasible iterates unless errors are recorded (Q10)
+            self.rec_errors.extend(verdicts[evaluated, 0].tolist())
+            self.losses.extend(verdicts[evaluated, 1].tolist())
+
+    def end_of_device_rule(self, done, code):
+        self.it = done - 1
+        if code:
+            self.satisfied, self.message = True, _StopRule.message_of(code)
+        self.final_gaps_known = True
+
+    def metrics(self, rule_active):
+        return DiagnosticMetrics(
+            rec_errors=self.rec_errors, feasibility_gaps=self.feasibility_gaps, regularized_loss=self.losses,
+            satisfied_stopping_condition=(self.satisfied if (self.satisfied or rule_active) else None),
+            satisfied_feasibility_condition=self.feasible, message=self.message, n_iter=self.it + 1)
+
+
+def _choose_loop(run):
+    """the outer loop this fit takes"""
+    eng, opt, sharded = run.eng, run.opt, run.grp.sharded
+    tol, absolute_tol, verbose, n_iter_max, has_ext = opt.tol, opt.absolute_tol, opt.verbose, opt.n_iter_max, run.has_ext
+    # penalty values that need a host call per iteration (the device-resident loops below do not apply)
+    host_value = any(r.kind in (_engine.PEN_TV, _engine.PEN_EXTERNAL, _engine.PEN_GL2) for m in range(3) for r in run.native[m]) or any(run.gathered_A)
+    fast_path = ((not (tol or absolute_tol)) and not sharded and not verbose and n_iter_max > 0 and not any(has_ext)
+                 and not host_value)
+    lazy_diag = (not (tol or absolute_tol)) and sharded and not verbose and n_iter_max > 0 and not host_value
+    # stopping rule on the device (mcl_run): single device, every penalty native, silent.  (tol set with absolute_tol=None is
+    # a TypeError in the reference's comparison - the host loop below raises it the same way.)
+    device_stop = (bool(tol or absolute_tol) and not sharded and not verbose and n_iter_max > 0 and not any(has_ext)
+                   and not host_value and not (tol and absolute_tol is None) and hasattr(eng, "run"))
+    # ... and the same rule under sharding (mcl_gate_begin / mcl_verdict): the phases are stepped with their reductions, the
+    # diagnostics vector is all-reduced and every rank evaluates the rule on the same bits.  Every rank must enqueue the same
+    # number of iterations (their collectives pair up), so the loop runs in fixed chunks with one synchronisation each.
+    sharded_stop = (bool(tol or absolute_tol) and sharded and not verbose and n_iter_max > 0 and not any(has_ext)
+                    and not host_value and not run.sharded_ball_A and not (tol and absolute_tol is None)
+                    and hasattr(eng, "gate_begin"))
+    return (_loop_lazy_diag if lazy_diag else _loop_sharded_stop if sharded_stop else _loop_device_stop if device_stop
+            else _loop_fast_path if fast_path else _loop_host)
+
+
+def _loop_lazy_diag(run, rule, rec):
+    """sharded, fixed iteration count: nothing depends on the diagnostics inside the loop, so their partial sums stay
+    on the device and are all-reduced once for all iterations (one collective per iteration remains: [G | R])"""
+    eng, grp, n_iter_max = run.eng, run.grp, run.opt.n_iter_max
+    ring = torch.zeros((n_iter_max, _engine.DIAG_LEN), dtype=torch.float64, device=run.device) if run.opt.return_errors else None
+    for it in range(n_iter_max):
+        with rule.watching(it > 0 and it % _AUTO_EXACT_PROBE_EVERY == 0):
+            run.iteration()
+            if ring is not None:  # the table reduction rides on the next iteration's C-phase reduction kernel
+                eng.diagnostics_deferred(include_replicated=(grp.rank == 0), out=ring[it])
+    rec.it = n_iter_max - 1
+    if ring is not None:
+        eng.flush_diagnostics()
+        grp.all_reduce(ring)
+        rec.add_rows(*run.read_diag_rows(ring.cpu().numpy()))
+
+
+def _loop_sharded_stop(run, rule, rec):
+    """a stopping rule under sharding: evaluated on the device behind every iteration's all-reduced diagnostics (see _choose_loop)"""
+    eng, grp, opt, device, n_iter_max = run.eng, run.grp, run.opt, run.device, run.opt.n_iter_max
+    eng.gate_begin(opt.tol, opt.absolute_tol, opt.feasibility_tol, initial_loss=rec.losses[-1], penalty_weight=run.l1_weights(),
+                   evaluate_loss_always=opt.return_errors)
+    gate_closed = False
+    try:
+        chunk, done, code = 8, 0, 0
+        ring = torch.zeros((n_iter_max if n_iter_max <= 4096 else 4096, _engine.DIAG_LEN), dtype=torch.float64, device=device)
+        verdict = torch.zeros((ring.shape[0], 4), dtype=torch.float64, device=device)
+        while done < n_iter_max and not code:
+            n_now = min(chunk, n_iter_max - done)
+            base = done % ring.shape[0]
+            if base + n_now > ring.shape[0]:
+                base = 0
+            for j in range(n_now):
+                run.iteration()
+                eng.diagnostics(include_replicated=(grp.rank == 0), out=ring[base + j])
+                grp.all_reduce(ring[base + j])
+                eng.verdict(ring[base + j], done + j, verdict[base + j])
+            if is_torch(ring) and ring.is_cuda:
+                torch.cuda.synchronize(device)
+            stopped, stop_it, code = eng.gate_status()
+            n_ran = (stop_it - done + 1) if stopped else n_now
+            ring_h, verdict_h = ring[base:base + n_ran].cpu().numpy(), verdict[base:base + n_ran].cpu().numpy()
+            rec.add_verdicts(run.read_diag_rows(ring_h)[1], verdict_h, opt.feasibility_tol)
+            done += n_ran
+            if not stopped:
+                code = 0
+        eng.gate_end(bool(code))
+        gate_closed = True
+    finally:
+        if not gate_closed:  # an exception inside the loop (a failed collective, a NotImplementedError of a step): never
+            eng.gate_end(True)  # leave the context gated - its kernels would silently do nothing from then on
+    rec.end_of_device_rule(done, code)
+
+
+def _loop_device_stop(run, rule, rec):
+    """a stopping rule is active (the DEFAULT call: tol=1e-8, absolute_tol=1e-10, feasibility_tol=1e-4): the rule is
+    evaluated by a kernel at the end of every iteration (mcl_run), the host enqueues ahead of the verdicts and never
+    blocks on one; state-writing kernels behind a stopping iteration see the device-side flag and do nothing, so
+    the factors returned are exactly those of the stopping iteration.  Chunked so that the rings stay small."""
+    opt, weights = run.opt, run.l1_weights()
+
+    def run_chunk(n_now):
+        n_ran, code, ring_h, verdict_h = run.eng.run(
+            n_now, opt.tol, opt.absolute_tol, opt.feasibility_tol, initial_loss=rec.losses[-1], penalty_weight=weights,
+            evaluate_loss_always=opt.return_errors, update_A=opt.update_A, update_B=opt.update_B_is, update_C=opt.update_C)
+        rec.add_verdicts(run.read_diag_rows(ring_h)[1], verdict_h, opt.feasibility_tol)
+        return n_ran, code
+
+    done, code, chunk = 0, 0, 4096
+    while done < opt.n_iter_max and not code:
+        n_now = min(_AUTO_EXACT_PROBE_EVERY if rule.candidate else chunk, opt.n_iter_max - done)
+        watched = rule.candidate and done > 0  # the first iteration of every further chunk runs under the condition monitor
+        with rule.watching(watched):
+            n_ran, code = run_chunk(1 if watched else n_now)
+        done += n_ran
+        if watched and not code and n_now > 1:
+            n_ran, code = run_chunk(n_now - 1)
+            done += n_ran
+    rec.end_of_device_rule(done, code)
+
+
+def _loop_fast_path(run, rule, rec):
+    """fixed iteration count: the whole outer loop runs natively, diagnostics stay on the device until the end"""
+    eng, opt = run.eng, run.opt
+    n_iter_max, updates = opt.n_iter_max, dict(update_A=opt.update_A, update_B=opt.update_B_is, update_C=opt.update_C)
+    ring = torch.zeros((n_iter_max, _engine.DIAG_LEN), dtype=torch.float64, device=run.device) if opt.return_errors else None
+    done = 0
+    while done < n_iter_max:  # (one call, unless the conditioning of a penalty-free mode is being watched)
+        n_now = min(_AUTO_EXACT_PROBE_EVERY, n_iter_max - done) if rule.candidate else n_iter_max - done
+        watched = rule.candidate and done > 0  # the first iteration of every further chunk runs under the monitor
+        with rule.watching(watched):
+            eng.iterate(1 if watched else n_now, **updates, diag_ring=(ring[done:] if ring is not None else None))
+        if watched and n_now > 1:
+            eng.iterate(n_now - 1, **updates, diag_ring=(ring[done + 1:] if ring is not None else None))
+        done += n_now
+    rec.it = n_iter_max - 1
+    if ring is not None:
+        rec.add_rows(*run.read_diag_rows(ring.cpu().numpy()))
+
+
+def _loop_host(run, rule, rec):
+    """the reference's loop (decomposition.py:990-1053): diagnostics, console output and the stopping rule on the host"""
+    opt = run.opt
+    progress, stop = _Progress(opt.verbose), _StopRule(opt.tol, opt.absolute_tol, opt.feasibility_tol)
+    progress.initial(rec.feasibility_gaps[0])
+    for it in range(opt.n_iter_max):
+        rec.it = it
+        with rule.watching(it > 0 and it % _AUTO_EXACT_PROBE_EVERY == 0):
+            run.iteration()
+        if not (stop.active or opt.return_errors):
+            progress.iteration(it)
+            continue
+        rec_error, gaps, reg_pen = run.diagnostics()
+        rec.feasibility_gaps.append(gaps)
+        if stop.active:
+            rec.feasible = stop.feasible(gaps)
+            if not rec.feasible and not opt.return_errors:
+                progress.iteration(it, gaps=gaps)  # the loss is not evaluated on infeasible iterates (Q10)
+                continue
+        rec.rec_errors.append(rec_error)
+        losses = rec.losses
+        losses.append(0.5 * rec_error ** 2 + reg_pen)
+        progress.iteration(it, rec_error, losses[-1], abs(losses[-2] - losses[-1]) / losses[-2], gaps)
+        fired = stop.verdict(rec.feasible, losses)
+        if fired is not None:
+            rec.satisfied, rec.message = True, fired
+            progress.converged(it, fired)
+            break
+    else:
+        progress.exhausted()
+
+
+def _admm_vars_out(out, row_ptr, state):
+    """ADMM variables in the caller's array type; state[mode]: (kind, aux, aux2, dual) per penalty, device tensors (a PEN_EXTERNAL's
+    aux: the object its penalty keeps; aux2: the Delta of a PARAFAC2, else None)"""
+    auxes, duals = [[], [], []], [[], [], []]
+    for mode in range(3):
+        for kind, aux, aux2, dual in state[mode]:
+            if kind == _engine.PEN_EXTERNAL:
+                auxes[mode].append(_aux_out(aux, out))
+            elif kind == _engine.PEN_PARAFAC2:
+                auxes[mode].append((out.split(aux, row_ptr), out(aux2)))
+            else:
+                auxes[mode].append(out.split(aux, row_ptr) if mode == 1 else out(aux))
+            duals[mode].append(out.split(dual, row_ptr) if mode == 1 else out(dual))
+    return ADMMVars(auxes=tuple(auxes), duals=tuple(duals))
+
+
 def cmf_aoadmm(
     matrices,
     rank,
@@ -833,9 +1571,10 @@ def cmf_aoadmm(
     ``"cp_als"`` (CP-ALS) and ``"parafac_hals"`` / ``"cp_hals"`` (non-negative CP-HALS), deterministic (``random_state``
     draws nothing for them), with ``init_params`` keys ``n_iter_max`` (default 50) and ``tol`` (default 1e-8 / 1e-7; 0 runs
     every sweep).  Not supported (out of scope, raise ``NotImplementedError``): ``"parafac2_als"``, other ``init_params``
-    keys, a CP start with rank above min(max J_i, K), K or max J_i above 2048, and CP starts under ``group=``.  ``inner_tol`` > 0 is evaluated by the engine on the device (single-device runs; sharded runs: on a host-driven step path).  Penalties without a native kernel (user
-    subclasses of ``matcouply_amd.penalties.ADMMPenalty``) are evaluated through their own Python methods on device
-    tensors between the native solve and dual-update steps.
+    keys, a CP start with rank above min(max J_i, K), K or max J_i above 2048, and CP starts under ``group=``.  ``inner_tol`` > 0
+    is evaluated by the engine on the device (single-device runs; sharded runs: on a host-driven step path).  Penalties without
+    a native kernel (user subclasses of ``matcouply_amd.penalties.ADMMPenalty``) are evaluated through their own Python methods
+    on device tensors between the native solve and dual-update steps.
 
     Sharded runs (``group=``, keyword-only, not in the reference): every rank of the ``torch.distributed`` process group
     passes ITS matrices (see :func:`partition_slabs`) and gets back its rows of ``A``, its ``B_i`` and the replicated ``C``;
@@ -861,6 +1600,7 @@ def cmf_aoadmm(
     >>> len(matcouply_amd.decomposition._listify({1: 0.5}, "l1_penalty"))
     3
     """
+    # ---- arguments, and the start with the reference's draw order -------------------------------------------------------
     if arithmetic not in ("auto", "exact", "fast"):
         raise ValueError(f'arithmetic must be "auto", "exact" or "fast", not {arithmetic!r}')
     random_state = check_random_state(random_state)
@@ -868,41 +1608,18 @@ def cmf_aoadmm(
     if group is not None and isinstance(init, str) and init in _CP_INITS:
         raise NotImplementedError(f'init="{init}" needs all matrices (its start is a decomposition of the whole padded '
                                   "tensor): not supported with group=; pass an explicit (weights, (A, B_is, C)) tuple instead.")
-    cmf = initialize_cmf(matrices, rank, init, svd_fun=svd_fun, random_state=random_state, init_params=init_params)
+    kw = dict(init=init, init_params=init_params, non_negative=non_negative, lower_bound=lower_bound, upper_bound=upper_bound,
+              l2_norm_bound=l2_norm_bound, unimodal=unimodal, parafac2=parafac2, l1_penalty=l1_penalty, tv_penalty=tv_penalty,
+              generalized_l2_penalty=generalized_l2_penalty, svd=svd, regs=regs, dual_init=dual_init, aux_init=aux_init,
+              update_A=update_A, update_B_is=update_B_is, update_C=update_C)
+    cmf, regs, auxes, duals = _start_penalties(kw, matrices, rank, random_state, svd_fun=svd_fun, verbose=verbose)
+    opt = SimpleNamespace(
+        l2_penalty=[l2 if l2 is not None else 0 for l2 in _listify(l2_penalty, "l2_penalty")], inner_tol=inner_tol,
+        inner_n_iter_max=inner_n_iter_max, update_A=update_A, update_B_is=update_B_is, update_C=update_C, n_iter_max=n_iter_max,
+        tol=tol, absolute_tol=absolute_tol, feasibility_tol=feasibility_tol, return_errors=return_errors, verbose=verbose)
+    opt.constant_A, opt.constant_B = _constant_flags(constant_feasibility_penalty)
 
-    l2_penalty = _listify(l2_penalty, "l2_penalty")
-    l2_penalty = [l2 if l2 is not None else 0 for l2 in l2_penalty]
-
-    regs = _parse_all_penalties(
-        non_negative=non_negative, lower_bound=lower_bound, upper_bound=upper_bound, l2_norm_bound=l2_norm_bound,
-        unimodal=unimodal, parafac2=parafac2, l1_penalty=l1_penalty, tv_penalty=tv_penalty,
-        generalized_l2_penalty=generalized_l2_penalty, svd=svd, regs=regs, dual_init=dual_init, aux_init=aux_init,
-        verbose=verbose)
-    if not update_A:
-        regs[0] = []
-    if not update_B_is:
-        regs[1] = []
-    if not update_C:
-        regs[2] = []
-    # inner_tol > 0 (early exit of the inner ADMM loops, decomposition.py:90-117) needs a convergence test after every
-    # inner iteration.  Single-device runs: the ENGINE evaluates it (mcl_options.inner_tol: one launch per step, a device-side
-    # flag the remaining inner launches test; native prox kernels stay native, no host synchronisation).  Sharded runs (the
-    # norms must be all-reduced over the ranks) and the CPU checker keep the step path: native solves, every prox through
-    # the penalty objects' own methods on device tensors, the test on the host
-    check_inner = bool(inner_tol) and inner_tol > 0
-    if isinstance(constant_feasibility_penalty, str) and constant_feasibility_penalty not in {"A", "B"}:
-        raise ValueError(
-            f"If `constant_feasibility_penalty` is a string, it must be 'A' or 'B', not {constant_feasibility_penalty}")
-    constant_A = (constant_feasibility_penalty and not isinstance(constant_feasibility_penalty, str)
-                  ) or constant_feasibility_penalty == "A"
-    constant_B = (constant_feasibility_penalty and not isinstance(constant_feasibility_penalty, str)
-                  ) or constant_feasibility_penalty == "B"
-
-    # ---- initial ADMM state with the reference's draw order (aux of modes 0,1,2 then duals of modes 0,1,2) ----
-    A_aux_list, B_aux_list, C_aux_list = initialize_aux(matrices, rank, regs, random_state=random_state)
-    A_dual_list, B_dual_list, C_dual_list = initialize_dual(matrices, rank, regs, random_state=random_state)
-
-    # ---- move everything to the device -----------------------------------------------------------------------
+    # ---- move everything to the device: the data, the factors, the penalties' variables -------------------------------------
     sub = _test_engine_factory()
     factory = sub or _default_engine_factory
     device = _device() if sub is None else getattr(sub, "device", torch.device("cpu"))
@@ -914,782 +1631,74 @@ def cmf_aoadmm(
     A, B, C = _to_dev(A0, device), _pack_rows(B0_is, device), _to_dev(C0, device)
     if B.shape != (X.shape[0], rank):
         raise ValueError("The B_i matrices of `init` do not match the shapes of `matrices`")
-
-    native = [[], [], []]
+    check_inner = bool(inner_tol) and inner_tol > 0  # on a single device the engine's test, else every prox through the host
     device_inner = check_inner and sub is None and group is None
-    aux_lists, dual_lists = (A_aux_list, B_aux_list, C_aux_list), (A_dual_list, B_dual_list, C_dual_list)
-    # host-evaluated penalties: the Python object keeps the auxiliary variable in ITS parametrisation (on the device),
-    # the engine sees `aux_as_matrix` of it (reference penalties.py:311-343)
-    ext_aux = {}
-    for mode in range(3):
-        for k, (reg, aux, dual) in enumerate(zip(regs[mode], aux_lists[mode], dual_lists[mode])):
-            desc = None if (check_inner and not device_inner) else penalties.native_descriptor_of(reg)
-            gl2_matrix = None
-            if desc is not None and desc[0] == _engine.PEN_GL2:
-                # every matrix of the mode must have as many rows as the norm matrix (anything else fails in the reference's
-                # product too: left to the penalty's own method); a sharded A holds only this rank's rows of the I x I problem
-                gl2_matrix, n_gl2 = reg._native_matrix()
-                rows_m = [shape(m_)[0] for m_ in matrices] if mode == 1 else [len(matrices) if mode == 0 else shape(matrices[0])[1]]
-                if any(rw != n_gl2 for rw in rows_m) or (group is not None and mode == 0):
-                    desc = None
-            dual_t = _pack_rows(dual, device) if mode == 1 else _to_dev(dual, device)
-            if desc is None:
-                if mode == 1:
-                    obj = _aux_to_device(aux, device)
-                    mat = _pack_rows(reg.auxes_as_matrices(obj), device)
-                else:
-                    obj = _aux_to_device(aux, device)
-                    mat = _to_dev(reg.aux_as_matrix(obj), device)
-                ext_aux[(mode, k)] = obj
-                native[mode].append(_engine.NativeReg(_engine.PEN_EXTERNAL, mat, dual_t))
-                continue
-            kind, nonneg, p0, p1 = desc
-            if kind == _engine.PEN_PARAFAC2:
-                P_is, Delta = aux
-                native[mode].append(_engine.NativeReg(kind, _pack_rows(P_is, device), dual_t,
-                                                      aux2=_to_dev(Delta, device)))
-            else:
-                aux_t = _pack_rows(aux, device) if mode == 1 else _to_dev(aux, device)
-                extra = {}
-                if kind == _engine.PEN_GL2:
-                    extra = dict(matrix=torch.as_tensor(gl2_matrix, dtype=torch.float64, device=device).contiguous(), matrix_rows=n_gl2)
-                native[mode].append(_engine.NativeReg(kind, aux_t, dual_t, non_negativity=nonneg, p0=p0, p1=p1, **extra))
+    native, ext_aux = _native_penalties(regs, auxes, duals, matrices, device, check_inner and not device_inner, group is not None)
 
-    world = 1
-    dist = None
-    if group is not None:
-        import torch.distributed as dist  # noqa: F811
-
-        world = dist.get_world_size(group)
-        rank_id = dist.get_rank(group)
-    else:
-        rank_id = 0
+    # ---- the engine and the run on it ------------------------------------------------------------------------------------
+    grp = _Group(group)
     # the arithmetic of small problems (exact-products mode) is chosen by the size of the WHOLE problem:
     # every rank of a sharded run, and every rank layout of the same problem, then computes with the same kernels
     exact_products = {"auto": 0, "exact": 1, "fast": 2}[arithmetic]
     n_el_total = float(X.shape[0]) * float(X.shape[1])
-    if world > 1 and arithmetic == "auto":
+    if grp.world > 1 and arithmetic == "auto":
         n_el = torch.tensor([n_el_total], dtype=torch.float64, device=X.device)
-        dist.all_reduce(n_el, group=group)
+        grp.all_reduce(n_el)
         n_el_total = float(n_el.item())
         exact_products = 1 if n_el_total <= float(1 << 20) else 2
-    eng = factory(X=X, row_ptr=row_ptr, rank=rank, A=A, B=B, C=C, regs=native, l2_penalty=l2_penalty,
+    eng = factory(X=X, row_ptr=row_ptr, rank=rank, A=A, B=B, C=C, regs=native, l2_penalty=opt.l2_penalty,
                   inner_n_iter_max=inner_n_iter_max, feasibility_penalty_scale=feasibility_penalty_scale,
-                  constant_A=constant_A, constant_B=constant_B, exact_products=exact_products,
+                  constant_A=opt.constant_A, constant_B=opt.constant_B, exact_products=exact_products,
                   **(dict(inner_tol=inner_tol) if device_inner else {}))
-    # the sharded code path (step calls with the reductions in between): taken with more than one rank - and, for
-    # rehearsals of that path on a single-GPU box, with a one-rank group when MCL_FORCE_SHARDED_PATH=1
-    sharded = world > 1 or (group is not None and os.environ.get("MCL_FORCE_SHARDED_PATH") == "1")
-    needs_B_steps = sharded and (constant_B or any(r.kind == _engine.PEN_PARAFAC2 for r in native[1]))
-    needs_A_steps = sharded and constant_A
-    # mode 0 under sharding: the rows of A live on different ranks.  Row-separable penalties need nothing; an L2 ball
-    # (the README case: l2_norm_bound on A with a constant feasibility penalty) needs the r column sums of squares of
-    # A + U all-reduced in every inner iteration; other matrix penalties are not supported.
-    sharded_ball_A = sharded and any(r.kind == _engine.PEN_L2BALL for r in native[0])
-    # ... any other matrix penalty (unimodality, total variation along the rows of A, a user's MatrixPenalty) is evaluated by
-    # EVERY rank on the all-gathered matrix A + U (I x r floats: small) through the penalty's own prox, each rank keeping its
-    # rows - the reference's arithmetic, replicated; row-separable kinds stay rank-local
-    def _local_on_A(nat, reg):
-        return nat.kind in (_engine.PEN_NN, _engine.PEN_BOX, _engine.PEN_L1) or (
-            nat.kind == _engine.PEN_EXTERNAL and isinstance(reg, penalties.RowVectorPenalty))
+    run = _Run(eng, regs, native, ext_aux, grp, row_ptr, device, opt)
+    grp.direct = _direct_comm(group, X.device) if (grp.sharded and sub is None) else None
 
-    gathered_A = [sharded and nat.kind != _engine.PEN_L2BALL and not _local_on_A(nat, reg)
-                  for nat, reg in zip(native[0], regs[0])]
-    if (sharded_ball_A or any(gathered_A)) and not constant_A:
-        raise NotImplementedError("a matrix penalty on mode 0 needs constant_feasibility_penalty (as in the reference, "
-                                  "which has no row update for it)")
-
-    # RCCL groups: the collectives go straight onto the engine's stream through a communicator of the engine's own
-    # (_rccl.DirectComm: no stream hand-over); any other backend (gloo in the CPU tests), or a failed self-test: torch's
-    direct = _direct_comm(group, X.device) if (sharded and sub is None) else None
-
-    def all_reduce(t, op="sum"):
-        if not sharded:
-            return
-        if (direct is not None and is_torch(t) and t.is_cuda and t.device == direct.device
-                and t.dtype in (torch.float32, torch.float64) and t.is_contiguous()):
-            direct.all_reduce(t, op)
-        elif sharded:
-            dist.all_reduce(t, op=(dist.ReduceOp.MAX if op == "max" else dist.ReduceOp.SUM), group=group)
-
-    has_ext = [any(r.kind == _engine.PEN_EXTERNAL for r in native[m]) for m in range(3)]
-    needs_B_steps = needs_B_steps or has_ext[1]
-    row_slices = [slice(int(row_ptr[i]), int(row_ptr[i + 1])) for i in range(len(row_ptr) - 1)]
-
-    def host_prox_B(k):
-        """user prox of penalty k on mode 1 (decomposition.py:276-285), evaluated on device tensors"""
-        reg, nat = regs[1][k], native[1][k]
-        rhos = [float(v) for v in eng.rho(1).cpu().numpy()]
-        shifted = [eng.B[sl] + nat.dual[sl] for sl in row_slices]
-        obj = reg.factor_matrices_update(shifted, rhos, ext_aux[(1, k)])
-        ext_aux[(1, k)] = obj
-        nat.aux.copy_(torch.cat([m.to(nat.aux.dtype) for m in reg.auxes_as_matrices(obj)], 0))
-        nat.dual.copy_(eng.B - (nat.aux - nat.dual))
-
-    # host-evaluated penalties on mode 1 that act on ALL matrices at once (a user's MatricesPenalty) under group=: like PARAFAC2
-    # they may couple the B_i of different ranks, so every rank evaluates the prox on the all-gathered matrices and keeps its own
-    gathered_B = [sharded and nat.kind == _engine.PEN_EXTERNAL and not isinstance(reg, penalties.MatrixPenalty)
-                  for reg, nat in zip(regs[1], native[1])]
-    b_layout = []  # row counts of every rank's matrices, in rank order (gathered once)
-
-    def gather_matrices_B(t):
-        """all ranks' matrices of a packed mode-1 array [rows of this rank, r], in rank order, as a list"""
-        if not b_layout:
-            mine = torch.tensor([sl.stop - sl.start for sl in row_slices], dtype=torch.int64, device=t.device)
-            n_loc = torch.tensor([len(row_slices)], dtype=torch.int64, device=t.device)
-            cnt = [torch.zeros_like(n_loc) for _ in range(world)]
-            dist.all_gather(cnt, n_loc, group=group)
-            cnt = [int(c.item()) for c in cnt]
-            padded = torch.zeros((max(cnt),), dtype=torch.int64, device=t.device)
-            padded[: len(row_slices)] = mine
-            parts = [torch.empty_like(padded) for _ in range(world)]
-            dist.all_gather(parts, padded, group=group)
-            b_layout.extend([int(v) for v in p[:c].cpu().numpy()] for p, c in zip(parts, cnt))
-        rows = [sum(js) for js in b_layout]
-        padded = torch.zeros((max(rows), t.shape[1]), dtype=t.dtype, device=t.device)
-        padded[: t.shape[0]] = t
-        parts = [torch.empty_like(padded) for _ in range(world)]
-        dist.all_gather(parts, padded, group=group)
-        out = []
-        for p, js in zip(parts, b_layout):
-            o = 0
-            for j in js:
-                out.append(p[o:o + j])
-                o += j
-        return out
-
-    def sharded_gathered_prox_B(k):
-        """a MatricesPenalty on the sharded B_i (decomposition.py:276-285): its prox on ALL matrices, this rank's kept"""
-        reg, nat = regs[1][k], native[1][k]
-        obj = ext_aux[(1, k)]
-        # the object the penalty keeps must be the list of matrices itself to be split over ranks by matrix
-        if not (isinstance(obj, (list, tuple)) and len(obj) == len(row_slices)
-                and all(is_torch(o) and tuple(o.shape) == (sl.stop - sl.start, nat.aux.shape[1]) for o, sl in zip(obj, row_slices))):
-            raise NotImplementedError("a host-evaluated MatricesPenalty on mode 1 whose auxiliary variable is not the list of "
-                                      "matrices itself is not supported with group=")
-        shifted = gather_matrices_B(eng.B + nat.dual)
-        auxes = gather_matrices_B(torch.cat([o.to(nat.aux.dtype) for o in obj], 0))
-        # the feasibility penalties of all matrices (one per matrix, fp64), in the same order
-        cnt = [len(js) for js in b_layout]
-        padded = torch.zeros((max(cnt),), dtype=torch.float64, device=nat.aux.device)
-        padded[: len(row_slices)] = eng.rho(1).to(device=nat.aux.device, dtype=torch.float64)
-        parts = [torch.empty_like(padded) for _ in range(world)]
-        dist.all_gather(parts, padded, group=group)
-        rho_all = [float(v) for p, c in zip(parts, cnt) for v in p[:c].cpu().numpy()]
-        full = reg.factor_matrices_update(shifted, rho_all, auxes)
-        lo = sum(len(js) for js in b_layout[:rank_id])
-        own = [m.clone() for m in full[lo:lo + len(row_slices)]]
-        ext_aux[(1, k)] = own
-        nat.aux.copy_(torch.cat([m.to(nat.aux.dtype) for m in reg.auxes_as_matrices(own)], 0))
-        nat.dual.copy_(eng.B - (nat.aux - nat.dual))
-
-    def host_prox_matrix(mode, k, F, rho_rows, constant):
-        """user prox of penalty k on mode 0 / 2 (decomposition.py:197-213 / 333-338)"""
-        reg, nat = regs[mode][k], native[mode][k]
-        shifted = F + nat.dual
-        obj = ext_aux.get((mode, k))
-        if obj is None:  # native kind evaluated through its host method inside a host-driven mode
-            obj = nat.aux.clone()
-        if constant:
-            obj = reg.factor_matrix_update(shifted, float(rho_rows[0]), obj)
-        else:
-            obj = obj.clone() if is_torch(obj) else obj
-            for i in range(F.shape[0]):
-                obj[i] = reg.factor_matrix_row_update(shifted[i], float(rho_rows[i]), obj[i])
-        if (mode, k) in ext_aux:
-            ext_aux[(mode, k)] = obj
-        nat.aux.copy_(reg.aux_as_matrix(obj).to(nat.aux.dtype))
-        nat.dual.copy_(F - (nat.aux - nat.dual))
-
-    def inner_converged(F, F_old, mode):
-        """decomposition.py:90-117 on device tensors: relative change and every feasibility gap of the mode below inner_tol"""
-        if not check_inner:  # (host-driven modes - host-evaluated penalties - run the test here even when the engine has it too)
-            return False
-        # squared norms in fp64: [ |F|^2, |F - F_old|^2, |F - aux_k|^2 ... ].  With group= the rows of modes 0 and 1 live on
-        # different ranks: the sums are all-reduced, so that every rank leaves the inner loop at the same iteration and the
-        # test is the reference's (over ALL B_i); C is replicated and needs nothing
-        F64 = F.double()
-        sq = torch.stack([(F64 ** 2).sum(), ((F64 - F_old.double()) ** 2).sum()]
-                         + [((F64 - nat.aux.double()) ** 2).sum() for nat in native[mode]])
-        if sharded and mode != 2:
-            all_reduce(sq)
-        sq = sq.cpu().numpy()
-        nrm = float(np.sqrt(sq[0]))
-        if float(np.sqrt(sq[1])) > inner_tol * nrm:
-            return False
-        if not native[mode]:
-            return True
-        return max(float(np.sqrt(v)) / nrm for v in sq[2:]) < inner_tol
-
-    def do_update_B():
-        if not needs_B_steps:
-            eng.update_B()
-            return
-        eng.B_begin()
-        if constant_B:
-            all_reduce(eng.B_rho_max(), "max")
-        eng.B_factor()
-        n_it = inner_n_iter_max if native[1] else min(1, inner_n_iter_max)
-        for _ in range(n_it):
-            B_old = eng.B.clone() if check_inner else None
-            eng.B_solve()
-            for k, reg in enumerate(native[1]):
-                if reg.kind == _engine.PEN_EXTERNAL:
-                    # a MatrixPenalty's prox acts on one matrix at a time: every rank evaluates it on its own matrices
-                    if gathered_B[k]:
-                        sharded_gathered_prox_B(k)
-                    else:
-                        host_prox_B(k)
-                    continue
-                eng.B_prox_local(k)
-                if reg.kind == _engine.PEN_PARAFAC2:
-                    all_reduce(eng.B_prox_reduce_buffer(k))
-                eng.B_prox_finish(k)
-            if check_inner:
-                eng.B_end()  # the convergence test reads B / aux on the host side
-                if inner_converged(eng.B, B_old, 1):
-                    break
-        eng.B_end()
-
-    def do_update_C():
-        gr = eng.update_C_local()
-        all_reduce(gr)
-        if not has_ext[2]:
-            eng.update_C_finish()
-            return
-        eng.C_begin()
-        n_it = inner_n_iter_max if native[2] else min(1, inner_n_iter_max)
-        for _ in range(n_it):
-            C_old = eng.C.clone() if check_inner else None
-            eng.C_solve()
-            rho_c = eng.rho(2).cpu().numpy()
-            for k in range(len(native[2])):
-                host_prox_matrix(2, k, eng.C, rho_c, True)
-            if inner_converged(eng.C, C_old, 2):
-                break
-        eng.C_end()
-
-    def sharded_ball_prox_A(k, rho_a):
-        """L2-ball prox on the sharded A (penalties.py:920-925): column norms over ALL rows = all-reduced partial sums"""
-        nat = native[0][k]
-        y = eng.A + nat.dual
-        if nat.non_negativity:
-            y = torch.clamp(y, min=0)
-        sq = (y.double() ** 2).sum(0)
-        all_reduce(sq)
-        nrm = torch.sqrt(sq).to(y.dtype)
-        bound = torch.as_tensor(nat.p0, dtype=y.dtype, device=y.device)
-        z = y * (bound / torch.maximum(nrm, bound))
-        nat.dual.copy_(eng.A - (z - nat.dual))
-        nat.aux.copy_(z)
-
-    a_counts = []
-
-    def gather_rows_A(t):
-        """all ranks' rows of a mode-0 matrix, in rank order (uneven shares: padded for the collective, trimmed after)"""
-        if not a_counts:
-            n_loc = torch.tensor([t.shape[0]], dtype=torch.int64, device=t.device)
-            cnt = [torch.zeros_like(n_loc) for _ in range(world)]
-            dist.all_gather(cnt, n_loc, group=group)
-            a_counts.extend(int(c.item()) for c in cnt)
-        padded = torch.zeros((max(a_counts), t.shape[1]), dtype=t.dtype, device=t.device)
-        padded[: t.shape[0]] = t
-        parts = [torch.empty_like(padded) for _ in range(world)]
-        dist.all_gather(parts, padded, group=group)
-        return torch.cat([p[:c] for p, c in zip(parts, a_counts)], 0)
-
-    def sharded_gathered_prox_A(k, rho_a):
-        """matrix penalty on the sharded A (decomposition.py:203): the penalty's prox on the gathered A + U, own rows kept"""
-        reg, nat = regs[0][k], native[0][k]
-        obj = ext_aux.get((0, k))
-        if obj is None:
-            aux_rows = nat.aux  # native kind evaluated through its host method: its aux IS the matrix
-        else:
-            # host-evaluated penalty (a user's MatrixPenalty; any matrix penalty while inner_tol is set): the object it keeps
-            # must be the matrix itself to be gathered by rows - another parametrisation cannot be split over ranks
-            aux_rows = reg.aux_as_matrix(obj)
-            if not (is_torch(obj) and is_torch(aux_rows) and tuple(obj.shape) == tuple(nat.aux.shape)
-                    and tuple(aux_rows.shape) == tuple(nat.aux.shape)):
-                raise NotImplementedError("a host-evaluated matrix penalty on mode 0 whose auxiliary variable is not the matrix "
-                                          "itself (aux_as_matrix is not the identity) is not supported with group=")
-        full = reg.factor_matrix_update(gather_rows_A(eng.A + nat.dual), float(rho_a[0]), gather_rows_A(aux_rows))
-        lo = sum(a_counts[:rank_id])
-        own = full[lo:lo + a_counts[rank_id]] if obj is not None else None
-        z = reg.aux_as_matrix(full)[lo:lo + a_counts[rank_id]].to(nat.aux.dtype)
-        if obj is not None:
-            ext_aux[(0, k)] = own.clone()  # this rank's rows of the object the penalty returned (what return_admm_vars hands out)
-        nat.dual.copy_(eng.A - (z - nat.dual))
-        nat.aux.copy_(z)
-
-    def do_update_A():
-        if sharded_ball_A or any(gathered_A):
-            eng.A_begin()
-            all_reduce(eng.A_rho_max(), "max")
-            eng.A_factor()
-            rho_a = eng.rho(0).cpu().numpy()
-            n_it = inner_n_iter_max if native[0] else min(1, inner_n_iter_max)
-            for _ in range(n_it):
-                A_old = eng.A.clone() if check_inner else None
-                eng.A_solve()
-                for k, nat in enumerate(native[0]):
-                    if nat.kind == _engine.PEN_L2BALL:
-                        sharded_ball_prox_A(k, rho_a)
-                    elif gathered_A[k]:
-                        sharded_gathered_prox_A(k, rho_a)
-                    else:
-                        host_prox_matrix(0, k, eng.A, rho_a, True)
-                if inner_converged(eng.A, A_old, 0):
-                    break
-            eng.A_end()
-            return
-        if has_ext[0]:
-            eng.A_begin()
-            if constant_A:
-                all_reduce(eng.A_rho_max(), "max")
-            eng.A_factor()
-            rho_a = eng.rho(0).cpu().numpy()
-            n_it = inner_n_iter_max if native[0] else min(1, inner_n_iter_max)
-            for _ in range(n_it):
-                A_old = eng.A.clone() if check_inner else None
-                eng.A_solve()
-                for k in range(len(native[0])):
-                    host_prox_matrix(0, k, eng.A, rho_a, constant_A)
-                if inner_converged(eng.A, A_old, 0):
-                    break
-            eng.A_end()
-            return
-        if not needs_A_steps:
-            eng.update_A()
-            return
-        eng.A_begin()
-        all_reduce(eng.A_rho_max(), "max")
-        eng.A_finish()
-
-    def read_diag(vec):
-        """MCL_DIAG vector (already all-reduced) -> (rec_error, (A_gaps, B_gaps, C_gaps), reg_penalty + l2)"""
-        d = vec.detach().cpu().numpy() if is_torch(vec) else np.asarray(vec)
-        xsq, inner, model = d[_engine.DIAG_X_SQ], d[_engine.DIAG_INNER], d[_engine.DIAG_MODEL_SQ]
-        norm_matrices = np.sqrt(xsq)
-        rec_error = np.sqrt(max(0.0, xsq - 2 * inner + model)) / norm_matrices
-        gaps, reg_penalty = [], 0.0
-        for mode in range(3):
-            fnorm = np.sqrt(d[_engine.DIAG_NORM_SQ + mode])
-            mode_gaps = []
-            for k, reg in enumerate(regs[mode]):
-                base = _engine.DIAG_REG + (mode * _engine.MCL_MAX_REGS + k) * 2
-                mode_gaps.append(np.sqrt(d[base]) / fnorm)
-                if isinstance(reg, penalties.L1Penalty):
-                    reg_penalty += reg.reg_strength * d[base + 1]
-                elif sharded and mode == 1 and native[mode][k].kind in (_engine.PEN_EXTERNAL, _engine.PEN_TV, _engine.PEN_GL2):
-                    reg_penalty += d[base + 1]  # this rank's matrices only: summed over the ranks with the vector (diagnostics())
-                elif native[mode][k].kind == _engine.PEN_GL2:
-                    reg_penalty += float(eng.penalty_value(mode, k))  # trace(F^T M F), evaluated by the engine
-                elif native[mode][k].kind in (_engine.PEN_EXTERNAL, _engine.PEN_TV) or (mode == 0 and sharded and gathered_A[k]):
-                    # value computed on device tensors; a sharded A is gathered first (every rank adds the same, whole value)
-                    factor = [eng.B[sl] for sl in row_slices] if mode == 1 else (
-                        (gather_rows_A(eng.A) if sharded else eng.A) if mode == 0 else eng.C)
-                    reg_penalty += float(reg.penalty(factor))
-            gaps.append(mode_gaps)
-            if l2_penalty[mode]:
-                reg_penalty += 0.5 * l2_penalty[mode] * d[_engine.DIAG_NORM_SQ + mode]
-        return rec_error, tuple(gaps), reg_penalty
-
-    def read_diag_rows(rows):
-        """read_diag for a whole ring of iterations at once (the same elementwise arithmetic in the same order, vectorised:
-        the per-iteration Python of read_diag costs as much as 7 % of a config-3 iteration): (rec_errors, gaps per iteration,
-        reg_penalties).  Only for stacks whose penalty values come out of the diagnostics vector (no host-evaluated value)."""
-        d = np.asarray(rows, dtype=np.float64).reshape(-1, _engine.DIAG_LEN)
-        xsq, inner, model = d[:, _engine.DIAG_X_SQ], d[:, _engine.DIAG_INNER], d[:, _engine.DIAG_MODEL_SQ]
-        rec = np.sqrt(np.maximum(0.0, xsq - 2 * inner + model)) / np.sqrt(xsq)
-        reg_pen = np.zeros(len(d))
-        per_mode = []
-        for mode in range(3):
-            fnorm = np.sqrt(d[:, _engine.DIAG_NORM_SQ + mode])
-            cols = []
-            for k, reg in enumerate(regs[mode]):
-                base = _engine.DIAG_REG + (mode * _engine.MCL_MAX_REGS + k) * 2
-                cols.append(np.sqrt(d[:, base]) / fnorm)
-                if isinstance(reg, penalties.L1Penalty):
-                    reg_pen = reg_pen + reg.reg_strength * d[:, base + 1]
-                elif native[mode][k].kind in (_engine.PEN_EXTERNAL, _engine.PEN_TV, _engine.PEN_GL2):
-                    raise AssertionError("read_diag_rows: host-evaluated penalty value")
-            per_mode.append(np.stack(cols, axis=1) if cols else np.zeros((len(d), 0)))
-            if l2_penalty[mode]:
-                reg_pen = reg_pen + 0.5 * l2_penalty[mode] * d[:, _engine.DIAG_NORM_SQ + mode]
-        gaps = [tuple(list(per_mode[m][i]) for m in range(3)) for i in range(len(d))]
-        return rec, gaps, reg_pen
-
-    def diagnostics():
-        vec = eng.diagnostics(include_replicated=(rank_id == 0))
-        if sharded:
-            # penalties on the B_i whose value is summed on the host (total variation, host-evaluated MatrixPenalty classes):
-            # the value over THIS rank's matrices travels in the penalty-value slot of the vector and is summed over the
-            # ranks with it
-            for k, reg in enumerate(regs[1]):
-                if isinstance(reg, penalties.L1Penalty):
-                    continue  # read_diag takes reg_strength * sum|B| from the native slot, which is summed over the ranks already
-                if native[1][k].kind == _engine.PEN_GL2:
-                    vec[_engine.DIAG_REG + (_engine.MCL_MAX_REGS + k) * 2 + 1] = float(eng.penalty_value(1, k))
-                elif gathered_B[k]:  # a value over ALL matrices (need not be a sum over them): counted once, by rank 0
-                    value = float(reg.penalty(gather_matrices_B(eng.B)))
-                    vec[_engine.DIAG_REG + (_engine.MCL_MAX_REGS + k) * 2 + 1] = value if rank_id == 0 else 0.0
-                elif native[1][k].kind in (_engine.PEN_EXTERNAL, _engine.PEN_TV):
-                    vec[_engine.DIAG_REG + (_engine.MCL_MAX_REGS + k) * 2 + 1] = float(reg.penalty([eng.B[sl] for sl in row_slices]))
-        all_reduce(vec)
-        return read_diag(vec)
-
-    # ---- arithmetic="auto" above the small-problem limit: decided by CONDITIONING, not by size alone ------------------------
-    # A mode without any penalty solves un-shifted normal equations (the reference: an fp64 SVD, decomposition.py:172, 252-256,
-    # 319-321) and multiplies whatever the fp32 kernels left in its inputs (1e-8 .. 4e-7 relative) by the condition number of
-    # its system.  On large problems those roundings average out over 1e5 .. 1e7 rows (BASELINE config 4: C to 8e-8 at
-    # condition 600) and the exact arithmetic would cost passes over X; below _AUTO_EXACT_MAX_ELEMENTS elements neither
-    # holds.  The condition numbers that matter are those AT THE START OF EACH PHASE (Gauss-Seidel: the A-phase of an
-    # iteration solves systems built from the B_i and C of the same iteration - a random start has kappa ~30 where the first
-    # A-phase meets 3e4), so they are measured there: a TRIAL of _AUTO_EXACT_TRIAL_ITERATIONS iterations runs under the engine's
-    # condition monitor (mcl_condition_monitor: per phase of a penalty-free mode, kappa = ||M||_F ||M^-1||_F of its system, from
-    # the factors, no pass over X), the initial state is restored, and with a kappa above _AUTO_EXACT_KAPPA the run takes the
-    # exact arithmetic (fp64 sums of exact products, fp64 inner loops) from its first iteration - the result is that of one
-    # arithmetic from start to end.  Long runs look again every _AUTO_EXACT_PROBE_EVERY iterations (one monitored iteration) and
-    # switch forward.  Under `group=` the maxima are all-reduced (every rank switches, or none).  Larger problems keep the fast
-    # kernels; a badly conditioned one is told about `arithmetic="exact"`.
-    updated_modes = (update_A, update_B_is, update_C)
-    free_modes = [m for m in range(3) if updated_modes[m] and len(regs[m]) == 0]
-    all_native = not any(r.kind == _engine.PEN_EXTERNAL for m in range(3) for r in native[m])
-    has_pf2 = update_B_is and any(r_.kind == _engine.PEN_PARAFAC2 for r_ in native[1]) and rank <= 32
-    auto_candidate = (arithmetic == "auto" and (bool(free_modes) or (has_pf2 and n_el_total <= _AUTO_EXACT_MAX_ELEMENTS))
-                      and n_el_total > float(1 << 20) and n_iter_max > 0 and all_native and hasattr(eng, "condition_monitor"))
-
-    def plain_iterations(n):
-        """n outer iterations without diagnostics, on whichever path this run takes"""
-        if sharded:
-            for _ in range(n):
-                if update_B_is:
-                    do_update_B()
-                if update_C:
-                    do_update_C()
-                if update_A:
-                    do_update_A()
-        else:
-            eng.iterate(n, update_A=update_A, update_B=update_B_is, update_C=update_C)
-
-    def monitored_kappa(n):
-        """worst kappa the penalty-free phases of the next n iterations meet (all ranks: the same number); the iterations RUN"""
-        mon = eng.condition_monitor(True, update_A, update_B_is, update_C)
-        try:
-            plain_iterations(n)
-        finally:
-            eng.condition_monitor(False)
-        if sharded:
-            all_reduce(mon, "max")
-        return kappa_of(mon)
-
-    def kappa_of(mon):
-        """monitor vector -> the number the rule looks at: the worst kappa of a penalty-free mode's system, or - on the same
-        footing, _AUTO_EXACT_KAPPA / _AUTO_EXACT_POLAR apart - the worst conditioning of a PARAFAC2 polar factor (the Gram route of
-        the fast kernels squares it: a factor of condition 1e5 sits at the edge of what fp32 statistics resolve)"""
-        m = mon.cpu().numpy()
-        return max(float(m[:3].max()), float(m[3]) * (_AUTO_EXACT_KAPPA / _AUTO_EXACT_POLAR))
-
-    def decide_arithmetic(worst):
-        nonlocal auto_candidate
-        if n_el_total > _AUTO_EXACT_MAX_ELEMENTS:
-            auto_candidate = False  # (large problems are looked at once, for the warning only)
-            if worst > _AUTO_EXACT_WARN_KAPPA:
-                import warnings
-
-                warnings.warn(
-                    f"cmf_aoadmm: a mode without penalties has normal equations of condition ~{worst:.1e}; the fp32 kernels this "
-                    f"problem size takes by default carry about 1e-8 x that in the factors. Pass arithmetic=\"exact\" for the "
-                    "reference's fp64 solve (slower: fp64 passes over the matrices).", RuntimeWarning, stacklevel=4)
-        elif worst > _AUTO_EXACT_KAPPA:
-            eng.set_exact(True)
-            auto_candidate = False
-            if verbose:
-                print(f"matcouply_amd: penalty-free mode with condition ~{worst:.1e}: the exact arithmetic from here on")
-
-    if auto_candidate:
-        state = [eng.A, eng.B, eng.C] + [t for m in range(3) for r_ in native[m] for t in (r_.aux, r_.dual, r_.aux2) if t is not None]
-        saved = [t.clone() for t in state]
-        worst = monitored_kappa(min(_AUTO_EXACT_TRIAL_ITERATIONS, n_iter_max))
-        for t, t0 in zip(state, saved):
-            t.copy_(t0)
-        del saved
-        eng.invalidate()  # the factors changed behind the engine's back
-        decide_arithmetic(worst)
-
-    rec_errors, feasibility_gaps, losses = [], [], []
-    rec_error, gaps0, reg0 = diagnostics()
-    rec_errors.append(rec_error)
-    losses.append(0.5 * rec_error ** 2 + reg0)
-    feasibility_gaps.append(gaps0)
-    progress = _Progress(verbose)
-    progress.initial(gaps0)
-    stop = _StopRule(tol, absolute_tol, feasibility_tol)
-
-    satisfied_stopping_condition = False
-    message = _StopRule.EXHAUSTED
-    feasibility_criterion = None
-
-    it = -1  # Needed if n_iter_max <= 0
-    # penalty values that need a host call per iteration (the device-resident loops below do not apply)
-    host_value = any(r.kind in (_engine.PEN_TV, _engine.PEN_EXTERNAL, _engine.PEN_GL2) for m in range(3) for r in native[m]) or any(gathered_A)
-    fast_path = ((not (tol or absolute_tol)) and not sharded and not verbose and n_iter_max > 0 and not any(has_ext)
-                 and not host_value)
-    lazy_diag = (not (tol or absolute_tol)) and sharded and not verbose and n_iter_max > 0 and not host_value
-    # stopping rule on the device (mcl_run): single device, every penalty native, silent.  (tol set with absolute_tol=None is
-    # a TypeError in the reference's comparison - the host loop below raises it the same way.)
-    device_stop = (bool(tol or absolute_tol) and not sharded and not verbose and n_iter_max > 0 and not any(has_ext)
-                   and not host_value and not (tol and absolute_tol is None) and hasattr(eng, "run"))
-    # ... and the same rule under sharding (mcl_gate_begin / mcl_verdict): the phases are stepped with their reductions, the
-    # diagnostics vector is all-reduced and every rank evaluates the rule on the same bits.  Every rank must enqueue the same
-    # number of iterations (their collectives pair up), so the loop runs in fixed chunks with one synchronisation each.
-    sharded_stop = (bool(tol or absolute_tol) and sharded and not verbose and n_iter_max > 0 and not any(has_ext)
-                    and not host_value and not sharded_ball_A and not (tol and absolute_tol is None)
-                    and hasattr(eng, "gate_begin"))
-    final_gaps_known = False
-    if lazy_diag:
-        # sharded, fixed iteration count: nothing depends on the diagnostics inside the loop, so their partial sums stay
-        # on the device and are all-reduced once for all iterations (one collective per iteration remains: [G | R])
-        ring = torch.zeros((n_iter_max, _engine.DIAG_LEN), dtype=torch.float64, device=device) if return_errors else None
-        for it in range(n_iter_max):
-            mon = (eng.condition_monitor(True, update_A, update_B_is, update_C)
-                   if (auto_candidate and it > 0 and it % _AUTO_EXACT_PROBE_EVERY == 0) else None)
-            if update_B_is:
-                do_update_B()
-            if update_C:
-                do_update_C()
-            if update_A:
-                do_update_A()
-            if ring is not None:  # the table reduction rides on the next iteration's C-phase reduction kernel
-                eng.diagnostics_deferred(include_replicated=(rank_id == 0), out=ring[it])
-            if mon is not None:
-                eng.condition_monitor(False)
-                all_reduce(mon, "max")
-                decide_arithmetic(kappa_of(mon))
-        if ring is not None:
-            eng.flush_diagnostics()
-            all_reduce(ring)
-            rec, gaps, reg = read_diag_rows(ring.cpu().numpy())
-            feasibility_gaps.extend(gaps)
-            rec_errors.extend(rec)
-            losses.extend(0.5 * rec ** 2 + reg)
-    elif sharded_stop:
-        weights = [[(reg.reg_strength if isinstance(reg, penalties.L1Penalty) else 0.0) for reg in regs[m]] for m in range(3)]
-        eng.gate_begin(tol, absolute_tol, feasibility_tol, initial_loss=losses[-1], penalty_weight=weights,
-                       evaluate_loss_always=return_errors)
-        gate_closed = False
-        try:
-            chunk, done, code, stop_it = 8, 0, 0, -1
-            ring = torch.zeros((n_iter_max if n_iter_max <= 4096 else 4096, _engine.DIAG_LEN), dtype=torch.float64, device=device)
-            verdict = torch.zeros((ring.shape[0], 4), dtype=torch.float64, device=device)
-            while done < n_iter_max and not code:
-                n_now = min(chunk, n_iter_max - done)
-                base = done % ring.shape[0]
-                if base + n_now > ring.shape[0]:
-                    base = 0
-                for j in range(n_now):
-                    if update_B_is:
-                        do_update_B()
-                    if update_C:
-                        do_update_C()
-                    if update_A:
-                        do_update_A()
-                    eng.diagnostics(include_replicated=(rank_id == 0), out=ring[base + j])
-                    all_reduce(ring[base + j])
-                    eng.verdict(ring[base + j], done + j, verdict[base + j])
-                if is_torch(ring) and ring.is_cuda:
-                    torch.cuda.synchronize(device)
-                stopped, stop_it, code = eng.gate_status()
-                n_ran = (stop_it - done + 1) if stopped else n_now
-                ring_h, verdict_h = ring[base:base + n_ran].cpu().numpy(), verdict[base:base + n_ran].cpu().numpy()
-                feasibility_gaps.extend(read_diag_rows(ring_h)[1])
-                if len(verdict_h):
-                    flags = verdict_h[:, 3].astype(np.int64)
-                    feasibility_criterion = bool(flags[-1] & _engine.VERDICT_FEASIBLE) if feasibility_tol else feasibility_tol
-                    evaluated = (flags & _engine.VERDICT_LOSS_EVALUATED) != 0
-                    rec_errors.extend(verdict_h[evaluated, 0].tolist())
-                    losses.extend(verdict_h[evaluated, 1].tolist())
-                done += n_ran
-                if not stopped:
-                    code = 0
-            eng.gate_end(bool(code))
-            gate_closed = True
-        finally:
-            if not gate_closed:  # an exception inside the loop (a failed collective, a NotImplementedError of a step): never
-                eng.gate_end(True)  # leave the context gated - its kernels would silently do nothing from then on
-        it = done - 1
-        if code:
-            satisfied_stopping_condition = True
-            message = _StopRule.RELATIVE if code == _engine.STOP_RELATIVE else _StopRule.ABSOLUTE
-        final_gaps_known = True
-    elif device_stop:
-        # a stopping rule is active (the DEFAULT call: tol=1e-8, absolute_tol=1e-10, feasibility_tol=1e-4): the rule is
-        # evaluated by a kernel at the end of every iteration (mcl_run), the host enqueues ahead of the verdicts and never
-        # blocks on one; state-writing kernels behind a stopping iteration see the device-side flag and do nothing, so
-        # the factors returned are exactly those of the stopping iteration.  Chunked so that the rings stay small.
-        weights = [[(reg.reg_strength if isinstance(reg, penalties.L1Penalty) else 0.0) for reg in regs[m]] for m in range(3)]
-        done, code, chunk = 0, 0, 4096
-
-        def run_chunk(n_now):
-            nonlocal done, feasibility_criterion
-            n_ran, code_, ring_h, verdict_h = eng.run(
-                n_now, tol, absolute_tol, feasibility_tol, initial_loss=losses[-1], penalty_weight=weights,
-                evaluate_loss_always=return_errors, update_A=update_A, update_B=update_B_is, update_C=update_C)
-            feasibility_gaps.extend(read_diag_rows(ring_h)[1])
-            if len(verdict_h):
-                flags = verdict_h[:, 3].astype(np.int64)
-                feasibility_criterion = bool(flags[-1] & _engine.VERDICT_FEASIBLE) if feasibility_tol else feasibility_tol
-                evaluated = (flags & _engine.VERDICT_LOSS_EVALUATED) != 0  # not on infeasible iterates unless errors are recorded (Q10)
-                rec_errors.extend(verdict_h[evaluated, 0].tolist())
-                losses.extend(verdict_h[evaluated, 1].tolist())
-            done += n_ran
-            return code_
-
-        while done < n_iter_max and not code:
-            n_now = min(_AUTO_EXACT_PROBE_EVERY if auto_candidate else chunk, n_iter_max - done)
-            if auto_candidate and done > 0:  # the first iteration of every further chunk runs under the condition monitor
-                mon = eng.condition_monitor(True, update_A, update_B_is, update_C)
-                code = run_chunk(1)
-                eng.condition_monitor(False)
-                decide_arithmetic(kappa_of(mon))
-                n_now -= 1
-                if code or n_now == 0:
-                    continue
-            code = run_chunk(n_now)
-        it = done - 1
-        if code:
-            satisfied_stopping_condition = True
-            message = _StopRule.RELATIVE if code == _engine.STOP_RELATIVE else _StopRule.ABSOLUTE
-        final_gaps_known = True
-    elif fast_path:
-        # fixed iteration count: the whole outer loop runs natively, diagnostics stay on the device until the end
-        ring = None
-        if return_errors:
-            ring = torch.zeros((n_iter_max, _engine.DIAG_LEN), dtype=torch.float64, device=device)
-        done = 0
-        while done < n_iter_max:  # (one call, unless the conditioning of a penalty-free mode is being watched)
-            n_now = min(_AUTO_EXACT_PROBE_EVERY, n_iter_max - done) if auto_candidate else n_iter_max - done
-            mon = eng.condition_monitor(True, update_A, update_B_is, update_C) if (auto_candidate and done > 0) else None
-            eng.iterate(1 if mon is not None else n_now, update_A=update_A, update_B=update_B_is, update_C=update_C,
-                        diag_ring=(ring[done:] if ring is not None else None))
-            if mon is not None:  # the first iteration of every further chunk ran under the monitor
-                eng.condition_monitor(False)
-                decide_arithmetic(kappa_of(mon))
-                if n_now > 1:
-                    eng.iterate(n_now - 1, update_A=update_A, update_B=update_B_is, update_C=update_C,
-                                diag_ring=(ring[done + 1:] if ring is not None else None))
-            done += n_now
-        it = n_iter_max - 1
-        if return_errors:
-            rec, gaps, reg = read_diag_rows(ring.cpu().numpy())
-            feasibility_gaps.extend(gaps)
-            rec_errors.extend(rec)
-            losses.extend(0.5 * rec ** 2 + reg)
-    else:
-        for it in range(n_iter_max):
-            mon = (eng.condition_monitor(True, update_A, update_B_is, update_C)
-                   if (auto_candidate and it > 0 and it % _AUTO_EXACT_PROBE_EVERY == 0) else None)
-            if update_B_is:
-                do_update_B()
-            if update_C:
-                do_update_C()
-            if update_A:
-                do_update_A()
-            if mon is not None:
-                eng.condition_monitor(False)
-                all_reduce(mon, "max")
-                decide_arithmetic(kappa_of(mon))
-
-            if not (stop.active or return_errors):
-                progress.iteration(it)
-                continue
-            rec_error, gaps, reg_pen = diagnostics()
-            feasibility_gaps.append(gaps)
-            if stop.active:
-                feasibility_criterion = stop.feasible(gaps)
-                if not feasibility_criterion and not return_errors:
-                    progress.iteration(it, gaps=gaps)  # the loss is not evaluated on infeasible iterates (Q10)
-                    continue
-            rec_errors.append(rec_error)
-            losses.append(0.5 * rec_error ** 2 + reg_pen)
-            progress.iteration(it, rec_errors[-1], losses[-1], abs(losses[-2] - losses[-1]) / losses[-2], gaps)
-            fired = stop.verdict(feasibility_criterion, losses)
-            if fired is not None:
-                satisfied_stopping_condition, message = True, fired
-                progress.converged(it, message)
-                break
-        else:
-            progress.exhausted()
-
-    if feasibility_tol and return_errors and final_gaps_known:
+    # ---- the fit: arithmetic trial, initial diagnostics, one of the four loops, the final feasibility -----------------------
+    rule = _ArithmeticRule(run, arithmetic, n_el_total, rank)
+    if rule.candidate:
+        rule.trial(min(_AUTO_EXACT_TRIAL_ITERATIONS, n_iter_max))
+    rec = _Record(run.diagnostics())
+    _choose_loop(run)(run, rule, rec)
+    if feasibility_tol and return_errors and rec.final_gaps_known:
         # the reference re-evaluates the gaps of the final state here: the state the last verdict was taken on
-        feasibility_criterion = _check_feasibility(feasibility_gaps[-1], feasibility_tol)
+        rec.feasible = _check_feasibility(rec.feasibility_gaps[-1], feasibility_tol)
     elif feasibility_tol and return_errors:
-        _, final_gaps, _ = diagnostics()
-        feasibility_criterion = _check_feasibility(final_gaps, feasibility_tol)
+        _, final_gaps, _ = run.diagnostics()
+        rec.feasible = _check_feasibility(final_gaps, feasibility_tol)
     elif not feasibility_tol:
-        feasibility_criterion = None
+        rec.feasible = None
 
     # ---- results back in the caller's array type ------------------------------------------------------------------
     cmf = CoupledMatrixFactorization((None, (out(eng.A), out.split(eng.B, row_ptr), out(eng.C))))
     if gather_A and group is not None:
-        # the one all-gather of a sharded run (SURVEY.md 8e): ranks hold different numbers of matrices, so the rows are
-        # padded to the largest share for the collective and trimmed afterwards.  The factorization returned stays this
-        # rank's (its rows of A, its B_i); the whole A rides along as `cmf.A_all`, this rank's rows being
+        # the one all-gather of a sharded run, with a count exchange of its own.  The factorization returned
+        # stays this rank's (its rows of A, its B_i); the whole A rides along as `cmf.A_all`, this rank's rows being
         # `cmf.A_all[cmf.rows_of_rank[0]:cmf.rows_of_rank[1]]`.
-        n_loc = torch.tensor([eng.A.shape[0]], dtype=torch.int64, device=eng.A.device)
-        counts = [torch.zeros_like(n_loc) for _ in range(world)]
-        dist.all_gather(counts, n_loc, group=group)
-        counts = [int(c.item()) for c in counts]
-        padded = torch.zeros((max(counts), eng.A.shape[1]), dtype=eng.A.dtype, device=eng.A.device)
-        padded[: eng.A.shape[0]] = eng.A
-        parts = [torch.empty_like(padded) for _ in range(world)]
-        dist.all_gather(parts, padded, group=group)
-        cmf.A_all = out(torch.cat([p[:c] for p, c in zip(parts, counts)], 0))
-        lo = sum(counts[:rank_id])
-        cmf.rows_of_rank = (lo, lo + counts[rank_id])
+        cmf.A_all = out(torch.cat(grp.gather_rows(eng.A, "A at the end"), 0))
+        cmf.rows_of_rank = grp.own_rows("A at the end")
     result = [cmf]
     if return_admm_vars:
-        auxes, duals = [[], [], []], [[], [], []]
-        for mode in range(3):
-            for k, reg in enumerate(native[mode]):
-                if reg.kind == _engine.PEN_EXTERNAL:
-                    auxes[mode].append(_aux_out(ext_aux[(mode, k)], out))
-                    duals[mode].append(out.split(reg.dual, row_ptr) if mode == 1 else out(reg.dual))
-                    continue
-                if reg.kind == _engine.PEN_PARAFAC2:
-                    auxes[mode].append((out.split(reg.aux, row_ptr), out(reg.aux2)))
-                else:
-                    auxes[mode].append(out.split(reg.aux, row_ptr) if mode == 1 else out(reg.aux))
-                duals[mode].append(out.split(reg.dual, row_ptr) if mode == 1 else out(reg.dual))
-        result.append(ADMMVars(auxes=tuple(auxes), duals=tuple(duals)))
+        result.append(_admm_vars_out(out, row_ptr, [
+            [(r.kind, ext_aux[(mode, k)] if r.kind == _engine.PEN_EXTERNAL else r.aux, r.aux2, r.dual)
+             for k, r in enumerate(native[mode])] for mode in range(3)]))
     if return_errors:
-        if not satisfied_stopping_condition and not (tol or absolute_tol):
-            satisfied_stopping_condition = None
-        result.append(DiagnosticMetrics(
-            rec_errors=rec_errors, feasibility_gaps=feasibility_gaps, regularized_loss=losses,
-            satisfied_stopping_condition=satisfied_stopping_condition,
-            satisfied_feasibility_condition=feasibility_criterion, message=message, n_iter=it + 1))
+        result.append(rec.metrics(rule_active=bool(tol or absolute_tol)))
     if _byproducts is not None and update_A:
         _byproducts["rhses"] = out(eng.rhses())
         _byproducts["cross_products"] = out(eng.cross_products())
     if hasattr(eng, "close"):
         eng.close()
-    if len(result) == 1:
-        return result[0]
-    return tuple(result)
+    return result[0] if len(result) == 1 else tuple(result)
 
 
 def _single_phase(mode, matrices, reg, cmf, aux_list, dual_list, l2_penalty, inner_n_iter_max, inner_tol,
                   feasibility_penalty_scale, constant_feasibility_penalty):
     """One call of one phase on the device, with the given ADMM variables as initial state."""
-    import copy
-
     if len(reg) != len(aux_list) or len(reg) != len(dual_list):
         raise ValueError("reg, aux and dual lists must have the same length")
     stack = []
     for r_k, aux, dual in zip(reg, aux_list, dual_list):
-        r_c = copy.copy(r_k)  # same penalty, initial state = the caller's variables
+        r_c = copy(r_k)  # same penalty, initial state = the caller's variables
         r_c.aux_init, r_c.dual_init = aux, dual
         stack.append(r_c)
     weights, (A, B_is, C) = cmf
@@ -1802,8 +1811,6 @@ _MULTISTART_KINDS = (_engine.PEN_NN, _engine.PEN_BOX, _engine.PEN_L1, _engine.PE
 
 def _cmf_kwargs(kwargs):
     """the keyword arguments of a cmf_aoadmm call as a complete dict of its parameters (TypeError for unknown ones)"""
-    import inspect
-
     bound = inspect.signature(cmf_aoadmm).bind(None, 1, **kwargs)
     bound.apply_defaults()
     kw = dict(bound.arguments)
@@ -1811,14 +1818,15 @@ def _cmf_kwargs(kwargs):
     return kw
 
 
-def _start_penalties(kw, matrices, rank, random_state):
-    """one start's initial state exactly as cmf_aoadmm draws it: factors, then aux of modes 0, 1, 2, then duals"""
-    cmf = initialize_cmf(matrices, rank, kw["init"], svd_fun=None, random_state=random_state, init_params=kw["init_params"])
+def _start_penalties(kw, matrices, rank, random_state, svd_fun=None, verbose=False):
+    """The one draw of a start, for cmf_aoadmm and the fused kernels alike, in the reference's order: the factors, then - the
+    penalty lists of modes that are not updated emptied first - the aux of modes 0, 1, 2, then the duals.  `kw`: cmf_aoadmm keywords."""
+    cmf = initialize_cmf(matrices, rank, kw["init"], svd_fun=svd_fun, random_state=random_state, init_params=kw["init_params"])
     regs = _parse_all_penalties(
         non_negative=kw["non_negative"], lower_bound=kw["lower_bound"], upper_bound=kw["upper_bound"],
         l2_norm_bound=kw["l2_norm_bound"], unimodal=kw["unimodal"], parafac2=kw["parafac2"], l1_penalty=kw["l1_penalty"],
         tv_penalty=kw["tv_penalty"], generalized_l2_penalty=kw["generalized_l2_penalty"], svd=kw["svd"], regs=kw["regs"],
-        dual_init=kw["dual_init"], aux_init=kw["aux_init"], verbose=False)
+        dual_init=kw["dual_init"], aux_init=kw["aux_init"], verbose=verbose)
     for mode, on in enumerate((kw["update_A"], kw["update_B_is"], kw["update_C"])):
         if not on:
             regs[mode] = []
@@ -1969,18 +1977,10 @@ def _multistart_fused(matrices, rank, random_states, kws, per_job_options=False)
 
         A, B, C = nxt(I), nxt(N), nxt(K)
         result = [CoupledMatrixFactorization((None, (out(A), out.split(B, row_ptr), out(C))))]
-        auxes_o, duals_o = [[], [], []], [[], [], []]
-        for mode in range(3):
-            for kind in kinds[mode]:
-                aux = nxt(rows[mode])
-                if kind == _engine.PEN_PARAFAC2:
-                    auxes_o[mode].append((out.split(aux, row_ptr), out(nxt(rank))))
-                else:
-                    auxes_o[mode].append(out.split(aux, row_ptr) if mode == 1 else out(aux))
-                dual = nxt(rows[mode])
-                duals_o[mode].append(out.split(dual, row_ptr) if mode == 1 else out(dual))
+        admm = [[(kind, nxt(rows[mode]), nxt(rank) if kind == _engine.PEN_PARAFAC2 else None, nxt(rows[mode]))
+                 for kind in kinds[mode]] for mode in range(3)]  # (aux, the Delta of a PARAFAC2, dual: the order of the state)
         if kw["return_admm_vars"]:
-            result.append(ADMMVars(auxes=tuple(auxes_o), duals=tuple(duals_o)))
+            result.append(_admm_vars_out(out, row_ptr, admm))
         if kw["return_errors"]:
             n = int(n_iter[s])
             d = diag[s, : n + 1]
@@ -1990,7 +1990,7 @@ def _multistart_fused(matrices, rank, random_states, kws, per_job_options=False)
                     for t in range(n + 1)]
             code = int(stop[s])
             satisfied = bool(code) if (tol or absolute_tol) else None
-            message = (_StopRule.RELATIVE if code == _engine.STOP_RELATIVE else _StopRule.ABSOLUTE) if code else _StopRule.EXHAUSTED
+            message = _StopRule.message_of(code)
             feasible = _check_feasibility(gaps[-1], feasibility_tol) if feasibility_tol else None
             result.append(DiagnosticMetrics(
                 rec_errors=[float(d[t, 0]) for t in kept], feasibility_gaps=gaps, regularized_loss=[float(d[t, 1]) for t in kept],
