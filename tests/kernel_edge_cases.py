@@ -2,6 +2,9 @@
 (csrc/parafac2als.hip) and the fused multi-start kernel (csrc/multistart.hip), and the fp64 checks that they are well posed.
 Shared by the GPU tests (tests/test_gpu_als_init.py, tests/test_gpu_parafac2_als.py, tests/test_gpu_multistart.py) and their
 CPU checks (tests/test_als_init_host.py, tests/test_parafac2_als_host.py, tests/test_multistart_host.py)."""
+import functools
+import zlib
+
 import numpy as np
 
 from tests import als_restatement as R
@@ -227,3 +230,178 @@ def rowchain_state(name):
     if c.get("inner_tol"):
         st.inner_tol = c["inner_tol"]
     return st
+
+
+# ---- the two passes over X: X C and [G | R] (csrc/contract.hip, csrc/xclds.hip; tests/test_gpu_contract.py) -----------------------
+# A case: J (rows per slab), K, rank, env (the MCL_* switches it sets), unaligned (X starts one element past a 16-byte boundary:
+# VEC = 1 although K % 4 = 0; fp32 only - a 16-bit X must be 8-byte aligned), A: the penalties of mode 0 - "nn" ([nn]: the fused
+# reductions in fp32 chains, GRAM = 1), "ridge" ([] with a ridge: fp64, GRAM = 2) or "both" (two runs), nt (a second run with
+# MCL_X_NT_MB=1: the non-temporal forms; needs N K 4 > 1 MiB), f32_only (the depth-8 LDS ring has no 16-bit twin), legB (the
+# real-valued leg runs it), twins (switch overlays whose results must equal the case's own bit for bit on the real-valued data;
+# None removes a switch).  Small problems get one 16-row block per wave from the planner; MCL_XC_WAVES=n (W below) makes waves of
+# many blocks, segments of up to 256 rows and waves of several segments.
+_JP8 = [0, 1, 15, 16, 17, 255, 256, 257]      # every slab length next to a block / segment edge; 817 rows, 54 blocks
+_JR7 = [300, 64, 41, 257, 0, 130, 400]        # 1192 rows: K >= 256 is more than 1 MiB
+_JW = [600, 40]                               # one slab spread over several waves
+_JBIG = [2100, 1500, 700, 130]                # 4430 rows: more than 1 MiB from K = 60 on
+_J1 = [1100]                                  # a single slab
+CONTRACT_RIDGE = 0.5
+
+
+def _cc(J, K, rank, A="nn", W=0, unaligned=False, nt=False, legB=False, f32_only=False, twins=(), **env):
+    e = {k: str(v) for k, v in env.items()}
+    if W:
+        e["MCL_XC_WAVES"] = str(W)
+    e.setdefault("MCL_EXACT", "0")  # the size-independent kernels, however small the case (tests/conftest.py: fast_kernels)
+    return dict(J=list(J), K=K, rank=rank, A=A, env=e, unaligned=unaligned, nt=nt, legB=legB, f32_only=f32_only, twins=list(twins))
+
+
+_NT = {"MCL_X_NT_MB": "1"}
+CONTRACT_CASES = {
+    # k_contract_xc<NB, VEC, KCT>: K that is no multiple of 256, an unaligned X, or MCL_XC_NOROW
+    "xc_nb1_kct2_k100": _cc(_JP8, 100, 1, W=3),
+    "xc_nb1_kct2_k90": _cc(_JP8, 90, 3, A="ridge"),
+    "xc_nb1_kct2_k33": _cc(_JP8, 33, 3),
+    "xc_nb1_kct2_k128_unaligned": _cc(_JR7, 128, 5, W=5, unaligned=True),
+    "xc_nb1_kct4_k200": _cc(_JR7, 200, 12, A="ridge", W=2),
+    "xc_nb1_kct4_k250": _cc(_JP8, 250, 16),
+    "xc_nb1_kct4_k256_unaligned": _cc(_JP8, 256, 16, unaligned=True),
+    "xc_nb1_kct4_k256_norow": _cc(_JP8, 256, 5, W=3, MCL_XC_NOROW=1),
+    "xc_nb1_kct0_k300": _cc(_JP8, 300, 16, W=3, legB=True),  # 5 chunks padded to 8; two slices of k_contract_xt, the second short
+    "xc_nb1_kct0_k301": _cc(_JR7, 301, 5),
+    "xc_nb1_kct0_k512_unaligned": _cc(_JP8, 512, 12, unaligned=True),
+    "xc_nb2_kct2_k100": _cc(_JP8, 100, 17, W=3, legB=True),
+    "xc_nb2_kct2_k66": _cc(_JR7, 66, 20),
+    "xc_nb2_kct2_k62": _cc(_JP8, 62, 17),
+    "xc_nb2_kct2_k64_unaligned": _cc(_JP8, 64, 32, unaligned=True),
+    "xc_nb2_kct0_k200": _cc(_JP8, 200, 32, A="ridge"),
+    "xc_nb2_kct0_k130": _cc(_JP8, 130, 20, W=6),
+    "xc_nb2_kct0_k256_unaligned": _cc(_JR7, 256, 17, unaligned=True),
+    "xc_nb4_k100": _cc(_JP8, 100, 33, W=3, legB=True),
+    "xc_nb4_k70": _cc(_JR7, 70, 40, A="ridge"),
+    "xc_nb4_k128_unaligned": _cc(_JP8, 128, 64, unaligned=True),
+    # a sweep-eligible shape whose fragment image of C is longer when the sweep is planned (4 chunks against 2)
+    "xc_sweep_k128_r20": _cc([300, 257, 130], 128, 20, W=2, legB=True, twins=[{"MCL_NO_SWEEP": "1"}]),
+    "xc_nosweep_k128_r20": _cc([300, 257, 130], 128, 20, W=2, MCL_NO_SWEEP=1),
+    # k_contract_xt at K <= 128 (KB = 1, 2 and NB = 2 at KB = 1), default planner: 279 waves, 70 row ranges (XCD-padded to 72)
+    "xt_kb1_nb1_k60": _cc(_JBIG, 60, 5, nt=True),
+    "xt_kb1_nb1_k60_depth2": _cc(_JBIG, 60, 5, nt=True, MCL_XT_DEPTH=2),
+    "xt_kb2_nb1_k100": _cc(_JBIG, 100, 12, nt=True, legB=True, twins=[{"MCL_XT_DEPTH": "2"}]),
+    "xt_kb2_nb1_k100_depth2": _cc(_JBIG, 100, 12, nt=True, MCL_XT_DEPTH=2),
+    "xt_kb1_nb2_k64": _cc(_JBIG, 64, 20, nt=True, W=9),
+    "xt_kb1_nb2_k64_depth2": _cc(_JBIG, 64, 20, nt=True, MCL_XT_DEPTH=2),
+    "xt_kb4_nb1_k300_depth2": _cc(_JR7, 300, 16, nt=True, W=5, MCL_XT_DEPTH=2),
+    # k_contract_xc_256<GRAM> (K = 256, rank <= 16) and its one-slot twin k_contract_xc_row<1, true, GRAM>.  Their sums run in
+    # different orders BY DESIGN (eight fp32 chains added as a tree in fp64 against four added pairwise in fp32): no bitwise pair
+    "xc256_r16": _cc(_JR7, 256, 16, A="both", W=5, nt=True, legB=True),
+    "xc256_r1_default_waves": _cc(_JP8, 256, 1),
+    "xc256_single_slab": _cc(_J1, 256, 16, W=7),
+    "xcrow_creg_r12": _cc(_JR7, 256, 12, A="both", W=3, nt=True, legB=True, MCL_XC_DEPTH1=1),
+    # k_contract_xc_row<NB, false, GRAM>
+    "xcrow_nb2_k256": _cc(_JR7, 256, 17, A="both", W=4, nt=True),
+    "xcrow_nb4_k256": _cc(_JR7, 256, 40, A="both", W=6, nt=True),
+    "xcrow_nb1_k768": _cc(_JP8, 768, 5, A="both", W=3, nt=True, legB=True),
+    "xcrow_nb1_k768_seg32": _cc(_JP8, 768, 12, W=3, MCL_SEG_ROWS=32),
+    "xcrow_nb2_k768": _cc(_JP8, 768, 20, A="both", W=2, nt=True, legB=True, MCL_XT_DEPTH=2),
+    "xcrow_nb4_k768": _cc(_JP8, 768, 48, A="both", W=1, nt=True),
+    "xcrow_nb2_k1536": _cc(_JW, 1536, 32, A="both", W=4, nt=True),
+    "xcrow_nb4_k512": _cc(_JP8, 512, 64, A="both", W=3, nt=True, legB=True, MCL_XT_DEPTH=2),
+    "xcrow_nb1_k1024_no_lds": _cc(_JP8, 1024, 16, A="both", W=3, nt=True, MCL_NO_XC_LDS=1),
+    # k_contract_xc_lds<NB, GRAM, XNT, DEPTH>: 1 .. 4 rounds of the depth-4 ring; depth 8 where K % 1024 = 0, else back to 4
+    "xclds_nb1_k512": _cc(_JP8, 512, 16, A="both", W=3, nt=True, legB=True, twins=[{"MCL_XC_LDS_DEPTH": "8"}]),
+    "xclds_nb1_k512_depth8_falls_back": _cc(_JP8, 512, 16, W=3, MCL_XC_LDS_DEPTH=8),
+    "xclds_nb1_k1024": _cc(_JP8, 1024, 12, A="both", W=3, nt=True, legB=True, twins=[{"MCL_XC_LDS_DEPTH": "8"}]),
+    "xclds_nb1_k1024_depth8": _cc(_JP8, 1024, 12, A="both", W=3, nt=True, f32_only=True, MCL_XC_LDS_DEPTH=8),
+    "xclds_nb1_k1536": _cc(_JW, 1536, 3, A="both", W=4, nt=True),
+    "xclds_nb1_k1536_depth8_falls_back": _cc(_JW, 1536, 3, W=4, MCL_XC_LDS_DEPTH=8),
+    "xclds_nb1_k2048": _cc(_JW, 2048, 16, A="both", W=2, nt=True),
+    "xclds_nb1_k2048_depth8": _cc(_JW, 2048, 16, A="both", W=2, nt=True, f32_only=True, MCL_XC_LDS_DEPTH=8),
+    "xclds_nb2_k512": _cc(_JP8, 512, 20, A="both", W=5, nt=True),
+    "xclds_nb2_k1024": _cc(_JP8, 1024, 32, A="both", W=3, nt=True, legB=True, twins=[{"MCL_XC_LDS_DEPTH": "8"}]),
+    "xclds_nb2_k1024_depth8": _cc(_JP8, 1024, 32, A="both", W=3, nt=True, f32_only=True, MCL_XC_LDS_DEPTH=8),
+    # the exact-products forms (MCL_EXACT=1): 1, 2, 8 and 9 chunks of 256 rows; N % 256 = 255, 1, 0, 1; K % 16 != 0
+    "exact_nb1_n255": _cc([100, 0, 155], 40, 5, legB=True, MCL_EXACT=1),
+    "exact_nb2_n257": _cc([256, 1], 24, 20, A="ridge", legB=True, MCL_EXACT=1),
+    "exact_nb4_n2048": _cc([1000, 1048], 20, 40, legB=True, MCL_EXACT=1),
+    "exact_nb1_n2049": _cc([1024, 1000, 25], 33, 16, A="ridge", MCL_EXACT=1),
+}
+
+# Built instantiations no dispatch can choose (kept: profiles/kernel_resources.json pins the kernel list).  Patterns over the names
+# tools/kernel_resources.py prints, `_h<TYPE, ` twins included; tests/test_contract_cases.py proves none is ever predicted.
+CONTRACT_UNREACHABLE = {
+    r"k_contract_xc(_h)?<(\w+, )?2, [14], 4>": "mcl_xc_chunks: at NB = 2 only two chunks of C fragments fit the registers (KCT = 2 or 0)",
+    r"k_contract_xc(_h)?<(\w+, )?4, [14], [24]>": "mcl_xc_chunks: at NB = 4 not even two chunks fit (KCT = 0 always)",
+    r"k_contract_xt(_h)?<(\w+, )?[124], [124], 1, 2, [012], true>": "launch_xt: the non-temporal load is the vector load (VEC = 4 only)",
+    r"k_contract_xt(_h)?<(\w+, )?1, 4, 1, 2, 2, true>": "launch_xt: the G-only launch (MODE = 2) does not read X",
+}
+
+
+def contract_runs():
+    """[(run name, case name, switches, 'nn' | 'ridge')]: every case, with A = both and nt expanded"""
+    out = []
+    for n, c in CONTRACT_CASES.items():
+        for a in (("nn", "ridge") if c["A"] == "both" else (c["A"],)):
+            for nt in ((False, True) if c["nt"] else (False,)):
+                out.append((n + ("/" + a if c["A"] == "both" else "") + ("/nt" if nt else ""), n, {**c["env"], **(_NT if nt else {})}, a))
+    return out
+
+
+def contract_x_types(case):
+    return ("f32",) if case["unaligned"] or case["f32_only"] else ("f32", "bf16", "f16")
+
+
+def contract_int_ranges(case):
+    """(xm, cm, bm, am): integer magnitudes of X, C, B, A - as large as keeps every sum of absolute products of the case below 2^24
+    by its worst case (and |x| <= 256: exact in bf16).  The conditions themselves are asserted on the data, not on this rule."""
+    J, K = case["J"], case["K"]
+    N, Jm = sum(J), max(J)
+    m, cap = [1, 1, 1, 1], [256, 16, 16, 4]
+
+    def ok(xm, cm, bm, am):
+        return max(K * xm * cm, N * xm * bm * am, N * (bm * am) ** 2, Jm * bm * K * xm * cm, Jm * bm * bm * K * cm * cm) < 2 ** 24
+
+    grown = True
+    while grown:
+        grown = False
+        for k in range(4):
+            t = list(m)
+            t[k] *= 2
+            if t[k] <= cap[k] and ok(*t):
+                m, grown = t, True
+    return tuple(m)
+
+
+@functools.lru_cache(maxsize=None)
+def contract_data(name, kind):
+    """X [N, K], A [I, r], B [N, r], C [K, r] as float64 arrays of fp32-representable values, and row_ptr.  kind 'int': small random
+    integers (contract_int_ranges); 'real': normal X and B, uniform A in [0.5, 1.5) and C in [-1, 1), rounded to fp32"""
+    c = CONTRACT_CASES[name]
+    J, K, r = c["J"], c["K"], c["rank"]
+    N, I = sum(J), len(J)
+    rng = np.random.RandomState(zlib.crc32(name.encode()) % (2 ** 31))
+    if kind == "int":
+        xm, cm, bm, am = contract_int_ranges(c)
+        f = lambda m, *s: rng.randint(-m, m + 1, size=s).astype(np.float64)
+        X, C, B, A = f(xm, N, K), f(cm, K, r), f(bm, N, r), f(am, I, r)
+    else:
+        f32 = lambda a: a.astype(np.float32).astype(np.float64)
+        X, C, B, A = f32(rng.standard_normal((N, K))), f32(rng.uniform(-1, 1, (K, r))), f32(rng.standard_normal((N, r))), f32(rng.uniform(0.5, 1.5, (I, r)))
+    return dict(X=X, A=A, B=B, C=C, row_ptr=np.concatenate([[0], np.cumsum(J)]).astype(np.int64))
+
+
+@functools.lru_cache(maxsize=None)
+def contract_reference(name, kind):
+    """fp64 NumPy reference of every by-product (exact on the integer data: every value is an integer far below 2^53), and the
+    sums of absolute products the bounds of both legs are stated in (suffix _abs)"""
+    d = contract_data(name, kind)
+    X, A, B, C, rp = d["X"], d["A"], d["B"], d["C"], d["row_ptr"]
+    I, r = A.shape
+    slab = np.repeat(np.arange(I), np.diff(rp))
+    Ba = B * A[slab]
+    out = dict(XC=X @ C, XC_abs=np.abs(X) @ np.abs(C), G=Ba.T @ Ba, G_abs=np.abs(Ba).T @ np.abs(Ba), R=X.T @ Ba, R_abs=np.abs(X).T @ np.abs(Ba))
+    seg = lambda M: np.stack([M[rp[i]:rp[i + 1]].sum(axis=0) for i in range(I)]) if I else np.zeros((0,) + M.shape[1:])
+    out["rhs"], out["rhs_abs"] = seg(B * out["XC"]), seg(np.abs(B) * out["XC_abs"])
+    CtC, CtC_abs = C.T @ C, np.abs(C).T @ np.abs(C)
+    out["Q"] = seg(B[:, :, None] * B[:, None, :]) * CtC
+    out["Q_abs"] = seg(np.abs(B)[:, :, None] * np.abs(B)[:, None, :]) * CtC_abs
+    return out
