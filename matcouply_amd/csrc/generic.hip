@@ -9,31 +9,9 @@
 #include <type_traits>
 
 #include "mcl_internal.h"
-#include "rows_mfma.h"
+#include "rows_stack.h"
 
 static __device__ __forceinline__ double wave_sum_d(double v) { return wave_sum(v); }  // DPP + readlane (rows_mfma.h)
-
-static __device__ __forceinline__ float prox_elem_g(int kind, int nonneg, float p0, float p1, float thr, float y) {
-    switch (kind) {
-        case MCL_PEN_NN: return fmaxf(y, 0.f);
-        case MCL_PEN_BOX: return fminf(fmaxf(y, p0), p1);
-        case MCL_PEN_L1:
-            if (nonneg) return fmaxf(y - thr, 0.f);
-            return copysignf(fmaxf(fabsf(y) - thr, 0.f), y);
-        default: return y;
-    }
-}
-
-static __device__ __forceinline__ double prox_elem_g(int kind, int nonneg, double p0, double p1, double thr, double y) {
-    switch (kind) {
-        case MCL_PEN_NN: return fmax(y, 0.0);
-        case MCL_PEN_BOX: return fmin(fmax(y, p0), p1);
-        case MCL_PEN_L1:
-            if (nonneg) return fmax(y - thr, 0.0);
-            return copysign(fmax(fabs(y) - thr, 0.0), y);
-        default: return y;
-    }
-}
 
 static ModeView view_of(mcl_context *c, int mode) {
     ModeView v{};
@@ -54,17 +32,6 @@ static ModeView view_of(mcl_context *c, int mode) {
 // All row kernels below use the tile / fragment layout of rows_mfma.h (coalesced 16-B accesses); products with a
 // wave-uniform r x r matrix (L^-1, Delta, T_i) run on the fp32 MFMA.
 // ---------------------------------------------------------------------------------------------------------
-#define TILE_PROLOGUE()                                                                                      \
-    MCL_GATE(mv.gate);                                                                                       \
-    const int lane = threadIdx.x & 63;                                                                       \
-    const int tile = blockIdx.x * 4 + (threadIdx.x >> 6);                                                    \
-    if (tile >= mv.n_tiles) return;                                                                          \
-    const int slab = __builtin_amdgcn_readfirstlane(mv.tile_slab[tile]);                                     \
-    const long row0 = __builtin_amdgcn_readfirstlane(mv.tile_row0[tile]);                                    \
-    const int nrows = __builtin_amdgcn_readfirstlane(mv.tile_nrows[tile]);                                   \
-    const int row16 = lane & 15, g = lane >> 4;                                                              \
-    (void)slab; (void)row16; (void)g
-
 #define FOR_ROW_BLOCKS()                                                                                     \
     _Pragma("unroll") for (int rb = 0; rb < 4; ++rb)                                                         \
         if (16 * rb < nrows)
@@ -75,23 +42,15 @@ __global__ __launch_bounds__(256) void k_rows_solve(ModeView mv, const float *__
                                                     const float *__restrict__ Arows, const float *__restrict__ Linv,
                                                     RegSet regs, int r, double *__restrict__ change_part) {
     // change_part != nullptr: per tile ||f_new - f_old||^2 (the inner stopping test, decomposition.py:100-107)
-    TILE_PROLOGUE();
+    ROW_TILE_PROLOGUE();
     double chg = 0.0;
     const float rho = mv.rho[slab];
     RowMat<NBR> L, D;
     L.load(Linv + (long)slab * r * r, r, lane);
-    int kpf2 = -1;
-    for (int k = 0; k < regs.n; ++k)
-        if (regs.kind[k] == MCL_PEN_PARAFAC2) kpf2 = k;
+    const int kpf2 = last_of_kind(regs, MCL_PEN_PARAFAC2);
     if (kpf2 >= 0) D.load(regs.aux2[kpf2], r, lane);
     float av[NBR][4];
-#pragma unroll
-    for (int h = 0; h < NBR; ++h)
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            const int col = 16 * h + 4 * g + v;
-            av[h][v] = (Arows != nullptr && col < r) ? Arows[(long)slab * r + col] : 1.f;
-        }
+    a_col_scale(Arows, slab, r, g, av);
     FOR_ROW_BLOCKS() {
         const bool ok = 16 * rb + row16 < nrows;
         const long j = row0 + 16 * rb + (ok ? row16 : 0);
@@ -103,21 +62,13 @@ __global__ __launch_bounds__(256) void k_rows_solve(ModeView mv, const float *__
             for (int v = 0; v < 4; ++v) t[h][v] *= av[h][v];
         }
         for (int k = 0; k < regs.n; ++k) {
-            f32x4 z[NBR];
+            f32x4 z[NBR], u[NBR];
 #pragma unroll
             for (int h = 0; h < NBR; ++h) z[h] = row_ld4<VEC>(regs.aux[k], j, 16 * h + 4 * g, ok, r);
-            if (k == kpf2) {
-                f32x4 pz[NBR];
-                D.apply(z, pz);
+            if (k == kpf2) times_delta(D, z);
 #pragma unroll
-                for (int h = 0; h < NBR; ++h) z[h] = pz[h];
-            }
-#pragma unroll
-            for (int h = 0; h < NBR; ++h) {
-                const f32x4 u = row_ld4<VEC>(regs.dual[k], j, 16 * h + 4 * g, ok, r);
-#pragma unroll
-                for (int v = 0; v < 4; ++v) t[h][v] = fmaf(rho, z[h][v] - u[v], t[h][v]);
-            }
+            for (int h = 0; h < NBR; ++h) u[h] = row_ld4<VEC>(regs.dual[k], j, 16 * h + 4 * g, ok, r);
+            rhs_add(rho, z, u, t);
         }
         L.apply(t, f);
         if (change_part != nullptr) {
@@ -158,41 +109,21 @@ __global__ __launch_bounds__(256) void k_rows_solve_stats(ModeView mv, const flo
                                                           RegSet regs, int r, double *__restrict__ stat_gram,
                                                           double *__restrict__ stat_colsq,
                                                           const double *__restrict__ Linv64 = nullptr) {
-    typedef double f64x4s __attribute__((ext_vector_type(4)));
     typedef RowArith<R64> RA;
-    __shared__ double ytile[R64 ? 4 * 16 * 17 : 1];  // R64: one padded 16 x 16 fp64 tile per wave (row -> column layout of Y)
-    TILE_PROLOGUE();
+    __shared__ double ytile[YGram<NBR, R64>::LDS_DOUBLES];  // R64: one padded 16 x 16 fp64 tile per wave (row -> column layout of Y)
+    ROW_TILE_PROLOGUE();
     const float rho = mv.rho[slab];
     typename RA::template Mat<NBR> L, D;
-    if constexpr (R64) L.load(Linv64 + (long)slab * r * r, r, lane);
-    else L.load(Linv + (long)slab * r * r, r, lane);
-    int kpf2 = -1;
-    for (int k = 0; k < regs.n; ++k)
-        if (regs.kind[k] == MCL_PEN_PARAFAC2) kpf2 = k;
+    load_slab_mat<R64>(L, Linv, Linv64, slab, r, lane);
+    const int kpf2 = last_of_kind(regs, MCL_PEN_PARAFAC2);
     if (kpf2 >= 0) D.load(regs.aux2[kpf2], r, lane);
     float av[NBR][4];
+    a_col_scale(Arows, slab, r, g, av);
+    YGram<NBR, R64> gram;
+    gram.clear(row16, g);
+    ColSq<NBR> csq[MCL_MAX_REGS];
 #pragma unroll
-    for (int h = 0; h < NBR; ++h)
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            const int col = 16 * h + 4 * g + v;
-            av[h][v] = (Arows != nullptr && col < r) ? Arows[(long)slab * r + col] : 1.f;
-        }
-    typename std::conditional<R64, double, float>::type bsel[4];
-#pragma unroll
-    for (int v = 0; v < 4; ++v) bsel[v] = (row16 == 4 * g + v) ? 1.f : 0.f;
-    f64x4s accS[NBR][NBR];
-#pragma unroll
-    for (int a = 0; a < NBR; ++a)
-#pragma unroll
-        for (int b = 0; b < NBR; ++b) accS[a][b] = f64x4s{0.0, 0.0, 0.0, 0.0};
-    double csq[MCL_MAX_REGS][NBR][4];
-#pragma unroll
-    for (int k = 0; k < MCL_MAX_REGS; ++k)
-#pragma unroll
-        for (int h = 0; h < NBR; ++h)
-#pragma unroll
-            for (int v = 0; v < 4; ++v) csq[k][h][v] = 0.0;
+    for (int k = 0; k < MCL_MAX_REGS; ++k) csq[k].clear();
     FOR_ROW_BLOCKS() {
         const bool ok = 16 * rb + row16 < nrows;
         const long j = row0 + 16 * rb + (ok ? row16 : 0);
@@ -209,18 +140,10 @@ __global__ __launch_bounds__(256) void k_rows_solve_stats(ModeView mv, const flo
                 f32x4 z[NBR];
 #pragma unroll
                 for (int h = 0; h < NBR; ++h) z[h] = (row_ld4<VEC>(regs.aux[k], j, 16 * h + 4 * g, ok, r));
-                if (k == kpf2) {
-                    f32x4 pz[NBR];
-                    D.apply(z, pz);
+                if (k == kpf2) times_delta(D, z);
 #pragma unroll
-                    for (int h = 0; h < NBR; ++h) z[h] = pz[h];
-                }
-#pragma unroll
-                for (int h = 0; h < NBR; ++h) {
-                    ukeep[k][h] = (row_ld4<VEC>(regs.dual[k], j, 16 * h + 4 * g, ok, r));
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) t[h][v] = fmaf(rho, z[h][v] - ukeep[k][h][v], t[h][v]);
-                }
+                for (int h = 0; h < NBR; ++h) ukeep[k][h] = (row_ld4<VEC>(regs.dual[k], j, 16 * h + 4 * g, ok, r));
+                rhs_add(rho, z, ukeep[k], t);
             }
         }
         L.apply(t, f);
@@ -231,77 +154,15 @@ __global__ __launch_bounds__(256) void k_rows_solve_stats(ModeView mv, const flo
 #pragma unroll
         for (int k = 0; k < MCL_MAX_REGS; ++k) {
             if (k < regs.n) {
-                if (regs.kind[k] == MCL_PEN_L2BALL) {
-#pragma unroll
-                    for (int h = 0; h < NBR; ++h)
-#pragma unroll
-                        for (int v = 0; v < 4; ++v) {
-                            float y = f[h][v] + ukeep[k][h][v];
-                            if (regs.nonneg[k]) y = fmaxf(y, 0.f);
-                            if (ok) csq[k][h][v] += (double)y * (double)y;
-                        }
-                } else if (k == kpf2) {
-                    double yt[NBR][4];
-#pragma unroll
-                    for (int nb = 0; nb < NBR; ++nb) {
-                        if constexpr (R64) {  // exact fp64 sum, transposed through the wave's LDS tile (the fp64 matrix pipe
-                            // is the scarce unit of these passes: 44 TFLOP/s at best, tools/mfma64_rate.hip):
-                            // lane (q, i16) reg w = Y[q + 4w][16nb + i16]
-                            double *yl = ytile + (threadIdx.x >> 6) * (16 * 17);
-#pragma unroll
-                            for (int v = 0; v < 4; ++v)
-                                yl[row16 * 17 + 4 * g + v] = ok ? (double)f[nb][v] + (double)ukeep[k][nb][v] : 0.0;
-#pragma unroll
-                            for (int w = 0; w < 4; ++w) yt[nb][w] = yl[(g + 4 * w) * 17 + row16];
-                        } else {
-                            f32x4 tr = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                            for (int v = 0; v < 4; ++v) {
-                                const float y = ok ? f[nb][v] + ukeep[k][nb][v] : 0.f;
-                                tr = MFMA16(y, bsel[v], tr);  // COL layout: lane (q, i16) reg w = Y[4q + w][16nb + i16]
-                            }
-#pragma unroll
-                            for (int w = 0; w < 4; ++w) yt[nb][w] = (double)tr[w];
-                        }
-                    }
-#pragma unroll
-                    for (int w = 0; w < 4; ++w)
-#pragma unroll
-                        for (int a = 0; a < NBR; ++a)
-#pragma unroll
-                            for (int b = 0; b < NBR; ++b)
-                                accS[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(yt[a][w], yt[b][w], accS[a][b], 0, 0, 0);
-                }
+                if (regs.kind[k] == MCL_PEN_L2BALL) csq[k].add(f, ukeep[k], regs.nonneg[k], ok);
+                else if (k == kpf2) gram.add(f, ukeep[k], ok, ytile, row16, g);
             }
         }
     }
-    constexpr int W = 16 * NBR;
-    if (kpf2 >= 0) {  // D layout of the f64 MFMA: col = l & 15, row = (l >> 4) + 4 reg
-        double *out = stat_gram + (long)tile * W * W;
+    if (kpf2 >= 0) gram.store(stat_gram, tile, row16, g);
 #pragma unroll
-        for (int a = 0; a < NBR; ++a)
-#pragma unroll
-            for (int b = 0; b < NBR; ++b)
-#pragma unroll
-                for (int v = 0; v < 4; ++v) out[(16 * a + g + 4 * v) * W + 16 * b + row16] = accS[a][b][v];
-    }
-#pragma unroll
-    for (int k = 0; k < MCL_MAX_REGS; ++k) {
-        if (k < regs.n && regs.kind[k] == MCL_PEN_L2BALL) {
-#pragma unroll
-            for (int h = 0; h < NBR; ++h)
-#pragma unroll
-                for (int v = 0; v < 4; ++v) {
-                    double sq = csq[k][h][v];
-                    sq += __shfl_xor(sq, 1);
-                    sq += __shfl_xor(sq, 2);
-                    sq += __shfl_xor(sq, 4);
-                    sq += __shfl_xor(sq, 8);
-                    const int col = 16 * h + 4 * g + v;
-                    if (row16 == 0 && col < r) stat_colsq[((long)tile * MCL_MAX_REGS + k) * r + col] = sq;
-                }
-        }
-    }
+    for (int k = 0; k < MCL_MAX_REGS; ++k)
+        if (k < regs.n && regs.kind[k] == MCL_PEN_L2BALL) csq[k].reduce_store(stat_colsq, tile, k, r, row16, g);
 }
 
 // per-slab sums of the per-tile statistics, fixed order: S[slab] (natural r x r layout) and colsq[k][slab]
@@ -370,7 +231,7 @@ __global__ __launch_bounds__(256) void k_A_rows_prox(const float *__restrict__ r
     if (e >= (long)I * r) return;
     const float rho = rhoA[e / r];
     const float f = A[e], u = regs.dual[k][e];
-    const float z = prox_elem_g(regs.kind[k], regs.nonneg[k], regs.p0[k], regs.p1[k], regs.p0[k] / rho, f + u);
+    const float z = prox_elem(regs.kind[k], regs.nonneg[k], regs.p0[k], regs.p1[k], regs.p0[k] / rho, f + u);
     regs.aux[k][e] = z;
     regs.dual[k][e] = f - (z - u);
 }
@@ -418,7 +279,7 @@ __global__ __launch_bounds__(256) void k_inner_check(int begin, const int *__res
 // row-separable prox + dual update of penalty k (generic path)
 template <int NBR, bool VEC>
 __global__ __launch_bounds__(256) void k_rows_prox_rowsep(ModeView mv, RegSet regs, int k, int r) {
-    TILE_PROLOGUE();
+    ROW_TILE_PROLOGUE();
     const float rho = mv.rho[slab];
     const float thr = regs.p0[k] / rho;
     FOR_ROW_BLOCKS() {
@@ -431,7 +292,7 @@ __global__ __launch_bounds__(256) void k_rows_prox_rowsep(ModeView mv, RegSet re
             f32x4 u = row_ld4<VEC>(regs.dual[k], j, col, ok, r), z;
 #pragma unroll
             for (int v = 0; v < 4; ++v) {
-                z[v] = prox_elem_g(regs.kind[k], regs.nonneg[k], regs.p0[k], regs.p1[k], thr, f[v] + u[v]);
+                z[v] = prox_elem(regs.kind[k], regs.nonneg[k], regs.p0[k], regs.p1[k], thr, f[v] + u[v]);
                 u[v] = f[v] - (z[v] - u[v]);
             }
             row_st4<VEC>(regs.aux[k], j, col, ok, r, z);
@@ -470,7 +331,7 @@ __global__ __launch_bounds__(256) void k_slab_colsq(const int *__restrict__ ext,
 template <int NBR, bool VEC>
 __global__ __launch_bounds__(256) void k_rows_l2ball(ModeView mv, RegSet regs, int k, int r,
                                                      const double *__restrict__ colsq) {
-    TILE_PROLOGUE();
+    ROW_TILE_PROLOGUE();
     const float bound = regs.p0[k];
     float scale[NBR][4];
 #pragma unroll
@@ -1550,7 +1411,7 @@ __global__ __launch_bounds__(64 * NsShape<NB>::SPW + ((TILES && NB == 1) ? 64 : 
 template <int NBR, bool VEC>
 __global__ __launch_bounds__(256) void k_pf2_apply(ModeView mv, const float *__restrict__ U, const float *__restrict__ T,
                                                    float *__restrict__ P, int r) {
-    TILE_PROLOGUE();
+    ROW_TILE_PROLOGUE();
     RowMat<NBR> Ts;
     Ts.load(T + (long)slab * r * r, r, lane);
     FOR_ROW_BLOCKS() {
@@ -1624,7 +1485,7 @@ __global__ void k_pf2_delta(const float *__restrict__ red, int r, float *__restr
 // dual update of the PARAFAC2 penalty: U = F - (P Delta - U)
 template <int NBR, bool VEC>
 __global__ __launch_bounds__(256) void k_rows_pf2_dual(ModeView mv, RegSet regs, int k, int r) {
-    TILE_PROLOGUE();
+    ROW_TILE_PROLOGUE();
     RowMat<NBR> D;
     D.load(regs.aux2[k], r, lane);
     FOR_ROW_BLOCKS() {
@@ -1649,7 +1510,7 @@ __global__ __launch_bounds__(256) void k_rows_pf2_dual(ModeView mv, RegSet regs,
 // plain dual update of penalty k: U = F - (Z - U)   (decomposition.py:282-285)
 template <int NBR, bool VEC>
 __global__ __launch_bounds__(256) void k_rows_dual(ModeView mv, RegSet regs, int k, int r) {
-    TILE_PROLOGUE();
+    ROW_TILE_PROLOGUE();
     FOR_ROW_BLOCKS() {
         const bool ok = 16 * rb + row16 < nrows;
         const long j = row0 + 16 * rb + (ok ? row16 : 0);
@@ -1678,18 +1539,14 @@ __global__ __launch_bounds__(256) void k_rows_finish_fused(ModeView mv, RegSet r
                                                            double *__restrict__ diag_tile, int want_diag,
                                                            const double *__restrict__ T64 = nullptr) {
     typedef RowArith<R64> RA;  // R64: the r x r products on the fp64 MFMA, exact Y = F + U (see k_rows_solve_stats)
-    TILE_PROLOGUE();
-    double nf = 0.0, na = 0.0, gap[MCL_MAX_REGS];  // per-tile diagnostics (same sums as k_rows_diag)
-#pragma unroll
-    for (int k = 0; k < MCL_MAX_REGS; ++k) gap[k] = 0.0;
+    ROW_TILE_PROLOGUE();
+    TileDiag diag;
+    diag.clear();
     const float rho = mv.rho[slab];
-    int kpf2 = -1;
-    for (int k = 0; k < regs.n; ++k)
-        if (regs.kind[k] == MCL_PEN_PARAFAC2) kpf2 = k;
+    const int kpf2 = last_of_kind(regs, MCL_PEN_PARAFAC2);
     typename RA::template Mat<NBR> Ts, D;
     if (kpf2 >= 0) {
-        if constexpr (R64) Ts.load(T64 + (long)slab * r * r, r, lane);
-        else Ts.load(T + (long)slab * r * r, r, lane);
+        load_slab_mat<R64>(Ts, T, T64, slab, r, lane);
         D.load(regs.aux2[kpf2], r, lane);
     }
     FOR_ROW_BLOCKS() {
@@ -1697,94 +1554,31 @@ __global__ __launch_bounds__(256) void k_rows_finish_fused(ModeView mv, RegSet r
         const long j = row0 + 16 * rb + (ok ? row16 : 0);
         f32x4 f[NBR];
 #pragma unroll
-        for (int h = 0; h < NBR; ++h) {
-            f[h] = (row_ld4<VEC>(mv.F, j, 16 * h + 4 * g, ok, r));  // zeros for padding rows / columns
-            if (want_diag) {
-#pragma unroll
-                for (int v = 0; v < 4; ++v) {
-                    nf += (double)f[h][v] * (double)f[h][v];
-                    na += fabs((double)f[h][v]);
-                }
-            }
-        }
+        for (int h = 0; h < NBR; ++h) f[h] = (row_ld4<VEC>(mv.F, j, 16 * h + 4 * g, ok, r));  // zeros for padding rows / columns
+        if (want_diag) diag.add_f(f);
 #pragma unroll
         for (int k = 0; k < MCL_MAX_REGS; ++k) {
             if (k >= regs.n) continue;
-            const int kind = regs.kind[k];
-            f32x4 u[NBR], z[NBR], zg[NBR];  // zg: what the feasibility gap is measured against (P Delta for PARAFAC2)
+            const int cls = class_of(regs.kind[k]);
+            f32x4 u[NBR], z[NBR], zg[NBR];
 #pragma unroll
             for (int h = 0; h < NBR; ++h) u[h] = (row_ld4<VEC>(regs.dual[k], j, 16 * h + 4 * g, ok, r));
-            if (kind == MCL_PEN_PARAFAC2) {
-                typename RA::Y y[NBR], pw[NBR];
-                f32x4 pd[NBR];
-#pragma unroll
-                for (int h = 0; h < NBR; ++h) y[h] = RA::ysum(f[h], u[h]);
-                Ts.apply(y, pw);   // P = Y T_i      (the aux variable)
-                D.apply(pw, pd);   // P Delta        (what the dual is measured against)
-#pragma unroll
-                for (int h = 0; h < NBR; ++h) {
-                    z[h] = RA::narrow(pw[h]);
-                    zg[h] = pd[h];
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) u[h][v] = f[h][v] - (pd[h][v] - u[h][v]);
-                }
-            } else if (kind == MCL_PEN_UNIMODAL) {  // aux rows already written by the column regressions
-#pragma unroll
-                for (int h = 0; h < NBR; ++h) {
-                    z[h] = (row_ld4<VEC>(regs.aux[k], j, 16 * h + 4 * g, ok, r));
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) u[h][v] = f[h][v] - (z[h][v] - u[h][v]);
-                }
-            } else if (kind == MCL_PEN_L2BALL) {
-                const float bound = regs.p0[k];
-#pragma unroll
-                for (int h = 0; h < NBR; ++h)
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) {
-                        const int col = 16 * h + 4 * g + v;
-                        const float nrm = (col < r) ? (float)sqrt(colsq[((long)k * mv.n_slabs + slab) * r + col]) : 1.f;
-                        float y = f[h][v] + u[h][v];
-                        if (regs.nonneg[k]) y = fmaxf(y, 0.f);
-                        z[h][v] = l2_scaled(y, bound / fmaxf(nrm, bound));
-                        u[h][v] = f[h][v] - (z[h][v] - u[h][v]);
-                    }
-            } else {
-                const float thr = regs.p0[k] / rho;
-#pragma unroll
-                for (int h = 0; h < NBR; ++h)
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) {
-                        z[h][v] = prox_elem_g(kind, regs.nonneg[k], regs.p0[k], regs.p1[k], thr, f[h][v] + u[h][v]);
-                        u[h][v] = f[h][v] - (z[h][v] - u[h][v]);
-                    }
-            }
+            // any number of L2 balls here, so a ball's scales are formed per element (the chained kernels hoist their one ball's)
+            const auto aux_rows = [&](int h) ROWS_INLINE { return row_ld4<VEC>(regs.aux[k], j, 16 * h + 4 * g, ok, r); };
+            const auto l2_scale = [&](int h, int v) ROWS_INLINE {
+                return l2_ball_scale(regs, k, colsq, mv.n_slabs, slab, r, 16 * h + 4 * g + v);
+            };
+            stack_prox<RA, NBR>(cls, regs, k, rho, Ts, D, f, u, aux_rows, l2_scale, z, zg);
+            dual_step(f, zg, u);
 #pragma unroll
             for (int h = 0; h < NBR; ++h) {
-                if (kind != MCL_PEN_UNIMODAL) row_st4<VEC>(regs.aux[k], j, 16 * h + 4 * g, ok, r, z[h]);
+                if (cls != CLS_UNI) row_st4<VEC>(regs.aux[k], j, 16 * h + 4 * g, ok, r, z[h]);
                 row_st4<VEC>(regs.dual[k], j, 16 * h + 4 * g, ok, r, u[h]);
-                if (kind != MCL_PEN_PARAFAC2) zg[h] = z[h];
-                if (want_diag)
-#pragma unroll
-                for (int v = 0; v < 4; ++v) {
-                    const bool valid = ok && (16 * h + 4 * g + v < r);
-                    const double dlt = valid ? (double)zg[h][v] - (double)f[h][v] : 0.0;
-                    gap[k] += dlt * dlt;
-                }
             }
+            if (want_diag) diag.add_gap(k, zg, f, ok, r, g);
         }
     }
-    if (!want_diag) return;
-    nf = wave_sum_d(nf);
-    na = wave_sum_d(na);
-#pragma unroll
-    for (int k = 0; k < MCL_MAX_REGS; ++k) gap[k] = wave_sum_d(gap[k]);
-    if (lane == 0) {
-        double *o = diag_tile + (long)tile * DIAG_COLS;
-        o[0] = nf;
-        o[1] = na;
-#pragma unroll
-        for (int k = 0; k < MCL_MAX_REGS; ++k) o[2 + k] = gap[k];
-    }
+    if (want_diag) diag.store(diag_tile, tile, lane);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1806,61 +1600,27 @@ __global__ __launch_bounds__(256) void k_rows_finish_solve_stats(ModeView mv, co
                                                                  double *__restrict__ stat_colsq,
                                                                  const double *__restrict__ Linv64 = nullptr,
                                                                  const double *__restrict__ T64 = nullptr) {
-    typedef double f64x4s __attribute__((ext_vector_type(4)));
     typedef RowArith<R64> RA;  // R64: the r x r products on the fp64 MFMA, exact Y = F + U (see k_rows_solve_stats)
-    __shared__ double ytile[R64 ? 4 * 16 * 17 : 1];  // R64: one padded 16 x 16 fp64 tile per wave (row -> column layout of Y)
-    TILE_PROLOGUE();
+    __shared__ double ytile[YGram<NBR, R64>::LDS_DOUBLES];  // R64: one padded 16 x 16 fp64 tile per wave (row -> column layout of Y)
+    ROW_TILE_PROLOGUE();
     const float rho = mv.rho[slab];
-    int kpf2 = -1;
-    for (int k = 0; k < regs.n; ++k)
-        if (regs.kind[k] == MCL_PEN_PARAFAC2) kpf2 = k;
+    const int kpf2 = last_of_kind(regs, MCL_PEN_PARAFAC2);
     typename RA::template Mat<NBR> L, Ts, D;
-    if constexpr (R64) L.load(Linv64 + (long)slab * r * r, r, lane);
-    else L.load(Linv + (long)slab * r * r, r, lane);
+    load_slab_mat<R64>(L, Linv, Linv64, slab, r, lane);
     if (kpf2 >= 0) {
-        if constexpr (R64) Ts.load(T64 + (long)slab * r * r, r, lane);
-        else Ts.load(T + (long)slab * r * r, r, lane);
+        load_slab_mat<R64>(Ts, T, T64, slab, r, lane);
         D.load(regs.aux2[kpf2], r, lane);
     }
-    float av[NBR][4];
-#pragma unroll
-    for (int h = 0; h < NBR; ++h)
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            const int col = 16 * h + 4 * g + v;
-            av[h][v] = (Arows != nullptr && col < r) ? Arows[(long)slab * r + col] : 1.f;
-        }
+    float av[NBR][4], l2s[NBR][4];
+    a_col_scale(Arows, slab, r, g, av);
     // L2-ball scale factors of iteration t (from the per-slab column norms); the host chains stacks with at most ONE
     // L2 ball (register budget: two waves per SIMD at rank 32)
-    int kl2 = -1;
-    for (int k = 0; k < regs.n; ++k)
-        if (regs.kind[k] == MCL_PEN_L2BALL) kl2 = k;
-    float l2s[NBR][4];
-#pragma unroll
-    for (int h = 0; h < NBR; ++h)
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            l2s[h][v] = 1.f;
-            if (kl2 >= 0) {
-                const int col = 16 * h + 4 * g + v;
-                const float bound = regs.p0[kl2];
-                const float nrm = (col < r) ? (float)sqrt(colsq[((long)kl2 * mv.n_slabs + slab) * r + col]) : 1.f;
-                l2s[h][v] = bound / fmaxf(nrm, bound);
-            }
-        }
-    typename std::conditional<R64, double, float>::type bsel[4];
-#pragma unroll
-    for (int v = 0; v < 4; ++v) bsel[v] = (row16 == 4 * g + v) ? 1.f : 0.f;
-    f64x4s accS[NBR][NBR];
-#pragma unroll
-    for (int a = 0; a < NBR; ++a)
-#pragma unroll
-        for (int b = 0; b < NBR; ++b) accS[a][b] = f64x4s{0.0, 0.0, 0.0, 0.0};
-    double csq[NBR][4];
-#pragma unroll
-    for (int h = 0; h < NBR; ++h)
-#pragma unroll
-        for (int v = 0; v < 4; ++v) csq[h][v] = 0.0;
+    const int kl2 = last_of_kind(regs, MCL_PEN_L2BALL);
+    l2_ball_scales(regs, kl2, colsq, mv.n_slabs, slab, r, g, l2s);
+    YGram<NBR, R64> gram;
+    gram.clear(row16, g);
+    ColSq<NBR> csq;
+    csq.clear();
     FOR_ROW_BLOCKS() {
         const bool ok = 16 * rb + row16 < nrows;
         const long j = row0 + 16 * rb + (ok ? row16 : 0);
@@ -1872,121 +1632,36 @@ __global__ __launch_bounds__(256) void k_rows_finish_solve_stats(ModeView mv, co
 #pragma unroll
             for (int v = 0; v < 4; ++v) t[h][v] *= av[h][v];
         }
-        // ---- iteration t: prox + dual of every penalty (same arithmetic as k_rows_finish_fused)
+        // ---- iteration t: prox + dual of every penalty
 #pragma unroll
         for (int k = 0; k < MCL_MAX_REGS; ++k) {
             if (k >= regs.n) continue;
-            const int kind = regs.kind[k];
-            f32x4 u[NBR], zg[NBR];
+            const int cls = class_of(regs.kind[k]);
+            f32x4 u[NBR], z[NBR], zg[NBR];
 #pragma unroll
             for (int h = 0; h < NBR; ++h) u[h] = (row_ld4<VEC>(regs.dual[k], j, 16 * h + 4 * g, ok, r));
-            if (kind == MCL_PEN_PARAFAC2) {
-                typename RA::Y y[NBR], pz[NBR];
-#pragma unroll
-                for (int h = 0; h < NBR; ++h) y[h] = RA::ysum(f[h], u[h]);
-                Ts.apply(y, pz);   // P = Y T_i
-                D.apply(pz, zg);   // P Delta
-            } else if (kind == MCL_PEN_UNIMODAL) {  // aux rows written by the column regressions
-#pragma unroll
-                for (int h = 0; h < NBR; ++h) zg[h] = (row_ld4<VEC>(regs.aux[k], j, 16 * h + 4 * g, ok, r));
-            } else if (kind == MCL_PEN_L2BALL) {
-#pragma unroll
-                for (int h = 0; h < NBR; ++h)
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) {
-                        float y = f[h][v] + u[h][v];
-                        if (regs.nonneg[k]) y = fmaxf(y, 0.f);
-                        zg[h][v] = l2_scaled(y, l2s[h][v]);
-                    }
-            } else {
-                const float thr = regs.p0[k] / rho;
-#pragma unroll
-                for (int h = 0; h < NBR; ++h)
-#pragma unroll
-                    for (int v = 0; v < 4; ++v)
-                        zg[h][v] = prox_elem_g(kind, regs.nonneg[k], regs.p0[k], regs.p1[k], thr, f[h][v] + u[h][v]);
-            }
+            const auto aux_rows = [&](int h) ROWS_INLINE { return row_ld4<VEC>(regs.aux[k], j, 16 * h + 4 * g, ok, r); };
+            const auto l2_scale = [&](int h, int v) ROWS_INLINE { return l2s[h][v]; };
+            stack_prox<RA, NBR>(cls, regs, k, rho, Ts, D, f, u, aux_rows, l2_scale, z, zg);
+            dual_step(f, zg, u);
+            rhs_add(rho, zg, u, t);
 #pragma unroll
             for (int h = 0; h < NBR; ++h) {
-#pragma unroll
-                for (int v = 0; v < 4; ++v) {
-                    u[h][v] = f[h][v] - (zg[h][v] - u[h][v]);
-                    t[h][v] = fmaf(rho, zg[h][v] - u[h][v], t[h][v]);
-                }
                 row_st4<VEC>(regs.dual[k], j, 16 * h + 4 * g, ok, r, u[h]);
                 if (k == kpf2) upf[h] = u[h];
                 if (k == kl2) ul2[h] = u[h];
             }
         }
-        // ---- iteration t + 1: solve, store, statistics of the new rows (same arithmetic as k_rows_solve_stats)
+        // ---- iteration t + 1: solve, store, statistics of the new rows
         f32x4 fn[NBR];
         L.apply(t, fn);
 #pragma unroll
         for (int h = 0; h < NBR; ++h) row_st4<VEC>(mv.F, j, 16 * h + 4 * g, ok, r, fn[h]);
-        if (kl2 >= 0) {
-#pragma unroll
-            for (int h = 0; h < NBR; ++h)
-#pragma unroll
-                for (int v = 0; v < 4; ++v) {
-                    float y = fn[h][v] + ul2[h][v];
-                    if (regs.nonneg[kl2]) y = fmaxf(y, 0.f);
-                    if (ok) csq[h][v] += (double)y * (double)y;
-                }
-        }
-        if (kpf2 >= 0) {
-            double yt[NBR][4];
-#pragma unroll
-            for (int nb = 0; nb < NBR; ++nb) {
-                if constexpr (R64) {  // exact fp64 sum, transposed through the wave's LDS tile: lane (q, i16) reg w = Y[q + 4w][16nb + i16]
-                    double *yl = ytile + (threadIdx.x >> 6) * (16 * 17);
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) yl[row16 * 17 + 4 * g + v] = ok ? (double)fn[nb][v] + (double)upf[nb][v] : 0.0;
-#pragma unroll
-                    for (int w = 0; w < 4; ++w) yt[nb][w] = yl[(g + 4 * w) * 17 + row16];
-                } else {
-                    f32x4 tr = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) {
-                        const float y = ok ? fn[nb][v] + upf[nb][v] : 0.f;
-                        tr = MFMA16(y, bsel[v], tr);  // COL layout: lane (q, i16) reg w = Y[4q + w][16nb + i16]
-                    }
-#pragma unroll
-                    for (int w = 0; w < 4; ++w) yt[nb][w] = (double)tr[w];
-                }
-            }
-#pragma unroll
-            for (int w = 0; w < 4; ++w)
-#pragma unroll
-                for (int a = 0; a < NBR; ++a)
-#pragma unroll
-                    for (int b = 0; b < NBR; ++b)
-                        accS[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(yt[a][w], yt[b][w], accS[a][b], 0, 0, 0);
-        }
+        if (kl2 >= 0) csq.add(fn, ul2, regs.nonneg[kl2], ok);
+        if (kpf2 >= 0) gram.add(fn, upf, ok, ytile, row16, g);
     }
-    constexpr int W = 16 * NBR;
-    if (kpf2 >= 0) {  // D layout of the f64 MFMA: col = l & 15, row = (l >> 4) + 4 reg
-        double *out = stat_gram + (long)tile * W * W;
-#pragma unroll
-        for (int a = 0; a < NBR; ++a)
-#pragma unroll
-            for (int b = 0; b < NBR; ++b)
-#pragma unroll
-                for (int v = 0; v < 4; ++v) out[(16 * a + g + 4 * v) * W + 16 * b + row16] = accS[a][b][v];
-    }
-    if (kl2 >= 0) {
-#pragma unroll
-        for (int h = 0; h < NBR; ++h)
-#pragma unroll
-            for (int v = 0; v < 4; ++v) {
-                double sq = csq[h][v];
-                sq += __shfl_xor(sq, 1);
-                sq += __shfl_xor(sq, 2);
-                sq += __shfl_xor(sq, 4);
-                sq += __shfl_xor(sq, 8);
-                const int col = 16 * h + 4 * g + v;
-                if (row16 == 0 && col < r) stat_colsq[((long)tile * MCL_MAX_REGS + kl2) * r + col] = sq;
-            }
-    }
+    if (kpf2 >= 0) gram.store(stat_gram, tile, row16, g);
+    if (kl2 >= 0) csq.reduce_store(stat_colsq, tile, kl2, r, row16, g);
 }
 
 // =========================================================================================================
