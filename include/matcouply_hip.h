@@ -382,6 +382,23 @@ int mcl_pf2als_multistart_run(const void *X, int32_t x_type, const int64_t *row_
                               void *hip_stream);
 const char *mcl_pf2als_multistart_last_error(void);
 
+/* ---- factor match scores of many pairs of fitted models (multistart_similarity, csrc/similarity.hip) ---------------------- */
+/* models: fp64 [n_models, (I + N + K) * rank], every model [A; B; C] row-major with B the stacked B_i (N = sum J_i): the layout
+ * of the first (I + N + K) * rank doubles of a multi-start state slice.  weights: fp64 [n_models, rank] or NULL (ones).
+ * pairs: HOST int32 [n_pairs, 2], checked against n_models before anything is launched; pair i = (s, t) compares model s with
+ * model t.  flags: bit 0 consider_weights, bit 1 absolute_value; skip_mode: -1 (none), 0, 1 or 2.  score: fp64 [n_pairs];
+ * perm: int32 [n_pairs, rank] or NULL: columns perm[i] of model t line it up with model s.  The definition of the score is in
+ * DESIGN.md section 14; the assignment is the exact optimum.  models, weights, score, perm, workspace: device pointers;
+ * workspace: mcl_fms_workspace_bytes(n_models, rank) bytes, 256-byte aligned (column norms and weights of every model).
+ * Needs 1 <= rank <= 16 and finite models.  Stateless; work is enqueued on the stream (the pairs are uploaded first, into the
+ * score buffer, and the stream is synchronised once for that).  No atomics and a fixed summation order: a pair's result does
+ * not depend on the other pairs of the call, and score(s, t) = score(t, s) bit for bit. */
+int64_t mcl_fms_workspace_bytes(int64_t n_models, int32_t rank);
+int mcl_fms_scores(const double *models, int64_t n_models, int64_t I, int64_t N, int64_t K, int32_t rank, const double *weights,
+                   const int32_t *pairs, int64_t n_pairs, int32_t flags, int32_t skip_mode, double *score, int32_t *perm,
+                   void *workspace, void *hip_stream);
+const char *mcl_fms_last_error(void);
+
 /* ---- introspection for tests / profiling ------------------------------------------------------------- */
 /* device pointers to internal by-products / planner tables (the int32 tables: read the bits) */
 enum mcl_buffer_id {

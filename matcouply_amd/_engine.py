@@ -64,6 +64,7 @@ EXPORTED_SYMBOLS = [
     "mcl_multistart_grid_workspace_bytes", "mcl_multistart_run_grid",
     "mcl_parafac2_als_workspace_bytes", "mcl_parafac2_als_typed", "mcl_parafac2_als_last_error",
     "mcl_pf2als_multistart_workspace_bytes", "mcl_pf2als_multistart_run", "mcl_pf2als_multistart_last_error",
+    "mcl_fms_workspace_bytes", "mcl_fms_scores", "mcl_fms_last_error",
 ]
 
 
@@ -203,6 +204,9 @@ def load_library():
         "mcl_pf2als_multistart_run": (ctypes.c_int, [P, I32, ctypes.POINTER(I64), I64, I64, I32, I32, I32, I32, ctypes.c_double,
                                                      ctypes.c_double, I32, P, P, P, P, P, I64, P]),
         "mcl_pf2als_multistart_last_error": (ctypes.c_char_p, []),
+        "mcl_fms_workspace_bytes": (I64, [I64, I32]),
+        "mcl_fms_scores": (ctypes.c_int, [P, I64, I64, I64, I64, I32, P, ctypes.POINTER(I32), I64, I32, I32, P, P, P, P]),
+        "mcl_fms_last_error": (ctypes.c_char_p, []),
         "mcl_read_bandwidth": (ctypes.c_int, [P, I64, I32, P, P, ctypes.POINTER(ctypes.c_double)]),
     }
     for name, (res, args) in sig.items():
@@ -430,6 +434,44 @@ def pf2als_multistart_run(X, row_ptr, rank, factors, n_iter_max, n_iter_parafac,
     if rc != 0:
         raise EngineError(lib.mcl_pf2als_multistart_last_error().decode())
     return P, errors, n_iter
+
+
+FMS_MAX_RANK = 16
+FMS_CONSIDER_WEIGHTS, FMS_ABSOLUTE_VALUE = 1, 2  # flag bits of mcl_fms_scores
+
+
+def fms_scores(models, I, N, K, rank, weights, pairs, flags, skip_mode, want_perm):
+    """Factor match scores of `pairs` of models on the device (mcl_fms_scores).  models: float64 [n_models, (I + N + K) * rank]
+    CUDA tensor, every model [A; B; C] row-major; weights: float64 [n_models, rank] CUDA tensor or None; pairs: int32 array
+    [n_pairs, 2] on the host; flags: FMS_* bits; skip_mode: -1, 0, 1 or 2.  -> (score float64 [n_pairs], perm int32
+    [n_pairs, rank] or None) on the device."""
+    import torch
+
+    lib = load_library()
+    n_models, r = int(models.shape[0]), int(rank)
+    if not (models.is_cuda and models.dtype == torch.float64 and models.is_contiguous() and models.dim() == 2
+            and models.shape[1] == (I + N + K) * r):
+        raise EngineError("models must be a contiguous float64 CUDA tensor [n_models, (I + N + K) * rank]")
+    if weights is not None and not (weights.is_cuda and weights.dtype == torch.float64 and weights.is_contiguous()
+                                    and tuple(weights.shape) == (n_models, r)):
+        raise EngineError("weights must be a contiguous float64 CUDA tensor [n_models, rank]")
+    pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    n_pairs = int(pairs.shape[0])
+    dev = models.device
+    nbytes = lib.mcl_fms_workspace_bytes(n_models, r)
+    ws = torch.empty(max(int(nbytes), 0) + 256, dtype=torch.uint8, device=dev)
+    off = (-ws.data_ptr()) % 256
+    score = torch.empty(n_pairs, dtype=torch.float64, device=dev)
+    perm = torch.empty((n_pairs, r), dtype=torch.int32, device=dev) if want_perm else None
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = lib.mcl_fms_scores(models.data_ptr(), n_models, int(I), int(N), int(K), r, weights.data_ptr() if weights is not None
+                                else None, pairs.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), n_pairs, int(flags), int(skip_mode),
+                                score.data_ptr(), perm.data_ptr() if want_perm else None, ws.data_ptr() + off,
+                                ctypes.c_void_p(stream))
+    if rc != 0:
+        raise EngineError(lib.mcl_fms_last_error().decode())
+    return score, perm
 
 
 def multistart_state_len(I, N, K, rank, kinds):
