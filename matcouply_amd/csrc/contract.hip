@@ -15,14 +15,8 @@
 #include <type_traits>
 
 #include "mcl_internal.h"
+#include "xc_parts.h"  // f32x4, f64x4, MFMA16, zero4 and the shared parts of the X C kernels
 #include "xload.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-
-#define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
-
-static __device__ __forceinline__ f32x4 zero4() { return f32x4{0.f, 0.f, 0.f, 0.f}; }
 
 // ---------------------------------------------------------------------------------------------------------
 // k_contract_xt
@@ -280,8 +274,8 @@ __global__ __launch_bounds__(256) void k_reduce_partials(const double *__restric
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// C in MFMA-fragment order for k_contract_xc:
-//   Cfrag[(((kc*4 + kq)*NB + nb)*64 + lane)*4 + m] = C[64kc + 16kq + 4(lane>>4) + m][16nb + (lane&15)]  (0 outside)
+// C in MFMA-fragment order for the X C kernels, the image cfrag_at (xc_parts.h) reads:
+//   Cfrag[cfrag_index(kc, kq, NB, nb, lane) + m] = C[64kc + 16kq + 4(lane>>4) + m][16nb + (lane&15)]  (0 outside)
 // ---------------------------------------------------------------------------------------------------------
 __global__ void k_build_cfrag(const float *__restrict__ C, int K, int r, int KC, int NB, float *__restrict__ Cfrag) {
     const long total = (long)KC * 4 * NB * 256;
@@ -293,7 +287,7 @@ __global__ void k_build_cfrag(const float *__restrict__ C, int K, int r, int KC,
     t /= NB;
     const int kq = t & 3, kc = t >> 2;
     const int k = 64 * kc + 16 * kq + 4 * (lane >> 4) + m, col = 16 * nb + (lane & 15);
-    Cfrag[idx] = (k < K && col < r) ? C[(long)k * r + col] : 0.f;
+    Cfrag[idx] = (k < K && col < r) ? C[(long)k * r + col] : 0.f;  // idx == cfrag_index(kc, kq, NB, nb, lane) + m
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -314,6 +308,7 @@ static __device__ __forceinline__ void k_contract_xc_body(const typename XL::T *
     __shared__ float lds_all[4][16 * 64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int q = lane >> 4, i16 = lane & 15;
+    using Tile = XcTile<64>;
     float *L = lds_all[wave];
     const int KC = (KCT > 0) ? KCT : KCrt;
     const long w = (long)blockIdx.x * 4 + wave;
@@ -331,8 +326,7 @@ static __device__ __forceinline__ void k_contract_xc_body(const typename XL::T *
             for (int kq = 0; kq < 4; ++kq)
 #pragma unroll
                 for (int nb = 0; nb < NB; ++nb)
-                    creg[kc][kq][nb] =
-                        *reinterpret_cast<const f32x4 *>(Cfrag + ((((long)kc * 4 + kq) * NB + nb) * 64 + lane) * 4);
+                    creg[kc][kq][nb] = cfrag_at<NB>(Cfrag, kc, kq, nb, lane);
     }
 
     xraw_t<XL, VEC == 4> xr[4][4];
@@ -366,13 +360,9 @@ static __device__ __forceinline__ void k_contract_xc_body(const typename XL::T *
             for (int kq = 0; kq < 4; ++kq) fr[kq] = xcvt<XL, VEC == 4>(xr[slot][kq]);
         } else {
 #pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const int row = 4 * t + q;
-                *reinterpret_cast<f32x4 *>(L + row * 64 + ((i16 ^ row) << 2)) = xcvt<XL, VEC == 4>(xr[slot][t]);
-            }
+            for (int t = 0; t < 4; ++t) Tile::put(L, 4 * t + q, i16, xcvt<XL, VEC == 4>(xr[slot][t]));
 #pragma unroll
-            for (int kq = 0; kq < 4; ++kq)
-                fr[kq] = *reinterpret_cast<const f32x4 *>(L + i16 * 64 + (((4 * kq + q) ^ i16) << 2));
+            for (int kq = 0; kq < 4; ++kq) fr[kq] = Tile::frag(L, i16, q, 0, kq);
         }
         issue(slot, nblk, nkc);
         if (dbg & 1) {  // timing experiment: no MFMA
@@ -425,8 +415,7 @@ static __device__ __forceinline__ void k_contract_xc_body(const typename XL::T *
                     for (int kq = 0; kq < 4; ++kq)
 #pragma unroll
                         for (int nb = 0; nb < NB; ++nb)
-                            cf[kq][nb] = *reinterpret_cast<const f32x4 *>(
-                                Cfrag + ((((long)(kc + d) * 4 + kq) * NB + nb) * 64 + lane) * 4);
+                            cf[kq][nb] = cfrag_at<NB>(Cfrag, kc + d, kq, nb, lane);
                     int nk = kc + d + 4;
                     long nblk = blk;
                     if (nk >= KC) {
@@ -458,14 +447,10 @@ __global__ __launch_bounds__(256) void k_contract_xc_h(const typename XL::T *__r
 // Same MFMA mapping as k_contract_xc, but the global access is ROW-CONTIGUOUS: a wave stages a 16-row x 256-column
 // super-chunk with 16 wave-loads of ONE 1 KB row segment each (lane l reads columns 4l..4l+3), i.e. the access
 // geometry of a plain streaming copy; for K = 256 the 16 loads cover one contiguous 16 KB region.  The tile lives
-// in a wave-private 16 KB LDS image whose 16-B slot index is XORed with the row (conflict-free ds_write_b128 /
-// ds_read_b128).  The next super-chunk's 16 loads are in flight while the current one is multiplied.
-// Work unit = SEGMENT (<= 256 rows of one slab).  GRAM: while the XC block is still in the accumulators
-// (lane (q, i16) holds rows 4q+v, column i16), the same-layout block of B is loaded and
-//     rhs_seg[c]  += sum_rows B[row][c] * XC[row][c]           (decomposition.py:147-158: diag(B_i^T X_i C))
-//     BtB_seg     += B_blk^T B_blk   (4 MFMAs: A = B-operand = b[v], reduction index <-> the 4 lane quarters)
-// are accumulated per segment; k_A_finish sums the segments of its slab.  This removes the separate
-// k_slab_gram pass (a 2 S_B re-read and a launch).
+// in a wave-private 16 KB XcTile<256>.  The next super-chunk's 16 loads are in flight while the current one is multiplied.
+// Work unit = SEGMENT (<= 256 rows of one slab).  GRAM: while the XC block is still in the accumulators, rhs_seg and BtB_seg
+// are accumulated per segment from the same-layout block of B (the arithmetic of SegGram, xc_parts.h, written out in this
+// body); k_A_finish sums the segments of its slab.  This removes the separate k_slab_gram pass (a 2 S_B re-read and a launch).
 // CREG: K == 256 and NB == 1: the 64 C-fragment registers stay resident.
 // ---------------------------------------------------------------------------------------------------------
 template <class XL, int NB, bool CREG, int GRAM, bool XNT>
@@ -473,6 +458,7 @@ static __device__ __forceinline__ void k_contract_xc_row_body(const typename XL:
     extern __shared__ float lds_dyn[];  // 4 waves x 16 rows x 256 floats
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int q = lane >> 4, i16 = lane & 15;
+    using Tile = XcTile<256>;
     float *L = lds_dyn + wave * (16 * 256);
     const int SC = K >> 8;  // super-chunks per row block
     const int w = blockIdx.x * 4 + wave;
@@ -490,8 +476,7 @@ static __device__ __forceinline__ void k_contract_xc_row_body(const typename XL:
             for (int kq = 0; kq < 4; ++kq)
 #pragma unroll
                 for (int nb = 0; nb < NB; ++nb)
-                    creg[kc][kq][nb] =
-                        *reinterpret_cast<const f32x4 *>(Cfrag + ((((long)kc * 4 + kq) * NB + nb) * 64 + lane) * 4);
+                    creg[kc][kq][nb] = cfrag_at<NB>(Cfrag, kc, kq, nb, lane);
     }
 
     typename XL::raw xr[16];
@@ -506,15 +491,7 @@ static __device__ __forceinline__ void k_contract_xc_row_body(const typename XL:
             const long j = row0 + min(16 * blk + t, nrows - 1);
             xr[t] = XL::template ld4<XNT>(X + j * K + 256 * sc + 4 * lane);
         }
-        if (GRAM && sc == 0) {  // unconditional clamped loads; masked at use
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-                for (int v = 0; v < 4; ++v) {
-                    const long j = row0 + min(16 * blk + 4 * q + v, nrows - 1);
-                    bnx[nb][v] = B[j * r + bcolc[nb]];
-                }
-        }
+        if (GRAM && sc == 0) b_rows_clamped<NB>(B, row0, blk, nrows, r, bcolc, q, bnx);  // masked at use
     };
 
     // four independent fp32 chains per output (one per 64-column chunk of a super-chunk), summed pairwise at the end of
@@ -539,11 +516,10 @@ static __device__ __forceinline__ void k_contract_xc_row_body(const typename XL:
             nrow0 = __builtin_amdgcn_readfirstlane(seg_row0[sg + 1]);
             nnrows = __builtin_amdgcn_readfirstlane(seg_rows[sg + 1]);
         }
-        // per-segment reductions.  GRAM == 2 (penalty-free A: its systems are not shifted and amplify every relative
-        // error of these sums): fp64 throughout - the products b * xc and b * b' of fp32 values are exact in fp64, so the
-        // only rounding left in rhs_i and B_i^T B_i is the fp32 rounding of X C itself.  GRAM == 1 (penalised A): fp32
-        // chains over the segment's <= 256 rows (4 fp32 MFMAs per block instead of 4 NB^2 fp64 ones at twice the cycles:
-        // 12 % of the kernel at rank 32), widened to fp64 when the segment is stored.
+        // per-segment reductions: the state and, below, the text of chains_sum4, SegGram::block and SegGram::store of xc_parts.h,
+        // kept IN this body.  Called as the forced-inline parts, the same text made the compiler change the s_waitcnt vmcnt
+        // values of the NB = 4 and the CREG forms of this kernel, whose loads no sched_barrier fences (at NB = 4, GRAM = 1 the
+        // loads of B moved in front of the loads of X); a change to SegGram is made here too
         double p[NB];
         float pf[NB];
         f64x4 accG[NB][NB];
@@ -574,13 +550,12 @@ static __device__ __forceinline__ void k_contract_xc_row_body(const typename XL:
                         for (int kq = 0; kq < 4; ++kq)
 #pragma unroll
                             for (int nb = 0; nb < NB; ++nb)
-                                cpre[kc][kq][nb] = *reinterpret_cast<const f32x4 *>(
-                                    Cfrag + ((((long)(4 * sc + kc) * 4 + kq) * NB + nb) * 64 + lane) * 4);
+                                cpre[kc][kq][nb] = cfrag_at<NB>(Cfrag, 4 * sc + kc, kq, nb, lane);
                     __builtin_amdgcn_sched_barrier(0);
                 }
-                // registers -> LDS: row t, logical 16-B slot = lane, physical slot = lane ^ t
+                // registers -> LDS: row t, logical 16-B slot = lane
 #pragma unroll
-                for (int t = 0; t < 16; ++t) *reinterpret_cast<f32x4 *>(L + t * 256 + ((lane ^ t) << 2)) = XL::cvt(xr[t]);
+                for (int t = 0; t < 16; ++t) Tile::put(L, t, lane, XL::cvt(xr[t]));
                 // prefetch the next super-chunk (possibly the first one of the next segment)
                 if (sc + 1 < SC) issue(row0, nrows, blk, sc + 1);
                 else if (blk + 1 < nblk) issue(row0, nrows, blk + 1, 0);
@@ -590,8 +565,7 @@ static __device__ __forceinline__ void k_contract_xc_row_body(const typename XL:
                 for (int kc = 0; kc < 4; ++kc) {
                     f32x4 fr[4];
 #pragma unroll
-                    for (int kq = 0; kq < 4; ++kq)
-                        fr[kq] = *reinterpret_cast<const f32x4 *>(L + i16 * 256 + (((16 * kc + 4 * kq + q) ^ i16) << 2));
+                    for (int kq = 0; kq < 4; ++kq) fr[kq] = Tile::frag(L, i16, q, kc, kq);
                     f32x4 cf[4][NB];
 #pragma unroll
                     for (int kq = 0; kq < 4; ++kq)
@@ -599,9 +573,7 @@ static __device__ __forceinline__ void k_contract_xc_row_body(const typename XL:
                         for (int nb = 0; nb < NB; ++nb) {
                             if (CREG) cf[kq][nb] = creg[kc][kq][nb];
                             else if (CPRE) cf[kq][nb] = cpre[kc][kq][nb];
-                            else
-                                cf[kq][nb] = *reinterpret_cast<const f32x4 *>(
-                                    Cfrag + ((((long)(4 * sc + kc) * 4 + kq) * NB + nb) * 64 + lane) * 4);
+                            else cf[kq][nb] = cfrag_at<NB>(Cfrag, 4 * sc + kc, kq, nb, lane);
                         }
 #pragma unroll
                     for (int kq = 0; kq < 4; ++kq)
@@ -700,11 +672,12 @@ __global__ __launch_bounds__(256) void k_contract_xc_row_h(const typename XL::T 
 // ---------------------------------------------------------------------------------------------------------
 // k_contract_xc_256 : the K = 256, rank <= 16 case of k_contract_xc_row (C fragments resident in 64 registers) with TWO
 // 16-row blocks of X in flight per wave instead of one (32 KB per wave, 128 KB per CU): a wave walks the 16-row blocks of
-// all its segments as one flat sequence through a 2-slot register ring; block b + 2 is requested as soon as block b sits
-// in the LDS tile.  Same arithmetic, tile layout, epilogue and per-segment outputs as k_contract_xc_row.  Config 4:
-// 180 -> 164 us (a third slot: 164 us - two blocks cover the latency; MCL_XC_DEPTH1=1 selects the one-slot kernel).
-// The flat walk: `cur` is the block being multiplied, `pre` the one being requested (two blocks ahead); past the wave's last
-// block `pre` keeps pointing at the last valid rows (unconditional clamped loads, nothing stored).
+// all its segments as one flat sequence (SegCursor, one tile per block) through a 2-slot register ring; block b + 2 is
+// requested as soon as block b sits in the XcTile<256>.  The block epilogue and the per-segment outputs are the NB == 1
+// SegGram; the sum of the chains is this kernel's own (below).  Config 4: 180 -> 164 us (a third slot: 164 us - two blocks
+// cover the latency; MCL_XC_DEPTH1=1 selects the one-slot kernel).
+// `cur` is the block being multiplied, `pre` the one being requested (two blocks ahead); past the wave's last block `pre`
+// keeps pointing at the last valid row (unconditional clamped loads, nothing stored).
 // ---------------------------------------------------------------------------------------------------------
 template <class XL, int GRAM, int D, bool XNT>
 static __device__ __forceinline__ void k_contract_xc_256_body(const typename XL::T *X, const float *Cfrag, float *XC, const float *B, const int *seg_row0, const int *seg_rows, const int *wave_seg_ptr, int n_waves, int r, double *seg_rhs, double *seg_btb) {
@@ -712,6 +685,7 @@ static __device__ __forceinline__ void k_contract_xc_256_body(const typename XL:
     constexpr int K = 256;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int q = lane >> 4, i16 = lane & 15;
+    using Tile = XcTile<256>;
     float *L = lds_dyn + wave * (16 * 256);
     const int w = blockIdx.x * 4 + wave;
     if (w >= n_waves) return;
@@ -723,81 +697,53 @@ static __device__ __forceinline__ void k_contract_xc_256_body(const typename XL:
     for (int kc = 0; kc < 4; ++kc)
 #pragma unroll
         for (int kq = 0; kq < 4; ++kq)
-            creg[kc][kq] = *reinterpret_cast<const f32x4 *>(Cfrag + (((long)kc * 4 + kq) * 64 + lane) * 4);
-    const int bcol = min(i16, r - 1);
-
-    struct Cursor {
-        int sg, blk, nblk, nrows;
-        long row0;
-    };
-    auto seg_at = [&](Cursor &c, int sg) {
-        c.sg = sg, c.blk = 0;
-        c.row0 = __builtin_amdgcn_readfirstlane(seg_row0[sg]);
-        c.nrows = __builtin_amdgcn_readfirstlane(seg_rows[sg]);
-        c.nblk = (c.nrows + 15) >> 4;
-    };
-    auto advance = [&](Cursor &c) {  // wave-uniform
-        if (c.blk + 1 < c.nblk) {
-            c.blk += 1;
-        } else if (c.sg + 1 < s1) {
-            seg_at(c, c.sg + 1);
-        } else {
-            c.blk = c.nblk;  // past the end: rows clamp to the last valid one
-        }
-    };
+            creg[kc][kq] = cfrag_at<1>(Cfrag, kc, kq, 0, lane);
+    const int bcolc[1] = {min(i16, r - 1)};
     int total = 0;
     for (int sg = s0; sg < s1; ++sg) total += (__builtin_amdgcn_readfirstlane(seg_rows[sg]) + 15) >> 4;
 
     typename XL::raw xr[D][16];
-    float bnx[D][4];
-    auto issue = [&](auto dc, const Cursor &c) {
+    float bnx[D][1][4];
+    auto issue = [&](auto dc, const SegCursor &c) {
         constexpr int d = decltype(dc)::value;
 #pragma unroll
         for (int t = 0; t < 16; ++t) {
             const long j = c.row0 + min(16 * c.blk + t, c.nrows - 1);
             xr[d][t] = XL::template ld4<XNT>(X + j * K + 4 * lane);
         }
-        if (GRAM) {
-#pragma unroll
-            for (int v = 0; v < 4; ++v) {
-                const long j = c.row0 + min(16 * c.blk + 4 * q + v, c.nrows - 1);
-                bnx[d][v] = B[j * r + bcol];
-            }
-        }
+        if (GRAM) b_rows_clamped<1>(B, c.row0, c.blk, c.nrows, r, bcolc, q, bnx[d]);
     };
 
-    Cursor cur, pre;
-    seg_at(cur, s0);
-    seg_at(pre, s0);
+    SegCursor cur;
+    cur.begin(seg_row0, seg_rows, s0, s1);
+    SegCursor pre = cur;
     issue(std::integral_constant<int, 0>{}, pre);
-    advance(pre);
+    pre.advance(1);
     __builtin_amdgcn_sched_barrier(0);
     if (D > 1) {
         issue(std::integral_constant<int, (D > 1 ? 1 : 0)>{}, pre);
-        advance(pre);
+        pre.advance(1);
         __builtin_amdgcn_sched_barrier(0);
     }
     if (D > 2) {
         issue(std::integral_constant<int, (D > 2 ? 2 : 0)>{}, pre);
-        advance(pre);
+        pre.advance(1);
         __builtin_amdgcn_sched_barrier(0);
     }
 
-    double p = 0.0;
-    float pf = 0.f;
-    f64x4 accG = {0.0, 0.0, 0.0, 0.0};
-    f32x4 accGf = zero4();
+    SegGram<1, GRAM> gram;
+    gram.reset();
     auto body = [&](auto dc, bool live) {
         constexpr int d = decltype(dc)::value;
-        float bcur[4];
+        float bcur[1][4];
         if (GRAM) {
 #pragma unroll
-            for (int v = 0; v < 4; ++v) bcur[v] = bnx[d][v];
+            for (int v = 0; v < 4; ++v) bcur[0][v] = bnx[d][0][v];
         }
 #pragma unroll
-        for (int t = 0; t < 16; ++t) *reinterpret_cast<f32x4 *>(L + t * 256 + ((lane ^ t) << 2)) = XL::cvt(xr[d][t]);
+        for (int t = 0; t < 16; ++t) Tile::put(L, t, lane, XL::cvt(xr[d][t]));
         issue(dc, pre);  // the slot is free again: its next block (two ahead) goes out now
-        advance(pre);
+        pre.advance(1);
         // EIGHT fp32 accumulation chains per output (32 columns = 8 MFMAs each; round 2: four of 16), summed as a tree in
         // fp64 and rounded once: the 256-term dot products of X C are the second largest rounding of config 4's B-phase
         // (tools/pf2_rounding_study.py), and that configuration's penalty-free A / C systems amplify it
@@ -807,56 +753,26 @@ static __device__ __forceinline__ void k_contract_xc_256_body(const typename XL:
             acc8[kc][0] = zero4(), acc8[kc][1] = zero4();
             f32x4 fr[4];
 #pragma unroll
-            for (int kq = 0; kq < 4; ++kq)
-                fr[kq] = *reinterpret_cast<const f32x4 *>(L + i16 * 256 + (((16 * kc + 4 * kq + q) ^ i16) << 2));
+            for (int kq = 0; kq < 4; ++kq) fr[kq] = Tile::frag(L, i16, q, kc, kq);
 #pragma unroll
             for (int kq = 0; kq < 4; ++kq)
 #pragma unroll
                 for (int m = 0; m < 4; ++m) acc8[kc][kq >> 1] = MFMA16(fr[kq][m], creg[kc][kq][m], acc8[kc][kq >> 1]);
         }
-        f32x4 acc;
+        f32x4 acc[1];
 #pragma unroll
         for (int v = 0; v < 4; ++v) {
             const double s01 = ((double)acc8[0][0][v] + (double)acc8[0][1][v]) + ((double)acc8[1][0][v] + (double)acc8[1][1][v]);
             const double s23 = ((double)acc8[2][0][v] + (double)acc8[2][1][v]) + ((double)acc8[3][0][v] + (double)acc8[3][1][v]);
-            acc[v] = (float)(s01 + s23);
+            acc[0][v] = (float)(s01 + s23);
         }
         if (!live) return;  // the dummy half of an odd trip: nothing stored (wave-uniform)
-        float bv[4];
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            const int rl = 16 * cur.blk + 4 * q + v;
-            const bool ok = (rl < cur.nrows) && (i16 < r);
-            if (ok) XC[(cur.row0 + rl) * r + i16] = acc[v];
-            if (GRAM) {
-                const float b = ok ? bcur[v] : 0.f;
-                bv[v] = b;
-                if (GRAM == 2) p = fma((double)b, (double)acc[v], p);
-                else pf = fmaf(b, acc[v], pf);
-            }
+        gram.block(acc, bcur, cur.row0, cur.blk, cur.nrows, r, XC, q, i16);
+        if (GRAM && cur.blk == cur.nblk - 1) {  // the segment ends with this block: its reductions go out (wave-uniform)
+            gram.store(cur.sg, r, seg_rhs, seg_btb, q, i16);
+            gram.reset();
         }
-        if (GRAM) {
-#pragma unroll
-            for (int v = 0; v < 4; ++v) {
-                if (GRAM == 2) accG = __builtin_amdgcn_mfma_f64_16x16x4f64((double)bv[v], (double)bv[v], accG, 0, 0, 0);
-                else accGf = MFMA16(bv[v], bv[v], accGf);
-            }
-            if (cur.blk == cur.nblk - 1) {  // the segment ends with this block: its reductions go out (wave-uniform)
-                double t = (GRAM == 2) ? p : (double)pf;
-                t += __shfl_xor(t, 16);
-                t += __shfl_xor(t, 32);
-                if (q == 0 && i16 < r) seg_rhs[(long)cur.sg * r + i16] = t;
-#pragma unroll
-                for (int v = 0; v < 4; ++v) {
-                    const int ra = (GRAM == 2) ? q + 4 * v : 4 * q + v;  // D layouts of the f64 / f32 MFMA
-                    const double val = (GRAM == 2) ? accG[v] : (double)accGf[v];
-                    if (ra < r && i16 < r) seg_btb[((long)cur.sg * r + ra) * r + i16] = val;
-                }
-                p = 0.0, pf = 0.f;
-                accG = f64x4{0.0, 0.0, 0.0, 0.0}, accGf = zero4();
-            }
-        }
-        advance(cur);
+        cur.advance(1);
     };
     for (int b = 0; b < total; b += D) {
         body(std::integral_constant<int, 0>{}, true);
@@ -1092,11 +1008,14 @@ static int launch_xc(mcl_context *c) {
     hipLaunchKernelGGL((MCL_XKERNEL(k_contract_xc_row, NB, CREG_, GRAM_, NT_)), dim3(g), dim3(256), sm, c->stream, mcl_x<XL>(c), c->Cfrag, \
                        c->XC, c->B, c->segs.row0, c->segs.nrows, c->wave_seg_ptr, c->n_seg_waves, (int)c->K, c->r, c->seg_rhs, \
                        c->seg_btb)
-#define MCL_XCR(CREG_, GRAM_)                                                                                        \
-    do {                                                                                                              \
-        if (c->x_streams) MCL_XCR_(CREG_, GRAM_, true);                                                               \
-        else MCL_XCR_(CREG_, GRAM_, false);                                                                           \
-    } while (0)
+        auto launch_row = [&](auto creg_c) {
+            xc_gram_dispatch(gram, c->x_streams, [&](auto gram_c, auto nt_c) {
+                constexpr bool CREG_ = decltype(creg_c)::value, NT_ = decltype(nt_c)::value;
+                constexpr int GRAM_ = decltype(gram_c)::value;
+                if constexpr (NB < 4 || GRAM_ != 2) MCL_XCR_(CREG_, GRAM_, NT_);  // (rank > 32 never asks for the fp64 form)
+                return 0;
+            });
+        };
         if (n_segs > 0 && !creg && mcl_try_contract_xc_lds(c, gram)) {
             // K % 512 == 0 with the fragment image of C resident in LDS and four X tiles in flight per wave (xclds.hip)
             c->xc_did_gram = gram != 0;
@@ -1109,36 +1028,20 @@ static int launch_xc(mcl_context *c) {
         if (n_segs > 0) {
             if constexpr (NB == 1) {  // resident C fragments: K = 256, rank <= 16 only
                 if (creg && !c->sw.xc_depth1) {  // two blocks of X in flight per wave
-#define MCL_XC256_(GRAM_, NT_)                                                                                        \
-    hipLaunchKernelGGL((MCL_XKERNEL(k_contract_xc_256, GRAM_, 2, NT_)), dim3(g), dim3(256), sm, c->stream, mcl_x<XL>(c), c->Cfrag, c->XC, c->B, \
-                       c->segs.row0, c->segs.nrows, c->wave_seg_ptr, c->n_seg_waves, c->r, c->seg_rhs, c->seg_btb)
-#define MCL_XC256(GRAM_)                                                                                              \
-    do {                                                                                                              \
-        if (c->x_streams) MCL_XC256_(GRAM_, true);                                                                    \
-        else MCL_XC256_(GRAM_, false);                                                                                \
-    } while (0)
-                    if (gram == 2) MCL_XC256(2);
-                    else if (gram == 1) MCL_XC256(1);
-                    else MCL_XC256(0);
-#undef MCL_XC256
-#undef MCL_XC256_
+                    xc_gram_dispatch(gram, c->x_streams, [&](auto gram_c, auto nt_c) {
+                        constexpr int GRAM_ = decltype(gram_c)::value;
+                        constexpr bool NT_ = decltype(nt_c)::value;
+                        hipLaunchKernelGGL((MCL_XKERNEL(k_contract_xc_256, GRAM_, 2, NT_)), dim3(g), dim3(256), sm, c->stream, mcl_x<XL>(c),
+                                           c->Cfrag, c->XC, c->B, c->segs.row0, c->segs.nrows, c->wave_seg_ptr, c->n_seg_waves, c->r,
+                                           c->seg_rhs, c->seg_btb);
+                        return 0;
+                    });
                 } else if (creg) {
-                    if (gram == 2) MCL_XCR(true, 2);
-                    else if (gram == 1) MCL_XCR(true, 1);
-                    else MCL_XCR(true, 0);
+                    launch_row(std::true_type{});
                 }
             }
-            if (!creg) {
-                if (gram == 2) {
-                    if constexpr (NB < 4) MCL_XCR(false, 2);
-                } else if (gram == 1) {
-                    MCL_XCR(false, 1);
-                } else {
-                    MCL_XCR(false, 0);
-                }
-            }
+            if (!creg) launch_row(std::false_type{});
         }
-#undef MCL_XCR
 #undef MCL_XCR_
         c->xc_did_gram = gram != 0;
         char buf[96];

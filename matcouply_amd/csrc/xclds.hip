@@ -6,30 +6,19 @@
 // rank 32) the pass waits for memory half of its life (profiles/r6_c5_sq_counters.json: SQ_WAIT_INST_ANY 52 % of SQ_WAVE_CYCLES)
 // and moves 70.9 GB in 16.7 ms = 4.4 TB/s where a streaming read reaches 6.8.  Here
 //   * the workgroup copies the fragment image of C into LDS once (config 5: 128 KB of the CU's 160 KB; the MFMA B operands are
-//     16-byte LDS reads, lane-linear: conflict-free),
+//     16-byte LDS reads, lane-linear: conflict-free; cfrag_at on the LDS base),
 //   * so the ONLY loads of the main loop are the X tiles (and, once per round, the rows of B for the fused A-phase reductions, in
 //     the same batch): a DEPTH-slot register ring keeps four or eight 16-row x 128-column tiles (32 / 64 KB per wave) in
 //     flight under exact s_waitcnt vmcnt(N) counts - every load unconditional at clamped addresses, a fixed number per step,
-//   * tiles are staged through a wave-private 8 KB LDS image (16-byte slot index XORed with the row: conflict-free writes and
-//     fragment reads), as in k_contract_xc_row.
-// Arithmetic and its order are those of k_contract_xc_row: four fp32 chains per output (one per 64-column chunk modulo 4,
-// ascending in K), summed pairwise at the end of a 16-row block; the fused reductions (GRAM) word for word.  Same segment /
-// wave tables.  Reference: decomposition.py:147-158 (X_i C, diag(B_i^T X_i C), B_i^T B_i) and :242.
+//   * tiles are staged through a wave-private 8 KB XcTile<128>.
+// What is not the pipeline comes from xc_parts.h: the tile, the walk (SegCursor with K / 128 tiles per block), the four fp32
+// chains per output (one per 64-column chunk modulo 4, ascending in K) and their sum (chains_sum4), the rows of B
+// (b_rows_clamped) and the fused reductions (SegGram).  Same segment / wave tables as k_contract_xc_row.
 #include "mcl_internal.h"
+#include "xc_parts.h"
 #include "xload.h"
 
-typedef float xf32x4 __attribute__((ext_vector_type(4)));
-typedef double xf64x4 __attribute__((ext_vector_type(4)));
-#define XMFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
-
 namespace {
-
-// position in the wave's tile stream: segment, 16-row block, 128-column tile
-struct TileCursor {
-    int sg, s1;       // current segment, end of the wave's segments
-    long row0;
-    int nrows, nblk, blk, hs;
-};
 
 template <class XL, int NB, int GRAM, bool XNT, int DEPTH>
 static __device__ __forceinline__ void k_contract_xc_lds_body(const typename XL::T *X, const float *Cfrag, float *XC, const float *B, const int *seg_row0, const int *seg_rows, const int *wave_seg_ptr, int n_waves, int K, int r, double *seg_rhs, double *seg_btb) {
@@ -38,12 +27,12 @@ static __device__ __forceinline__ void k_contract_xc_lds_body(const typename XL:
     const int q = lane >> 4, i16 = lane & 15;
     const int cf_f4 = (K >> 6) * 4 * NB * 64;  // float4 elements of the image
     {
-        xf32x4 *dst = reinterpret_cast<xf32x4 *>(lds_dyn);
-        const xf32x4 *src = reinterpret_cast<const xf32x4 *>(Cfrag);
+        f32x4 *dst = reinterpret_cast<f32x4 *>(lds_dyn);
+        const f32x4 *src = reinterpret_cast<const f32x4 *>(Cfrag);
         for (int e = threadIdx.x; e < cf_f4; e += 256) dst[e] = src[e];
     }
     __syncthreads();
-    const xf32x4 *Cs = reinterpret_cast<const xf32x4 *>(lds_dyn);
+    using Tile = XcTile<128>;
     float *L = lds_dyn + 4 * cf_f4 + wave * (16 * 128);
     const int w = blockIdx.x * 4 + wave;
     if (w >= n_waves) return;
@@ -51,82 +40,45 @@ static __device__ __forceinline__ void k_contract_xc_lds_body(const typename XL:
     if (s0 >= s1) return;
     const int TPB = K >> 7;  // tiles per 16-row block (a multiple of DEPTH)
 
-    // ---- the prefetch side: four tiles in registers
+    // ---- the prefetch side: DEPTH tiles in registers
     typename XL::raw xr[DEPTH][8];
     float bnx[NB][4];  // rows 4q + v, column 16 nb + i16 of B for the block the prefetch cursor is in
     int bcolc[NB];
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) bcolc[nb] = min(16 * nb + i16, r - 1);
-    auto seg_of = [&](TileCursor &c, int sg) {
-        c.sg = sg;
-        c.row0 = __builtin_amdgcn_readfirstlane(seg_row0[sg]);
-        c.nrows = __builtin_amdgcn_readfirstlane(seg_rows[sg]);
-        c.nblk = (c.nrows + 15) >> 4;
-        c.blk = 0, c.hs = 0;
-    };
-    auto advance = [&](TileCursor &c) {  // next tile; at the end of the wave's work the cursor stays on its last tile
-        if (c.hs + 1 < TPB) {
-            c.hs += 1;
-        } else if (c.blk + 1 < c.nblk) {
-            c.blk += 1, c.hs = 0;
-        } else if (c.sg + 1 < c.s1) {
-            seg_of(c, c.sg + 1);
-        }
-    };
     const int half = lane >> 5, slot = lane & 31;
-    auto issue = [&](const TileCursor &c, typename XL::raw (&dst)[8]) {
+    auto issue = [&](const SegCursor &c, typename XL::raw (&dst)[8]) {
 #pragma unroll
         for (int t = 0; t < 8; ++t) {
             const long j = c.row0 + min(16 * c.blk + 2 * t + half, c.nrows - 1);
             dst[t] = XL::template ld4<XNT>(X + j * K + 128 * c.hs + 4 * slot);
         }
     };
-    auto issue_b = [&](const TileCursor &c) {
-        if (GRAM) {
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-                for (int v = 0; v < 4; ++v) {
-                    const long j = c.row0 + min(16 * c.blk + 4 * q + v, c.nrows - 1);
-                    bnx[nb][v] = B[j * r + bcolc[nb]];
-                }
-        }
+    auto issue_b = [&](const SegCursor &c) {
+        if (GRAM) b_rows_clamped<NB>(B, c.row0, c.blk, c.nrows, r, bcolc, q, bnx);
     };
 
-    TileCursor pc;  // prefetch cursor
-    pc.s1 = s1;
-    seg_of(pc, s0);
-    TileCursor cc = pc;  // compute cursor
+    SegCursor pc;  // prefetch cursor
+    pc.begin(seg_row0, seg_rows, s0, s1);
+    SegCursor cc = pc;  // compute cursor: stepped by hand below, the epilogues sit between its steps
     issue_b(pc);
 #pragma unroll
     for (int s = 0; s < DEPTH; ++s) {
         issue(pc, xr[s]);
-        advance(pc);
+        pc.advance(TPB);
     }
 
     long total_rounds = 0;
     for (int sg = s0; sg < s1; ++sg) total_rounds += (long)((__builtin_amdgcn_readfirstlane(seg_rows[sg]) + 15) >> 4) * (TPB / DEPTH);
 
     constexpr int NCH = (NB == 4) ? 1 : 4;
-    xf32x4 acc4[NCH][NB];
+    f32x4 acc4[NCH][NB];
 #pragma unroll
     for (int kc = 0; kc < NCH; ++kc)
 #pragma unroll
-        for (int nb = 0; nb < NB; ++nb) acc4[kc][nb] = xf32x4{0.f, 0.f, 0.f, 0.f};
-    // per-segment reductions (see k_contract_xc_row)
-    double p[NB];
-    float pf[NB];
-    xf64x4 accG[NB][NB];
-    xf32x4 accGf[NB][NB];
-    auto seg_reset = [&]() {
-#pragma unroll
-        for (int a = 0; a < NB; ++a) {
-            p[a] = 0.0, pf[a] = 0.f;
-#pragma unroll
-            for (int b = 0; b < NB; ++b) accG[a][b] = xf64x4{0.0, 0.0, 0.0, 0.0}, accGf[a][b] = xf32x4{0.f, 0.f, 0.f, 0.f};
-        }
-    };
-    seg_reset();
+        for (int nb = 0; nb < NB; ++nb) acc4[kc][nb] = zero4();
+    SegGram<NB, GRAM> gram;
+    gram.reset();
     float bcur[NB][4];
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb)
@@ -142,29 +94,25 @@ static __device__ __forceinline__ void k_contract_xc_lds_body(const typename XL:
         }
 #pragma unroll
         for (int s = 0; s < DEPTH; ++s) {
-            // tile `cc` sits in xr[s]: registers -> LDS (row R, logical 16-B slot l -> physical slot l ^ (R & 15))
+            // tile `cc` sits in xr[s]: registers -> LDS
 #pragma unroll
-            for (int t = 0; t < 8; ++t) {
-                const int R = 2 * t + half;
-                *reinterpret_cast<xf32x4 *>(L + R * 128 + ((slot ^ (R & 15)) << 2)) = XL::cvt(xr[s][t]);
-            }
+            for (int t = 0; t < 8; ++t) Tile::put(L, 2 * t + half, slot, XL::cvt(xr[s][t]));
             // the slot is free: the tile DEPTH ahead (once per round with the rows of B of its block: a fixed number of loads)
             if (s == 0) issue_b(pc);
             issue(pc, xr[s]);
-            advance(pc);
+            pc.advance(TPB);
             __builtin_amdgcn_sched_barrier(0);
             const int chunk0 = 2 * cc.hs;  // 64-column chunks 2 hs, 2 hs + 1 of C
 #pragma unroll
             for (int kc = 0; kc < 2; ++kc) {
-                xf32x4 fr[4];
+                f32x4 fr[4];
+#pragma unroll
+                for (int kq = 0; kq < 4; ++kq) fr[kq] = Tile::frag(L, i16, q, kc, kq);
+                f32x4 cf[4][NB];
 #pragma unroll
                 for (int kq = 0; kq < 4; ++kq)
-                    fr[kq] = *reinterpret_cast<const xf32x4 *>(L + i16 * 128 + (((16 * kc + 4 * kq + q) ^ i16) << 2));
-                xf32x4 cf[4][NB];
 #pragma unroll
-                for (int kq = 0; kq < 4; ++kq)
-#pragma unroll
-                    for (int nb = 0; nb < NB; ++nb) cf[kq][nb] = Cs[(((long)(chunk0 + kc) * 4 + kq) * NB + nb) * 64 + lane];
+                    for (int nb = 0; nb < NB; ++nb) cf[kq][nb] = cfrag_at<NB>(lds_dyn, chunk0 + kc, kq, nb, lane);
                 // the chain of chunk (2 hs + kc) mod 4: hs = s (mod 4) inside a round (DEPTH is a multiple of 4)
                 const int ch = (NCH == 4) ? ((2 * s + kc) & 3) : 0;
 #pragma unroll
@@ -172,77 +120,24 @@ static __device__ __forceinline__ void k_contract_xc_lds_body(const typename XL:
 #pragma unroll
                     for (int m = 0; m < 4; ++m)
 #pragma unroll
-                        for (int nb = 0; nb < NB; ++nb) acc4[ch][nb] = XMFMA16(fr[kq][m], cf[kq][nb][m], acc4[ch][nb]);
+                        for (int nb = 0; nb < NB; ++nb) acc4[ch][nb] = MFMA16(fr[kq][m], cf[kq][nb][m], acc4[ch][nb]);
             }
             cc.hs += 1;
         }
         if (cc.hs < TPB) continue;
-        // ---- epilogue of the 16-row block
-        xf32x4 acc[NB];
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb) {
-            if (NCH == 4) acc[nb] = (acc4[0][nb] + acc4[1][nb]) + (acc4[2 % NCH][nb] + acc4[3 % NCH][nb]);
-            else acc[nb] = acc4[0][nb];
-#pragma unroll
-            for (int kc = 0; kc < NCH; ++kc) acc4[kc][nb] = xf32x4{0.f, 0.f, 0.f, 0.f};
-        }
-        float bv[NB][4];
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb) {
-            const int col = 16 * nb + i16;
-#pragma unroll
-            for (int v = 0; v < 4; ++v) {
-                const int rl = 16 * cc.blk + 4 * q + v;
-                const long j = cc.row0 + rl;
-                const bool ok = (rl < cc.nrows) && (col < r);
-                if (ok) XC[j * r + col] = acc[nb][v];
-                if (GRAM) {
-                    const float b = ok ? bcur[nb][v] : 0.f;
-                    bv[nb][v] = b;
-                    if (GRAM == 2) p[nb] = fma((double)b, (double)acc[nb][v], p[nb]);
-                    else pf[nb] = fmaf(b, acc[nb][v], pf[nb]);
-                }
-            }
-        }
-        if (GRAM) {
-#pragma unroll
-            for (int v = 0; v < 4; ++v)
-#pragma unroll
-                for (int a = 0; a < NB; ++a)
-#pragma unroll
-                    for (int b = 0; b < NB; ++b) {
-                        if (GRAM == 2)
-                            accG[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64((double)bv[a][v], (double)bv[b][v], accG[a][b], 0, 0, 0);
-                        else
-                            accGf[a][b] = XMFMA16(bv[a][v], bv[b][v], accGf[a][b]);
-                    }
-        }
+        // ---- end of the 16-row block
+        f32x4 acc[NB];
+        chains_sum4<NCH, NB>(acc4, acc);
+        gram.block(acc, bcur, cc.row0, cc.blk, cc.nrows, r, XC, q, i16);
         cc.hs = 0;
         cc.blk += 1;
         if (cc.blk < cc.nblk) continue;
         // ---- end of the segment
         if (GRAM) {
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb) {
-                double t = (GRAM == 2) ? p[nb] : (double)pf[nb];
-                t += __shfl_xor(t, 16);
-                t += __shfl_xor(t, 32);
-                const int col = 16 * nb + i16;
-                if (q == 0 && col < r) seg_rhs[(long)cc.sg * r + col] = t;
-            }
-#pragma unroll
-            for (int a = 0; a < NB; ++a)
-#pragma unroll
-                for (int b = 0; b < NB; ++b)
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) {
-                        const int ra = 16 * a + ((GRAM == 2) ? q + 4 * v : 4 * q + v), cb = 16 * b + i16;
-                        const double val = (GRAM == 2) ? accG[a][b][v] : (double)accGf[a][b][v];
-                        if (ra < r && cb < r) seg_btb[((long)cc.sg * r + ra) * r + cb] = val;
-                    }
-            seg_reset();
+            gram.store(cc.sg, r, seg_rhs, seg_btb, q, i16);
+            gram.reset();
         }
-        if (cc.sg + 1 < s1) seg_of(cc, cc.sg + 1);
+        if (cc.sg + 1 < s1) cc.seg_at(cc.sg + 1);
     }
 }
 template <int NB, int GRAM, bool XNT, int DEPTH>
@@ -304,24 +199,17 @@ static int try_xc_lds(mcl_context *c, int gram) {
             MCL_XCL__(NB_, GRAM_, NT_, 4);                       \
         }                                                        \
     } while (0)
-#define MCL_XCL(NB_, GRAM_)                                      \
-    do {                                                         \
-        if (c->x_streams) MCL_XCL_(NB_, GRAM_, true);            \
-        else MCL_XCL_(NB_, GRAM_, false);                        \
-    } while (0)
-    if (c->NB == 1) {
-        if (gram == 2) MCL_XCL(1, 2);
-        else if (gram == 1) MCL_XCL(1, 1);
-        else MCL_XCL(1, 0);
-    } else {
-        if (gram == 2) MCL_XCL(2, 2);
-        else if (gram == 1) MCL_XCL(2, 1);
-        else MCL_XCL(2, 0);
-    }
-#undef MCL_XCL
+    auto launch = [&](auto nb_c) {
+        return xc_gram_dispatch(gram, c->x_streams, [&](auto gram_c, auto nt_c) {
+            constexpr int NB_ = decltype(nb_c)::value, GRAM_ = decltype(gram_c)::value;
+            constexpr bool NT_ = decltype(nt_c)::value;
+            MCL_XCL_(NB_, GRAM_, NT_);
+            return hipGetLastError() == hipSuccess ? 1 : 0;
+        });
+    };
+    return c->NB == 1 ? launch(std::integral_constant<int, 1>{}) : launch(std::integral_constant<int, 2>{});
 #undef MCL_XCL_
 #undef MCL_XCL__
-    return hipGetLastError() == hipSuccess ? 1 : 0;
 }
 
 int mcl_try_contract_xc_lds(mcl_context *c, int gram) {
