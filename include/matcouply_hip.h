@@ -399,6 +399,26 @@ int mcl_fms_scores(const double *models, int64_t n_models, int64_t I, int64_t N,
                    void *workspace, void *hip_stream);
 const char *mcl_fms_last_error(void);
 
+/* ---- fit, per-matrix SSE and core consistency of many fitted models (multistart_evaluation, csrc/evaluate.hip) ------------ */
+/* models: fp64 [n_models, (I + N + K) * rank], the layout of mcl_fms_scores (weights folded into A by the caller).  X: the packed
+ * data [N, K] of element type x_type, row_ptr: HOST int64 [I + 1], strictly increasing from 0 (every matrix has a row).
+ * mcl_eval_tables_typed reads X once per model and writes S [n_models, I, r, r] (S_i = B_i^T X_i C), BtB [n_models, I, r, r],
+ * sse [n_models, I] (|X_i - B_i diag(a_i) C^T|_F^2, summed from the residual) and norm [I] (|X_i|_F^2).  mcl_eval_core takes
+ * these tables and writes core [n_models, r, r, r] (G[p][q][s] = sum_i (A^+)[p][i] ((B_i^T B_i)^+ S_i (C^T C)^+)[q][s]), cc and
+ * cc_normalised [n_models] (100 (1 - sum (G - T)^2 / r), resp. / sum G^2; T the superdiagonal of ones).  The definitions are in
+ * DESIGN.md section 15.  X, models, the tables, the outputs and ws are device pointers; ws: mcl_eval_workspace_bytes bytes,
+ * 256-byte aligned.  Needs 1 <= rank <= 32, 1 <= n_models <= 65535 and finite models: the models are read back and checked
+ * before anything is launched (one synchronisation of the stream).  Stateless; the work is enqueued on the stream.  No atomics
+ * and a fixed summation order: a model's results do not depend on the other models of the call, and two runs are bitwise equal.
+ * mcl_eval_workspace_bytes returns -1 for arguments the entries refuse. */
+int64_t mcl_eval_workspace_bytes(const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank, int64_t n_models);
+int mcl_eval_tables_typed(const void *X, int32_t x_type, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank,
+                          const double *models, int64_t n_models, double *S, double *BtB, double *sse, double *norm, void *ws,
+                          int64_t ws_bytes, void *stream);
+int mcl_eval_core(const double *models, int64_t n_models, int64_t I, int64_t N, int64_t K, int32_t rank, const double *S,
+                  const double *BtB, double *core, double *cc, double *cc_normalised, void *stream);
+const char *mcl_eval_last_error(void);
+
 /* ---- introspection for tests / profiling ------------------------------------------------------------- */
 /* device pointers to internal by-products / planner tables (the int32 tables: read the bits) */
 enum mcl_buffer_id {

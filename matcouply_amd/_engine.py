@@ -65,6 +65,7 @@ EXPORTED_SYMBOLS = [
     "mcl_parafac2_als_workspace_bytes", "mcl_parafac2_als_typed", "mcl_parafac2_als_last_error",
     "mcl_pf2als_multistart_workspace_bytes", "mcl_pf2als_multistart_run", "mcl_pf2als_multistart_last_error",
     "mcl_fms_workspace_bytes", "mcl_fms_scores", "mcl_fms_last_error",
+    "mcl_eval_workspace_bytes", "mcl_eval_tables_typed", "mcl_eval_core", "mcl_eval_last_error",
 ]
 
 
@@ -207,6 +208,10 @@ def load_library():
         "mcl_fms_workspace_bytes": (I64, [I64, I32]),
         "mcl_fms_scores": (ctypes.c_int, [P, I64, I64, I64, I64, I32, P, ctypes.POINTER(I32), I64, I32, I32, P, P, P, P]),
         "mcl_fms_last_error": (ctypes.c_char_p, []),
+        "mcl_eval_workspace_bytes": (I64, [ctypes.POINTER(I64), I64, I64, I32, I64]),
+        "mcl_eval_tables_typed": (ctypes.c_int, [P, I32, ctypes.POINTER(I64), I64, I64, I32, P, I64, P, P, P, P, P, I64, P]),
+        "mcl_eval_core": (ctypes.c_int, [P, I64, I64, I64, I64, I32, P, P, P, P, P, P]),
+        "mcl_eval_last_error": (ctypes.c_char_p, []),
         "mcl_read_bandwidth": (ctypes.c_int, [P, I64, I32, P, P, ctypes.POINTER(ctypes.c_double)]),
     }
     for name, (res, args) in sig.items():
@@ -472,6 +477,77 @@ def fms_scores(models, I, N, K, rank, weights, pairs, flags, skip_mode, want_per
     if rc != 0:
         raise EngineError(lib.mcl_fms_last_error().decode())
     return score, perm
+
+
+EVAL_MAX_RANK = 32
+EVAL_MAX_MODELS = 65535
+
+
+def _eval_models_check(models, I, N, K, r):
+    import torch
+
+    if not (models.is_cuda and models.dtype == torch.float64 and models.is_contiguous() and models.dim() == 2
+            and models.shape[1] == (I + N + K) * r):
+        raise EngineError("models must be a contiguous float64 CUDA tensor [n_models, (I + N + K) * rank]")
+
+
+def eval_tables(X, row_ptr, rank, models):
+    """The tables of mcl_eval_tables_typed (csrc/evaluate.hip): one read of X per model.  X packed [sum J_i, K] float32 /
+    bfloat16 / float16 CUDA tensor; models float64 [n_models, (I + N + K) * rank] CUDA tensor, every model [A; B; C] row-major
+    with the weights folded into A.  -> (S [n, I, r, r], BtB [n, I, r, r], sse [n, I], norm [I]) float64 on the device."""
+    import torch
+
+    lib = load_library()
+    xt = x_type_of(X.dtype)
+    if not (X.is_cuda and X.is_contiguous() and X.dim() == 2):
+        raise EngineError("X must be a contiguous CUDA tensor [sum J_i, K]")
+    row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int64)
+    I, K, N, r = len(row_ptr) - 1, int(X.shape[1]), int(X.shape[0]), int(rank)
+    if int(row_ptr[-1]) != N:
+        raise EngineError("row_ptr must end at X.shape[0]")
+    _eval_models_check(models, I, N, K, r)
+    n = int(models.shape[0])
+    rp = row_ptr.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+    nbytes = lib.mcl_eval_workspace_bytes(rp, I, K, r, n)
+    dev = X.device
+    ws = torch.empty(max(int(nbytes), 0) + 256, dtype=torch.uint8, device=dev)
+    off = (-ws.data_ptr()) % 256
+    S = torch.empty((n, I, r, r), dtype=torch.float64, device=dev)
+    BtB = torch.empty((n, I, r, r), dtype=torch.float64, device=dev)
+    sse = torch.empty((n, I), dtype=torch.float64, device=dev)
+    norm = torch.empty(I, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = lib.mcl_eval_tables_typed(X.data_ptr(), xt, rp, I, K, r, models.data_ptr(), n, S.data_ptr(), BtB.data_ptr(), sse.data_ptr(),
+                                       norm.data_ptr(), ws.data_ptr() + off, max(int(nbytes), 0), ctypes.c_void_p(stream))
+    if rc != 0:
+        raise EngineError(lib.mcl_eval_last_error().decode())
+    return S, BtB, sse, norm
+
+
+def eval_core(models, I, N, K, rank, S, BtB):
+    """The least-squares cores and core consistencies of mcl_eval_core from the tables of eval_tables (float64 CUDA tensors
+    [n_models, I, rank, rank]).  -> (core [n, r, r, r], cc [n], cc_normalised [n]) float64 on the device."""
+    import torch
+
+    lib = load_library()
+    I, N, K, r = int(I), int(N), int(K), int(rank)
+    _eval_models_check(models, I, N, K, r)
+    n = int(models.shape[0])
+    for name, t in (("S", S), ("BtB", BtB)):
+        if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == (n, I, r, r)):
+            raise EngineError(f"{name} must be a contiguous float64 CUDA tensor [n_models, I, rank, rank]")
+    dev = models.device
+    core = torch.empty((n, r, r, r), dtype=torch.float64, device=dev)
+    cc = torch.empty(n, dtype=torch.float64, device=dev)
+    ccn = torch.empty(n, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = lib.mcl_eval_core(models.data_ptr(), n, I, N, K, r, S.data_ptr(), BtB.data_ptr(), core.data_ptr(), cc.data_ptr(),
+                               ccn.data_ptr(), ctypes.c_void_p(stream))
+    if rc != 0:
+        raise EngineError(lib.mcl_eval_last_error().decode())
+    return core, cc, ccn
 
 
 def multistart_state_len(I, N, K, rank, kinds):
