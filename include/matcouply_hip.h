@@ -419,6 +419,26 @@ int mcl_eval_core(const double *models, int64_t n_models, int64_t I, int64_t N, 
                   const double *BtB, double *core, double *cc, double *cc_normalised, void *stream);
 const char *mcl_eval_last_error(void);
 
+/* ---- new matrices fitted to a fixed PARAFAC2 model (parafac2_project, csrc/projection.hip) --------------------------------- */
+/* For every matrix X_i [J_i, K] of the packed data X [N, K] (element type x_type; row_ptr: HOST int64 [I + 1] from 0, every
+ * J_i >= rank): minimise |X_i - P Delta diag(a) C^T|_F^2 over a [rank] and P [J_i, rank] with P^T P = I by alternation from
+ * a_init[i]; the iteration and its stopping rule (per matrix: e2_t < absolute_tol, or t >= 2 and |e2_{t-1} - e2_t| <= tol e2_{t-1},
+ * or t = n_iter_max) are in DESIGN.md section 16.  Delta [rank, rank], C [K, rank] and a_init [I, rank] are fp64 device arrays,
+ * which the caller has rounded through fp32; they are read back and checked for non-finite entries before anything is launched
+ * (one synchronisation of the stream).  Outputs (device): A fp64 [I, rank]; B fp32 [N, rank] (B_i = P_i Delta) and P fp32
+ * [N, rank], packed like X; stats fp64 [I, 2] = {sse_i from the formula e2 |X_i|^2, |X_i|_F^2}; n_iter int32 [I]; errors fp64
+ * [I, n_iter_max] or NULL: the e2 of every iteration of matrix i, NaN behind its stop.  workspace: device,
+ * mcl_pf2_project_workspace_bytes bytes (-1 for shapes the entry refuses), 256-byte aligned.  Needs 1 <= rank <= 32 and rank <= K (W = X C has rank K at most: below, P would be a partial isometry).  Every bad
+ * argument is refused with a message before any launch.  Stateless; the work is enqueued on the stream.  No atomics and a fixed
+ * summation order that depends on a matrix's own shape only: a matrix's result does not depend on the other matrices of the call,
+ * and two runs are bitwise equal. */
+int64_t mcl_pf2_project_workspace_bytes(const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank);
+int mcl_pf2_project_typed(const void *X, int32_t x_type, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank, const double *Delta,
+                          const double *C, const double *a_init, int32_t n_iter_max, double tol, double absolute_tol, double *A, float *B,
+                          float *P, double *stats, int32_t *n_iter, double *errors, void *workspace, int64_t workspace_bytes,
+                          void *hip_stream);
+const char *mcl_pf2_project_last_error(void);
+
 /* ---- introspection for tests / profiling ------------------------------------------------------------- */
 /* device pointers to internal by-products / planner tables (the int32 tables: read the bits) */
 enum mcl_buffer_id {

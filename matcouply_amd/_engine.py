@@ -66,6 +66,7 @@ EXPORTED_SYMBOLS = [
     "mcl_pf2als_multistart_workspace_bytes", "mcl_pf2als_multistart_run", "mcl_pf2als_multistart_last_error",
     "mcl_fms_workspace_bytes", "mcl_fms_scores", "mcl_fms_last_error",
     "mcl_eval_workspace_bytes", "mcl_eval_tables_typed", "mcl_eval_core", "mcl_eval_last_error",
+    "mcl_pf2_project_workspace_bytes", "mcl_pf2_project_typed", "mcl_pf2_project_last_error",
 ]
 
 
@@ -212,6 +213,10 @@ def load_library():
         "mcl_eval_tables_typed": (ctypes.c_int, [P, I32, ctypes.POINTER(I64), I64, I64, I32, P, I64, P, P, P, P, P, I64, P]),
         "mcl_eval_core": (ctypes.c_int, [P, I64, I64, I64, I64, I32, P, P, P, P, P, P]),
         "mcl_eval_last_error": (ctypes.c_char_p, []),
+        "mcl_pf2_project_workspace_bytes": (I64, [ctypes.POINTER(I64), I64, I64, I32]),
+        "mcl_pf2_project_typed": (ctypes.c_int, [P, I32, ctypes.POINTER(I64), I64, I64, I32, P, P, P, I32, ctypes.c_double,
+                                                 ctypes.c_double, P, P, P, P, P, P, P, I64, P]),
+        "mcl_pf2_project_last_error": (ctypes.c_char_p, []),
         "mcl_read_bandwidth": (ctypes.c_int, [P, I64, I32, P, P, ctypes.POINTER(ctypes.c_double)]),
     }
     for name, (res, args) in sig.items():
@@ -548,6 +553,50 @@ def eval_core(models, I, N, K, rank, S, BtB):
     if rc != 0:
         raise EngineError(lib.mcl_eval_last_error().decode())
     return core, cc, ccn
+
+
+PROJECT_MAX_RANK = 32
+PROJECT_MAX_ROWS = 1 << 26  # packed rows, and K: the kernels index rows x rank with 32 bits
+
+
+def pf2_project(X, row_ptr, rank, Delta, C, a_init, n_iter_max, tol, absolute_tol, want_errors):
+    """New matrices fitted to a fixed PARAFAC2 model on the device (mcl_pf2_project_typed, csrc/projection.hip).  X packed
+    [sum J_i, K] float32 / bfloat16 / float16 CUDA tensor; Delta [rank, rank], C [K, rank], a_init [I, rank]: float64 CUDA tensors
+    holding float32 values.  -> (A float64 [I, rank], B float32 [sum J_i, rank], P float32 [sum J_i, rank], stats float64 [I, 2]
+    (sse, |X_i|^2), n_iter int32 [I], errors float64 [I, n_iter_max] or None) on the device."""
+    import torch
+
+    lib = load_library()
+    xt = x_type_of(X.dtype)
+    if not (X.is_cuda and X.is_contiguous() and X.dim() == 2):
+        raise EngineError("X must be a contiguous CUDA tensor [sum J_i, K]")
+    row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int64)
+    I, K, N, r = len(row_ptr) - 1, int(X.shape[1]), int(X.shape[0]), int(rank)
+    if int(row_ptr[-1]) != N:
+        raise EngineError("row_ptr must end at X.shape[0]")
+    for name, t, shp in (("Delta", Delta, (r, r)), ("C", C, (K, r)), ("a_init", a_init, (I, r))):
+        if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == shp):
+            raise EngineError(f"{name} must be a contiguous float64 CUDA tensor {list(shp)}")
+    rp = row_ptr.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+    nbytes = lib.mcl_pf2_project_workspace_bytes(rp, I, K, r)
+    dev = X.device
+    ws = torch.empty(max(int(nbytes), 0) + 256, dtype=torch.uint8, device=dev)
+    off = (-ws.data_ptr()) % 256
+    A = torch.empty((I, r), dtype=torch.float64, device=dev)
+    B = torch.empty((N, r), dtype=torch.float32, device=dev)
+    Pm = torch.empty((N, r), dtype=torch.float32, device=dev)
+    stats = torch.empty((I, 2), dtype=torch.float64, device=dev)
+    n_iter = torch.empty(I, dtype=torch.int32, device=dev)
+    errors = torch.empty((I, int(n_iter_max)), dtype=torch.float64, device=dev) if want_errors else None
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = lib.mcl_pf2_project_typed(X.data_ptr(), xt, rp, I, K, r, Delta.data_ptr(), C.data_ptr(), a_init.data_ptr(), int(n_iter_max),
+                                       float(tol), float(absolute_tol), A.data_ptr(), B.data_ptr(), Pm.data_ptr(), stats.data_ptr(),
+                                       n_iter.data_ptr(), errors.data_ptr() if want_errors else None, ws.data_ptr() + off,
+                                       max(int(nbytes), 0), ctypes.c_void_p(stream))
+    if rc != 0:
+        raise EngineError(lib.mcl_pf2_project_last_error().decode())
+    return A, B, Pm, stats, n_iter, errors
 
 
 def multistart_state_len(I, N, K, rank, kinds):
