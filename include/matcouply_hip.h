@@ -380,6 +380,17 @@ int mcl_pf2als_multistart_run(const void *X, int32_t x_type, const int64_t *row_
                               int32_t n_iter_max, int32_t n_iter_parafac, double tol, double absolute_tol, int32_t nn_modes,
                               double *factors, double *P, double *errors, int32_t *n_iter, void *workspace, int64_t workspace_bytes,
                               void *hip_stream);
+/* The same fit of per-job scaled matrices (parafac2_als_resample: bootstrap, jackknife and K-fold over the matrices): job s =
+ * workgroup s fits the matrices slab_scale[s][i] X_i, every element multiplied after its exact conversion to double, and no job
+ * holds an X of its own.  slab_scale: DEVICE fp64 [n_starts, I], the square roots of the job's weights (finite, >= 0; NULL is an
+ * error).  With w = slab_scale^2 the job minimises sum_i w_i |X_i - P_i B D_i C^T|^2 once row i of its A is divided by
+ * slab_scale[s][i]; errors hold the weighted relative error.  A matrix of scale 0 whose start row of A is 0 keeps that row and
+ * its P_i at exact zeros.  Everything else, the workspace included, is as for mcl_pf2als_multistart_run; with every scale 1 the
+ * results are bitwise its results, and a job's result does not depend on its neighbours' scales. */
+int mcl_pf2als_multistart_run_weighted(const void *X, int32_t x_type, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank,
+                                       int32_t n_starts, const double *slab_scale, int32_t n_iter_max, int32_t n_iter_parafac, double tol,
+                                       double absolute_tol, int32_t nn_modes, double *factors, double *P, double *errors, int32_t *n_iter,
+                                       void *workspace, int64_t workspace_bytes, void *hip_stream);
 const char *mcl_pf2als_multistart_last_error(void);
 
 /* ---- factor match scores of many pairs of fitted models (multistart_similarity, csrc/similarity.hip) ---------------------- */

@@ -64,6 +64,7 @@ EXPORTED_SYMBOLS = [
     "mcl_multistart_grid_workspace_bytes", "mcl_multistart_run_grid",
     "mcl_parafac2_als_workspace_bytes", "mcl_parafac2_als_typed", "mcl_parafac2_als_last_error",
     "mcl_pf2als_multistart_workspace_bytes", "mcl_pf2als_multistart_run", "mcl_pf2als_multistart_last_error",
+    "mcl_pf2als_multistart_run_weighted",
     "mcl_fms_workspace_bytes", "mcl_fms_scores", "mcl_fms_last_error",
     "mcl_eval_workspace_bytes", "mcl_eval_tables_typed", "mcl_eval_core", "mcl_eval_last_error",
     "mcl_pf2_project_workspace_bytes", "mcl_pf2_project_typed", "mcl_pf2_project_last_error",
@@ -205,6 +206,8 @@ def load_library():
         "mcl_pf2als_multistart_workspace_bytes": (I64, [ctypes.POINTER(I64), I64, I64, I32, I32]),
         "mcl_pf2als_multistart_run": (ctypes.c_int, [P, I32, ctypes.POINTER(I64), I64, I64, I32, I32, I32, I32, ctypes.c_double,
                                                      ctypes.c_double, I32, P, P, P, P, P, I64, P]),
+        "mcl_pf2als_multistart_run_weighted": (ctypes.c_int, [P, I32, ctypes.POINTER(I64), I64, I64, I32, I32, P, I32, I32,
+                                                              ctypes.c_double, ctypes.c_double, I32, P, P, P, P, P, I64, P]),
         "mcl_pf2als_multistart_last_error": (ctypes.c_char_p, []),
         "mcl_fms_workspace_bytes": (I64, [I64, I32]),
         "mcl_fms_scores": (ctypes.c_int, [P, I64, I64, I64, I64, I32, P, ctypes.POINTER(I32), I64, I32, I32, P, P, P, P]),
@@ -412,6 +415,30 @@ def pf2als_multistart_run(X, row_ptr, rank, factors, n_iter_max, n_iter_parafac,
     tensor (A, B, C of every start), updated in place; nn_modes: modes (0 / 2) fitted non-negative.  -> (P float64
     [n_starts, sum J_i, rank] (the projections), errors float64 [n_starts, n_iter_max] (rows valid up to n_iter when tol > 0),
     n_iter int32 [n_starts]) on the device."""
+    return _pf2als_multistart_launch(X, row_ptr, rank, factors, None, n_iter_max, n_iter_parafac, tol, absolute_tol, nn_modes)
+
+
+def pf2als_multistart_run_weighted(X, row_ptr, rank, factors, slab_scale, n_iter_max, n_iter_parafac, tol, absolute_tol, nn_modes):
+    """pf2als_multistart_run on per-job scaled matrices (mcl_pf2als_multistart_run_weighted): job s fits slab_scale[s, i] X_i.
+    slab_scale: float64 [n_jobs, I] CUDA tensor, the square roots of the job's weights (layout: pf2als_slab_scale_offset).  The
+    factors come back in the scaled problem's units (row i of A still carries slab_scale[s, i]); errors are the weighted
+    relative errors."""
+    import torch
+
+    I = len(row_ptr) - 1
+    if not (torch.is_tensor(slab_scale) and slab_scale.is_cuda and slab_scale.dtype == torch.float64 and slab_scale.is_contiguous()
+            and tuple(slab_scale.shape) == (int(factors.shape[0]), I)):
+        raise EngineError("slab_scale must be a contiguous float64 CUDA tensor [n_jobs, I]")
+    return _pf2als_multistart_launch(X, row_ptr, rank, factors, slab_scale, n_iter_max, n_iter_parafac, tol, absolute_tol, nn_modes)
+
+
+def pf2als_slab_scale_offset(I, job, slab):
+    """index (in doubles) of job `job`'s factor of matrix `slab` in the slab_scale array of mcl_pf2als_multistart_run_weighted:
+    [n_jobs, I] row-major, no padding; job s = workgroup s reads the I doubles from pf2als_slab_scale_offset(I, s, 0) on"""
+    return int(job) * int(I) + int(slab)
+
+
+def _pf2als_multistart_launch(X, row_ptr, rank, factors, slab_scale, n_iter_max, n_iter_parafac, tol, absolute_tol, nn_modes):
     import torch
 
     lib = load_library()
@@ -438,9 +465,12 @@ def pf2als_multistart_run(X, row_ptr, rank, factors, n_iter_max, n_iter_parafac,
     mask = sum(1 << int(m) for m in (nn_modes or ()))
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = lib.mcl_pf2als_multistart_run(X.data_ptr(), xt, rp, I, K, r, S, int(n_iter_max), int(n_iter_parafac), float(tol),
-                                           float(absolute_tol), int(mask), factors.data_ptr(), P.data_ptr(), errors.data_ptr(),
-                                           n_iter.data_ptr(), ws.data_ptr() + off, nbytes, ctypes.c_void_p(stream))
+        tail = (int(n_iter_max), int(n_iter_parafac), float(tol), float(absolute_tol), int(mask), factors.data_ptr(), P.data_ptr(),
+                errors.data_ptr(), n_iter.data_ptr(), ws.data_ptr() + off, nbytes, ctypes.c_void_p(stream))
+        if slab_scale is None:
+            rc = lib.mcl_pf2als_multistart_run(X.data_ptr(), xt, rp, I, K, r, S, *tail)
+        else:
+            rc = lib.mcl_pf2als_multistart_run_weighted(X.data_ptr(), xt, rp, I, K, r, S, slab_scale.data_ptr(), *tail)
     if rc != 0:
         raise EngineError(lib.mcl_pf2als_multistart_last_error().decode())
     return P, errors, n_iter

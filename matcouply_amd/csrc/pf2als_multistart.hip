@@ -17,6 +17,9 @@
 // fixed order that depends only on the problem's shape (wg_fp64.h), so a start's result is bitwise independent of how many
 // starts share the launch and of which.
 //
+// parafac2_als_resample (resampling.py): k_ms_pf2als_weighted is the same fit of the matrices
+// scale[s][i] X_i, job s reading its own I factors - bootstrap, jackknife and K-fold jobs over the matrices share the one X.
+//
 // Memory: X, row_ptr and the row -> slab map are shared.  Each start owns its factors (the caller's fp64 [I + r + K, r]), its
 // projections and errors, and a slice of the fp64 scratch workspace: W [N, r], Y [I, r, K], T / WtW / V [I, r, r], M_A [I, r],
 // M_C [K, r].  The r x r matrices of the sweeps (B, the Grams, M_B) live in LDS.
@@ -68,7 +71,9 @@ static __host__ __device__ inline PmScratch pm_scratch(int64_t I, int64_t N, int
     return s;
 }
 
-template <int R, class XL>
+// SCALED: the job fits the matrices scale_i X_i (resampling over the matrices): every element of X_i is
+// multiplied by the job's factor of slab i after the exact conversion to double.  Without SCALED `scale` is never read.
+template <int R, class XL, bool SCALED>
 struct Pf2Start {
     static constexpr int RR = R * R;
     const typename XL::T *X;
@@ -139,16 +144,27 @@ struct Pf2Start {
     }
 
     // W = X C, WtW_i, then per slab T_i = D_i B^T G_i^-1/2 (one thread per slab, a batch at a time in LDS), then Y_i
-    __device__ __forceinline__ void project() {
+    // (scale: the job's factor per slab [I], SCALED only)
+    __device__ __forceinline__ void project(const double *scale) {
         const int t = threadIdx.x;
         for (int64_t j = t; j < N; j += MS_THREADS) {
             double acc[R];
             #pragma unroll
             for (int l = 0; l < R; ++l) acc[l] = 0.0;
-            for (int64_t c = 0; c < K; ++c) {
-                const double xv = x(j, c);
-                #pragma unroll
-                for (int l = 0; l < R; ++l) acc[l] += xv * C[c * R + l];
+            if constexpr (SCALED) {
+                const double f = scale[slab[j]];
+                if (f != 0.0)  // a slab of scale 0 has W = 0 either way: its pass over X is skipped
+                    for (int64_t c = 0; c < K; ++c) {
+                        const double xv = x(j, c) * f;
+                        #pragma unroll
+                        for (int l = 0; l < R; ++l) acc[l] += xv * C[c * R + l];
+                    }
+            } else {
+                for (int64_t c = 0; c < K; ++c) {
+                    const double xv = x(j, c);
+                    #pragma unroll
+                    for (int l = 0; l < R; ++l) acc[l] += xv * C[c * R + l];
+                }
             }
             #pragma unroll
             for (int l = 0; l < R; ++l) W[j * R + l] = acc[l];
@@ -200,10 +216,20 @@ struct Pf2Start {
             double z[R];
             #pragma unroll
             for (int p = 0; p < R; ++p) z[p] = 0.0;
-            for (int64_t j = rp[i]; j < rp[i + 1]; ++j) {
-                const double xv = x(j, k);
-                #pragma unroll
-                for (int p = 0; p < R; ++p) z[p] += W[j * R + p] * xv;
+            if constexpr (SCALED) {
+                const double f = scale[i];
+                if (f != 0.0)  // W_i = 0 and T_i = 0: Y_i is written as zeros below
+                    for (int64_t j = rp[i]; j < rp[i + 1]; ++j) {
+                        const double xv = x(j, k) * f;
+                        #pragma unroll
+                        for (int p = 0; p < R; ++p) z[p] += W[j * R + p] * xv;
+                    }
+            } else {
+                for (int64_t j = rp[i]; j < rp[i + 1]; ++j) {
+                    const double xv = x(j, k);
+                    #pragma unroll
+                    for (int p = 0; p < R; ++p) z[p] += W[j * R + p] * xv;
+                }
             }
             const double *Ti = T + i * RR;
             #pragma unroll 1
@@ -310,62 +336,90 @@ struct Pf2Start {
         const double fit = wg_sum(f, red);
         return x_sq > 0.0 ? fmax(0.0, x_sq - 2.0 * cross + fit) / x_sq : 0.0;
     }
+
+    // the factors, the scratch slice and the LDS of start blockIdx.x
+    __device__ __forceinline__ void bind(const PmArgs a, double *red_, double *sys_, double *small) {
+        const int64_t s = blockIdx.x;
+        X = static_cast<const typename XL::T *>(a.X), rp = a.row_ptr, slab = a.slab_of_row, I = a.I, N = a.N, K = a.K;
+        A = a.factors + s * (a.I + R + a.K) * R;
+        B = A + a.I * R;
+        C = B + RR;
+        double *ws = a.scratch + s * a.scratch_len;
+        const PmScratch sc = pm_scratch(a.I, a.N, a.K, R);
+        W = ws + sc.W, Y = ws + sc.Y, T = ws + sc.T, WtW = ws + sc.WtW, V = ws + sc.V, MA = ws + sc.MA, MC = ws + sc.MC;
+        red = red_, sys = sys_;
+        Bs = small, BtB = small + RR, CtC = small + 2 * RR, AtA = small + 3 * RR, MB = small + 4 * RR;
+        nb = std::min(MS_THREADS, PM_SYS_BYTES / (2 * RR * 8));
+    }
+
+    // the whole fit of the start: the body of k_ms_pf2als (SCALED false, scale unused) and of k_ms_pf2als_weighted (SCALED true,
+    // scale: the job's factor per slab [I])
+    __device__ __forceinline__ void fit(const PmArgs a, const double *scale) {
+        const int64_t s = blockIdx.x;
+        const int t = threadIdx.x;
+        if (t < RR) Bs[t] = B[t];
+
+        double xs = 0.0;  // |X|^2 (every start: the same order, the same bits); SCALED: sum_i scale_i^2 |X_i|^2, in that order too
+        for (int64_t e = t; e < N * K; e += MS_THREADS) {
+            double v = x(0, e);
+            if constexpr (SCALED) v *= scale[slab[e / K]];
+            xs += v * v;
+        }
+        const double x_sq = wg_sum(xs, red);  // (its barriers also publish Bs)
+
+        const bool hals_a = a.nn_modes & 1, hals_c = (a.nn_modes >> 2) & 1;
+        double *errors = a.errors ? a.errors + s * a.n_iter_max : nullptr;
+        double prev = 0.0;
+        int it = 0;
+        while (it < a.n_iter_max) {
+            project(scale);
+            for (int sw = 0; sw < a.n_iter_parafac; ++sw) sweep(hals_a, hals_c);
+            ++it;
+            if (a.tol > 0.0) {
+                const double e2 = error_sq(x_sq);
+                if (t == 0) errors[it - 1] = sqrt(e2);
+                const bool stop = it >= 2 && (fabs(prev - e2) <= a.tol * prev || e2 < a.absolute_tol);
+                prev = e2;
+                if (stop) break;
+            }
+        }
+        double *P = a.P + s * N * R;
+        for (int64_t e = t; e < N * R; e += MS_THREADS) {  // P = W T, from the last iteration's W and T
+            const int64_t j = e / R;
+            const int q = (int)(e % R);
+            const double *Ti = T + (int64_t)slab[j] * RR;
+            double v = 0.0;
+            for (int p = 0; p < R; ++p) v += W[j * R + p] * Ti[p * R + q];
+            P[e] = v;
+        }
+        if (t == 0) a.n_iter[s] = it;
+    }
 };
+
+// The LDS of a start is declared in the kernels, and `st` lives in them: with either inside a function both kernels call, the
+// unweighted instantiations no longer get the registers they had (rank 14: 382 VGPRs for 168).
+#define PM_START_LDS                       \
+    __shared__ double red[MS_THREADS];     \
+    __shared__ double sys[PM_SYS_BYTES / 8]; \
+    __shared__ double small[5 * R * R];
 
 template <int R, class XL>
 __global__ __launch_bounds__(MS_THREADS) void k_ms_pf2als(PmArgs a) {
-    constexpr int RR = R * R;
-    __shared__ double red[MS_THREADS];
-    __shared__ double sys[PM_SYS_BYTES / 8];
-    __shared__ double small[5 * RR];
-    const int64_t s = blockIdx.x;
-    const int t = threadIdx.x;
-    Pf2Start<R, XL> st{static_cast<const typename XL::T *>(a.X), a.row_ptr, a.slab_of_row, a.I, a.N, a.K};
-    st.A = a.factors + s * (a.I + R + a.K) * R;
-    st.B = st.A + a.I * R;
-    st.C = st.B + RR;
-    double *ws = a.scratch + s * a.scratch_len;
-    const PmScratch sc = pm_scratch(a.I, a.N, a.K, R);
-    st.W = ws + sc.W, st.Y = ws + sc.Y, st.T = ws + sc.T, st.WtW = ws + sc.WtW, st.V = ws + sc.V, st.MA = ws + sc.MA, st.MC = ws + sc.MC;
-    st.red = red, st.sys = sys;
-    st.Bs = small, st.BtB = small + RR, st.CtC = small + 2 * RR, st.AtA = small + 3 * RR, st.MB = small + 4 * RR;
-    st.nb = std::min(MS_THREADS, PM_SYS_BYTES / (2 * RR * 8));
-    if (t < RR) st.Bs[t] = st.B[t];
-
-    double xs = 0.0;  // |X|^2 (every start: the same order, the same bits)
-    for (int64_t e = t; e < a.N * a.K; e += MS_THREADS) {
-        const double v = st.x(0, e);
-        xs += v * v;
-    }
-    const double x_sq = wg_sum(xs, red);  // (its barriers also publish Bs)
-
-    const bool hals_a = a.nn_modes & 1, hals_c = (a.nn_modes >> 2) & 1;
-    double *errors = a.errors ? a.errors + s * a.n_iter_max : nullptr;
-    double prev = 0.0;
-    int it = 0;
-    while (it < a.n_iter_max) {
-        st.project();
-        for (int sw = 0; sw < a.n_iter_parafac; ++sw) st.sweep(hals_a, hals_c);
-        ++it;
-        if (a.tol > 0.0) {
-            const double e2 = st.error_sq(x_sq);
-            if (t == 0) errors[it - 1] = sqrt(e2);
-            const bool stop = it >= 2 && (fabs(prev - e2) <= a.tol * prev || e2 < a.absolute_tol);
-            prev = e2;
-            if (stop) break;
-        }
-    }
-    double *P = a.P + s * a.N * R;
-    for (int64_t e = t; e < a.N * R; e += MS_THREADS) {  // P = W T, from the last iteration's W and T
-        const int64_t j = e / R;
-        const int q = (int)(e % R);
-        const double *Ti = st.T + (int64_t)st.slab[j] * RR;
-        double v = 0.0;
-        for (int p = 0; p < R; ++p) v += st.W[j * R + p] * Ti[p * R + q];
-        P[e] = v;
-    }
-    if (t == 0) a.n_iter[s] = it;
+    PM_START_LDS
+    Pf2Start<R, XL, false> st;
+    st.bind(a, red, sys, small);
+    st.fit(a, nullptr);
 }
+
+// slab_scale: fp64 [gridDim.x, I]; job blockIdx.x reads its own row and nothing of its neighbours'
+template <int R, class XL>
+__global__ __launch_bounds__(MS_THREADS) void k_ms_pf2als_weighted(PmArgs a, const double *slab_scale) {
+    PM_START_LDS
+    Pf2Start<R, XL, true> st;
+    st.bind(a, red, sys, small);
+    st.fit(a, slab_scale + (int64_t)blockIdx.x * a.I);
+}
+#undef PM_START_LDS
 
 struct PmPlan {
     int64_t N, scratch_len, off_rowptr, off_slab, off_scratch, total;
@@ -396,37 +450,31 @@ PmPlan pm_plan(const int64_t *row_ptr, int64_t I, int64_t K, int rank, int32_t n
 }
 
 template <class XL>
-void pm_launch(int rank, const PmArgs &a, int n_starts, hipStream_t s) {
+void pm_launch(int rank, const PmArgs &a, const double *slab_scale, int n_starts, hipStream_t s) {
     switch (rank) {
-#define PM_CASE(R) \
-    case R: hipLaunchKernelGGL((k_ms_pf2als<R, XL>), dim3(n_starts), dim3(MS_THREADS), 0, s, a); break;
+#define PM_CASE(R)                                                                                                          \
+    case R:                                                                                                                 \
+        if (slab_scale) hipLaunchKernelGGL((k_ms_pf2als_weighted<R, XL>), dim3(n_starts), dim3(MS_THREADS), 0, s, a, slab_scale); \
+        else hipLaunchKernelGGL((k_ms_pf2als<R, XL>), dim3(n_starts), dim3(MS_THREADS), 0, s, a);                           \
+        break;
         PM_CASE(1) PM_CASE(2) PM_CASE(3) PM_CASE(4) PM_CASE(5) PM_CASE(6) PM_CASE(7) PM_CASE(8)
         PM_CASE(9) PM_CASE(10) PM_CASE(11) PM_CASE(12) PM_CASE(13) PM_CASE(14) PM_CASE(15) PM_CASE(16)
 #undef PM_CASE
     }
 }
 
-}  // namespace
-
-extern "C" {
-
-const char *mcl_pf2als_multistart_last_error(void) { return g_pm_error.c_str(); }
-
-int64_t mcl_pf2als_multistart_workspace_bytes(const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank, int32_t n_starts) {
-    if (!pm_check(row_ptr, I, K, rank, n_starts).empty()) return -1;
-    return pm_plan(row_ptr, I, K, rank, n_starts).total;
-}
-
-int mcl_pf2als_multistart_run(const void *X, int32_t x_type, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank, int32_t n_starts,
-                              int32_t n_iter_max, int32_t n_iter_parafac, double tol, double absolute_tol, int32_t nn_modes,
-                              double *factors, double *P, double *errors, int32_t *n_iter, void *workspace, int64_t workspace_bytes,
-                              void *hip_stream) {
-    auto fail = [](const std::string &m) {
-        g_pm_error = "mcl_pf2als_multistart_run: " + m;
+// mcl_pf2als_multistart_run (weighted false, slab_scale unused) and mcl_pf2als_multistart_run_weighted
+int pm_run(const char *who, bool weighted, const double *slab_scale, const void *X, int32_t x_type, const int64_t *row_ptr, int64_t I,
+           int64_t K, int32_t rank, int32_t n_starts, int32_t n_iter_max, int32_t n_iter_parafac, double tol, double absolute_tol,
+           int32_t nn_modes, double *factors, double *P, double *errors, int32_t *n_iter, void *workspace, int64_t workspace_bytes,
+           void *hip_stream) {
+    auto fail = [who](const std::string &m) {
+        g_pm_error = std::string(who) + ": " + m;
         return 1;
     };
     const std::string bad = pm_check(row_ptr, I, K, rank, n_starts);
     if (!bad.empty()) return fail(bad);
+    if (weighted && !slab_scale) return fail("slab_scale is NULL (a device array [n_starts, I] of the square roots of the weights)");
     if (!X || !factors || !P || !n_iter || !workspace || (tol > 0.0 && !errors)) return fail("NULL argument");
     if (x_type != MCL_X_F32 && x_type != MCL_X_BF16 && x_type != MCL_X_F16)
         return fail("unknown x_type " + std::to_string(x_type) + " (MCL_X_F32 = 0, MCL_X_BF16 = 1, MCL_X_F16 = 2)");
@@ -458,12 +506,39 @@ int mcl_pf2als_multistart_run(const void *X, int32_t x_type, const int64_t *row_
     a.tol = tol, a.absolute_tol = absolute_tol;
     mcl_x_dispatch(x_type, [&](auto xl) {
         using XL = decltype(xl);
-        pm_launch<XL>(rank, a, n_starts, s);
+        pm_launch<XL>(rank, a, weighted ? slab_scale : nullptr, n_starts, s);
         return 0;
     });
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(std::string("launch failed: ") + hipGetErrorString(e));
     return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char *mcl_pf2als_multistart_last_error(void) { return g_pm_error.c_str(); }
+
+int64_t mcl_pf2als_multistart_workspace_bytes(const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank, int32_t n_starts) {
+    if (!pm_check(row_ptr, I, K, rank, n_starts).empty()) return -1;
+    return pm_plan(row_ptr, I, K, rank, n_starts).total;
+}
+
+int mcl_pf2als_multistart_run(const void *X, int32_t x_type, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank, int32_t n_starts,
+                              int32_t n_iter_max, int32_t n_iter_parafac, double tol, double absolute_tol, int32_t nn_modes,
+                              double *factors, double *P, double *errors, int32_t *n_iter, void *workspace, int64_t workspace_bytes,
+                              void *hip_stream) {
+    return pm_run("mcl_pf2als_multistart_run", false, nullptr, X, x_type, row_ptr, I, K, rank, n_starts, n_iter_max, n_iter_parafac, tol,
+                  absolute_tol, nn_modes, factors, P, errors, n_iter, workspace, workspace_bytes, hip_stream);
+}
+
+int mcl_pf2als_multistart_run_weighted(const void *X, int32_t x_type, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank,
+                                       int32_t n_starts, const double *slab_scale, int32_t n_iter_max, int32_t n_iter_parafac, double tol,
+                                       double absolute_tol, int32_t nn_modes, double *factors, double *P, double *errors, int32_t *n_iter,
+                                       void *workspace, int64_t workspace_bytes, void *hip_stream) {
+    return pm_run("mcl_pf2als_multistart_run_weighted", true, slab_scale, X, x_type, row_ptr, I, K, rank, n_starts, n_iter_max,
+                  n_iter_parafac, tol, absolute_tol, nn_modes, factors, P, errors, n_iter, workspace, workspace_bytes, hip_stream);
 }
 
 }  // extern "C"
