@@ -53,6 +53,11 @@ def native_regs(descs, aux, dual, device):
             out.append(NativeReg(kind, t(z), t(u), p0=d["reg_strength"], p1=d.get("l1_strength", 0.0)))
         elif d["kind"] == "unimodal":
             out.append(NativeReg(kind, t(z), t(u), non_negativity=d.get("non_negativity", False)))
+        elif d["kind"] == "gl2":  # fp64 [U | s | U^T] of the norm matrix, as the solver hands it over (decomposition.py)
+            from matcouply_amd import penalties as pen
+
+            mat, n = pen.GeneralizedL2Penalty(np.asarray(d["norm_matrix"], dtype=np.float64), validate=False)._native_matrix()
+            out.append(NativeReg(kind, t(z), t(u), matrix=torch.tensor(mat, dtype=torch.float64, device=device), matrix_rows=n))
         else:
             out.append(NativeReg(kind, t(z), t(u)))
     return out

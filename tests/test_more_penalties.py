@@ -196,12 +196,7 @@ def test_generalized_l2_keyword():
 
 # ---- TotalVariationPenalty: the reference's prox lives in the absent GPL package condat_tv, so the anchor is the
 # ---- optimality system of the problem itself (plus a brute-force dual solver on small inputs)
-def _tv_kkt(x, y, lam, tol=1e-9):
-    u = np.cumsum(x - y)           # -u[:-1] is the dual variable of the differences
-    assert abs(u[-1]) < tol * max(1.0, np.abs(x).sum())
-    s, d = -u[:-1], np.diff(y)
-    assert np.all(np.abs(s) <= lam + tol)
-    assert np.all(np.abs(s[d > 1e-12] - lam) < 1e-7) and np.all(np.abs(s[d < -1e-12] + lam) < 1e-7)
+from tests.prox_cases import _tv_kkt  # noqa: E402  (the dual-variable system; shared with the prox-kernel tests)
 
 
 def _tv_brute(x, lam, iters=20000):
