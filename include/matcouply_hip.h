@@ -363,6 +363,21 @@ int64_t mcl_multistart_grid_workspace_bytes(const int64_t *row_ptr, int64_t I, i
 int mcl_multistart_run_grid(const void *X, int32_t x_type, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank,
                             const mcl_multistart_options *options, int32_t n_jobs, double *state, double *diag, int32_t *n_iter,
                             int32_t *stop, void *workspace, int64_t workspace_bytes, void *hip_stream);
+/* Weighted jobs in the same launch (cmf_aoadmm_resample: bootstrap, jackknife and K-fold over the matrices): job s minimises
+ * 0.5 sum_i w_si |X_i - B_i D_i C^T|^2 / sum_i w_si |X_i|^2 + penalties + l2 terms, the AO-ADMM run of mcl_multistart_run with
+ * every per-matrix Gram and right-hand side multiplied by w_si; rec_error is the weighted relative error.  slab_weights is a
+ * HOST fp64 array [n_jobs, I], uploaded to the workspace: every weight finite and >= 0, a positive one in every job (else an
+ * error, before any launch).  A matrix of weight 0 is not in the job: the caller zeroes its row of A, its B_i and its rows of
+ * every aux and dual of modes 0 and 1 (its P_i for PARAFAC2) in the job's state slice; the kernel writes a zero inverse for its
+ * systems, skips its prox and dual steps and its passes over X, and returns those rows as exact zeros.  Everything else is as
+ * for mcl_multistart_run (one *opt for all jobs).  A job's result does not depend on n_jobs or on its neighbours' weights; with
+ * every weight 1 the state, diag, n_iter and stop are bitwise those of mcl_multistart_run. */
+int64_t mcl_multistart_weighted_workspace_bytes(const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank,
+                                                const mcl_multistart_options *opt, int32_t n_jobs);
+int mcl_multistart_run_weighted(const void *X, int32_t x_type, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank,
+                                const mcl_multistart_options *opt, int32_t n_jobs, const double *slab_weights, double *state,
+                                double *diag, int32_t *n_iter, int32_t *stop, void *workspace, int64_t workspace_bytes,
+                                void *hip_stream);
 
 /* ---- many random starts of parafac2_als at once (parafac2_als_multistart, csrc/pf2als_multistart.hip) ---------------------- */
 /* One workgroup per start runs the whole unconstrained PARAFAC2-ALS fit of mcl_parafac2_als_typed (projections from the polar

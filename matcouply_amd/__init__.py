@@ -12,5 +12,6 @@ from .similarity import factor_match_score, multistart_similarity, permute_cmf  
 from .evaluation import (ModelEvaluation, core_consistency, fit, multistart_evaluation, relative_sse,  # noqa: F401,E402
                          slabwise_sse)
 from .projection import Projection, parafac2_project  # noqa: F401,E402
-from .resampling import (parafac2_als_resample, resample_heldout_sse, resample_summary,  # noqa: F401,E402
+from .resampling import (cmf_aoadmm_resample, cmf_resample_summary, parafac2_als_resample,  # noqa: F401,E402
+                         parafac2_aoadmm_heldout_sse, parafac2_aoadmm_resample, resample_heldout_sse, resample_summary,
                          resampling_weights)

@@ -62,6 +62,7 @@ EXPORTED_SYMBOLS = [
     "mcl_als_init_workspace_bytes", "mcl_als_init_typed", "mcl_als_init_last_error",
     "mcl_multistart_workspace_bytes", "mcl_multistart_run", "mcl_multistart_last_error",
     "mcl_multistart_grid_workspace_bytes", "mcl_multistart_run_grid",
+    "mcl_multistart_weighted_workspace_bytes", "mcl_multistart_run_weighted",
     "mcl_parafac2_als_workspace_bytes", "mcl_parafac2_als_typed", "mcl_parafac2_als_last_error",
     "mcl_pf2als_multistart_workspace_bytes", "mcl_pf2als_multistart_run", "mcl_pf2als_multistart_last_error",
     "mcl_pf2als_multistart_run_weighted",
@@ -199,6 +200,9 @@ def load_library():
         "mcl_multistart_grid_workspace_bytes": (I64, [ctypes.POINTER(I64), I64, I64, I32, ctypes.POINTER(MultistartOptions), I32]),
         "mcl_multistart_run_grid": (ctypes.c_int, [P, I32, ctypes.POINTER(I64), I64, I64, I32, ctypes.POINTER(MultistartOptions), I32,
                                                    P, P, P, P, P, I64, P]),
+        "mcl_multistart_weighted_workspace_bytes": (I64, [ctypes.POINTER(I64), I64, I64, I32, ctypes.POINTER(MultistartOptions), I32]),
+        "mcl_multistart_run_weighted": (ctypes.c_int, [P, I32, ctypes.POINTER(I64), I64, I64, I32, ctypes.POINTER(MultistartOptions),
+                                                       I32, P, P, P, P, P, P, I64, P]),
         "mcl_parafac2_als_workspace_bytes": (I64, [ctypes.POINTER(I64), I64, I64, I32]),
         "mcl_parafac2_als_typed": (ctypes.c_int, [P, I32, ctypes.POINTER(I64), I64, I64, I32, P, P, P, I32, I32, ctypes.c_double,
                                                   ctypes.c_double, I32, P, P, P, P, P, P, P, I64, P]),
@@ -697,6 +701,22 @@ def multistart_run_grid(X, row_ptr, rank, options, state):
     array = (MultistartOptions * len(options))(*options)
     return _multistart_launch(X, row_ptr, rank, array, len(options), state, lib.mcl_multistart_grid_workspace_bytes,
                               lib.mcl_multistart_run_grid)
+
+
+def multistart_run_weighted(X, row_ptr, rank, options, slab_weights, state):
+    """multistart_run with a weight per matrix and job in the data term (mcl_multistart_run_weighted): `slab_weights` is a host
+    float64 array [n_jobs, I], finite and >= 0 with a positive entry in every row; the state rows of a matrix of weight 0 must
+    be zeros on entry (matcouply_hip.h) and come back as zeros -> (diag, n_iter, stop) as multistart_run."""
+    lib = load_library()
+    w = np.ascontiguousarray(slab_weights, dtype=np.float64)
+    if w.ndim != 2 or w.shape != (int(state.shape[0]), len(row_ptr) - 1):
+        raise EngineError(f"slab_weights must be [n_jobs = {int(state.shape[0])}, I = {len(row_ptr) - 1}], not {list(w.shape)}")
+    wp = ctypes.c_void_p(w.ctypes.data)
+
+    def run(X_, xt, rp, I, K, r, opt, S, *tail):
+        return lib.mcl_multistart_run_weighted(X_, xt, rp, I, K, r, opt, S, wp, *tail)
+
+    return _multistart_launch(X, row_ptr, rank, options, None, state, lib.mcl_multistart_weighted_workspace_bytes, run)
 
 
 class NativeReg:

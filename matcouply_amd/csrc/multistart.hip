@@ -22,6 +22,9 @@
 // layout, matcouply_hip.h) and a slice of the scratch workspace (right-hand sides, inverses, X C, ...), all fp64.  At the sizes
 // this serves, the slices stay in L2 / MALL.
 //
+// cmf_aoadmm_resample (resampling.py): k_multistart_weighted is the same fit with a weight per matrix and
+// job in the data term (mcl_multistart_run_weighted) - bootstrap, jackknife and K-fold jobs over the matrices share the one X.
+//
 // cmf_aoadmm_grid: the same launch with options of its own for every workgroup (mcl_multistart_run_grid).  The workgroup copies
 // jobs[blockIdx.x] over the options of its LDS copy of the arguments, which is where every helper reads them; the jobs share X
 // and one state layout (ms_check_grid), everything else - strengths, tolerances, iteration limits - is per job.
@@ -92,13 +95,19 @@ static __device__ inline double prox_value(const mcl_multistart_penalty &p, doub
     return y;
 }
 
-template <int R, class XL>
+// WEIGHTED: the job minimises the loss with the data term sum_i w_i |X_i - B_i D_i C^T|^2 / sum_i w_i |X_i|^2 (resampling over
+// the matrices): every per-matrix Gram and right-hand side is multiplied by w_i, a matrix of weight 0 is
+// not in the job (its rows of A, B and of every aux and dual are zeros on entry and stay exact zeros).  A weight multiplies ONE
+// factor of a product and never a product that feeds an add, so that the contraction into fused multiply-adds is the
+// unweighted kernel's and a weight of 1.0 changes no bit.  Without WEIGHTED `w` is never read.
+template <int R, class XL, bool WEIGHTED>
 struct Start {
     const MsArgs &a;
     const typename XL::T *X;
     const int64_t *rp;
     const int32_t *slab;
     int64_t I, N, K;
+    const double *w;  // WEIGHTED: the job's weight per slab [I]
     double *A, *B, *C, *ws;
     MsScratch sc;
     double *red, *sys, *sh;  // LDS: reduction scratch, system batch, small shared values
@@ -110,6 +119,34 @@ struct Start {
     __device__ __forceinline__ double *dual(int m, int k) const { return A + a.off_dual[m][k]; }
     __device__ __forceinline__ double *delta(int m, int k) const { return A + a.off_delta[m][k]; }
     __device__ __forceinline__ double x(int64_t j, int64_t c) const { return (double)XL::ld1(X + j * K + c); }
+    // the weight of slab i (1 without WEIGHTED, folded away), and whether the slab is in the job
+    __device__ __forceinline__ double wt(int64_t i) const {
+        if constexpr (WEIGHTED) return w[i];
+        return 1.0;
+    }
+    __device__ __forceinline__ bool in_job(int64_t i) const {
+        if constexpr (WEIGHTED) return w[i] != 0.0;
+        return true;
+    }
+    // the maximum of rho over the slabs of the job into every slab of the job (constant feasibility penalty); 0 outside it
+    __device__ __forceinline__ void constant_rho(double *rho) {
+        const int t = threadIdx.x;
+        if (t == 0) {
+            double mx = rho[0];
+            if constexpr (WEIGHTED) {
+                bool any = false;
+                for (int64_t i = 0; i < I; ++i)
+                    if (in_job(i)) mx = any ? fmax(mx, rho[i]) : rho[i], any = true;
+            } else {
+                for (int64_t i = 1; i < I; ++i) mx = fmax(mx, rho[i]);
+            }
+            sh[2 * R * R] = mx;
+        }
+        __syncthreads();
+        const double mx = sh[2 * R * R];
+        for (int64_t i = t; i < I; i += MS_THREADS) rho[i] = in_job(i) ? mx : 0.0;
+        __syncthreads();
+    }
 
     // aux of penalty k of mode m as a packed matrix, element (j, l): P Delta for PARAFAC2 (Delta copied to sh_delta first)
     __device__ __forceinline__ double auxp(int m, int k, int64_t j, int l, const double *dl) const {
@@ -122,7 +159,7 @@ struct Start {
         return aux(m, k)[j * R + l];
     }
 
-    // invert n systems: build(i, S) writes system i into S (one thread), the inverse goes to out + i R R
+    // invert the systems of the n = I slabs: build(i, S) writes system i into S (one thread), the inverse goes to out + i R R
     template <class Build>
     __device__ __forceinline__ void invert_systems(int64_t n, double *out, Build build) {
         const int t = threadIdx.x;
@@ -130,9 +167,13 @@ struct Start {
             const int64_t i = base + t;
             if (t < nb && i < n) {
                 double *S = sys + t * 2 * R * R, *W = S + R * R;
-                build(i, S);
-                spd_inverse<R>(S, W);
-                for (int e = 0; e < R * R; ++e) out[i * R * R + e] = S[e];
+                if (in_job(i)) {
+                    build(i, S);
+                    spd_inverse<R>(S, W);
+                    for (int e = 0; e < R * R; ++e) out[i * R * R + e] = S[e];
+                } else {  // not (0 + l2) I inverted: the slab's rows stay zeros
+                    for (int e = 0; e < R * R; ++e) out[i * R * R + e] = 0.0;
+                }
             }
         }
         __syncthreads();
@@ -154,9 +195,16 @@ struct Start {
             if (m == 0) return rho_rows_slab[j];
             return rho_scalar;
         };
+        // a row of a slab outside the job keeps its zeros: no prox, no dual step (a Box with a positive lower bound would move it)
+        auto live = [&](int64_t j) {
+            if (m == 1) return in_job(slab[j]);
+            if (m == 0) return in_job(j);
+            return true;
+        };
         if (p.kind == MCL_PEN_NN || p.kind == MCL_PEN_BOX || p.kind == MCL_PEN_L1) {
             for (int64_t e = t; e < rows * R; e += MS_THREADS) {
                 const int64_t j = e / R;
+                if (!live(j)) continue;
                 const double f = Fm[e], u = U[e];
                 const double z = prox_value(p, f + u, rho_of(j));
                 Z[e] = z;
@@ -187,6 +235,7 @@ struct Start {
             for (int64_t e = t; e < rows * R; e += MS_THREADS) {
                 const int64_t j = e / R;
                 const int l = (int)(e % R);
+                if (!live(j)) continue;
                 const double nrm = sqrt(m == 1 ? cs[slab[j] * R + l] : cs[l]);
                 const double z = Z[e] * p.p0 / fmax(nrm, p.p0);
                 Z[e] = z;
@@ -318,41 +367,40 @@ struct Start {
         const int n = a.o.n_regs[1];
         double *cc = ws + sc.small, *rhs = ws + sc.rhsB, *Linv = ws + sc.LinvB, *rho = ws + sc.rhoB;
         ctc(cc);
-        for (int64_t j = t; j < N; j += MS_THREADS) {  // rhs_i = X_i (C * a_i)
+        for (int64_t j = t; j < N; j += MS_THREADS) {  // rhs_i = w_i X_i (C * a_i)
             const double *ai = A + (int64_t)slab[j] * R;
             double acc[R];
             #pragma unroll
             for (int l = 0; l < R; ++l) acc[l] = 0.0;
-            for (int64_t c = 0; c < K; ++c) {
-                const double xv = x(j, c);
-                #pragma unroll
-                for (int l = 0; l < R; ++l) acc[l] += xv * (C[c * R + l] * ai[l]);
-            }
+            if (in_job(slab[j]))  // a slab outside the job: no pass over its X
+                for (int64_t c = 0; c < K; ++c) {
+                    const double xv = x(j, c);
+                    #pragma unroll
+                    for (int l = 0; l < R; ++l) acc[l] += xv * (C[c * R + l] * ai[l]);
+                }
             #pragma unroll
-            for (int l = 0; l < R; ++l) rhs[j * R + l] = acc[l];
+            for (int l = 0; l < R; ++l) {
+                if constexpr (WEIGHTED) acc[l] *= w[slab[j]];
+                rhs[j * R + l] = acc[l];
+            }
         }
         for (int64_t i = t; i < I; i += MS_THREADS) {
             double tr = 0.0;
             for (int l = 0; l < R; ++l) tr += cc[l * R + l] * A[i * R + l] * A[i * R + l];
+            if constexpr (WEIGHTED) tr *= w[i];
             rho[i] = 0.5 * tr * a.o.feasibility_penalty_scale;
         }
         __syncthreads();
-        if (a.o.constant_B) {
-            if (t == 0) {
-                double mx = rho[0];
-                for (int64_t i = 1; i < I; ++i) mx = fmax(mx, rho[i]);
-                sh[2 * R * R] = mx;
-            }
-            __syncthreads();
-            const double mx = sh[2 * R * R];
-            for (int64_t i = t; i < I; i += MS_THREADS) rho[i] = mx;
-            __syncthreads();
-        }
+        if (a.o.constant_B) constant_rho(rho);
         invert_systems(I, Linv, [&](int64_t i, double *S) {
             const double *ai = A + i * R;
             const double shift = rho[i] * n + a.o.l2_penalty[1];
             for (int p = 0; p < R; ++p)
-                for (int q = 0; q < R; ++q) S[p * R + q] = cc[p * R + q] * ai[p] * ai[q] + (p == q ? shift : 0.0);
+                for (int q = 0; q < R; ++q) {
+                    double g = cc[p * R + q];
+                    if constexpr (WEIGHTED) g *= w[i];
+                    S[p * R + q] = g * ai[p] * ai[q] + (p == q ? shift : 0.0);
+                }
         });
         for (int it = 0; it < a.o.inner_n_iter_max; ++it) {
             // Delta of every PARAFAC2 penalty into LDS for the right-hand side
@@ -393,8 +441,18 @@ struct Start {
         const int n = a.o.n_regs[2];
         double *G = ws + sc.small + R * R, *Linv = ws + sc.small + 2 * R * R, *RC = ws + sc.RC;
         auto ba = [&](int64_t j, int l) { return B[j * R + l] * A[(int64_t)slab[j] * R + l]; };
-        rows_reduce(R * R, N, G, red, [&](int64_t j, int e) { return ba(j, e / R) * ba(j, e % R); });
-        rows_reduce((int)(K * R), N, RC, red, [&](int64_t j, int e) { return x(j, e / R) * ba(j, e % R); });
+        auto wba = [&](int64_t j, int l) {  // w_i (B_i D_i)
+            if constexpr (WEIGHTED) return w[slab[j]] * ba(j, l);
+            else return ba(j, l);
+        };
+        // G = sum_i w_i D_i B_i^T B_i D_i, RC = sum_i w_i X_i^T B_i D_i (a slab outside the job: no pass over its X)
+        rows_reduce(R * R, N, G, red, [&](int64_t j, int e) { return wba(j, e / R) * ba(j, e % R); });
+        // (the product itself is returned, not 0.0 on another path: a select between the multiply and rows_reduce's add would
+        // keep the two from being contracted as they are in the unweighted kernel)
+        rows_reduce((int)(K * R), N, RC, red, [&](int64_t j, int e) {
+            const double xv = in_job(slab[j]) ? x(j, e / R) : 0.0;
+            return xv * wba(j, e % R);
+        });
         double tr = 0.0;
         for (int l = 0; l < R; ++l) tr += G[l * R + l];
         const double rho = 0.5 * tr * a.o.feasibility_penalty_scale;
@@ -443,6 +501,7 @@ struct Start {
             const int l = (int)(e % R);
             double s = 0.0;
             for (int64_t j = rp[i]; j < rp[i + 1]; ++j) s += B[j * R + l] * XC[j * R + l];
+            if constexpr (WEIGHTED) s *= w[i];
             rhsA[e] = s;
         }
         for (int64_t e = t; e < I * R * R; e += MS_THREADS) {
@@ -450,6 +509,7 @@ struct Start {
             const int ab = (int)(e % (R * R)), p = ab / R, q = ab % R;
             double s = 0.0;
             for (int64_t j = rp[i]; j < rp[i + 1]; ++j) s += B[j * R + p] * B[j * R + q];
+            if constexpr (WEIGHTED) s *= w[i];
             Q[e] = s * cc[ab];
         }
         __syncthreads();
@@ -459,17 +519,7 @@ struct Start {
             rho[i] = 0.5 * tr * a.o.feasibility_penalty_scale;
         }
         __syncthreads();
-        if (a.o.constant_A) {
-            if (t == 0) {
-                double mx = rho[0];
-                for (int64_t i = 1; i < I; ++i) mx = fmax(mx, rho[i]);
-                sh[2 * R * R] = mx;
-            }
-            __syncthreads();
-            const double mx = sh[2 * R * R];
-            for (int64_t i = t; i < I; i += MS_THREADS) rho[i] = mx;
-            __syncthreads();
-        }
+        if (a.o.constant_A) constant_rho(rho);
         invert_systems(I, Linv, [&](int64_t i, double *S) {
             const double shift = rho[i] * n + a.o.l2_penalty[0];
             for (int e = 0; e < R * R; ++e) S[e] = Q[i * R * R + e] + ((e / R == e % R) ? shift : 0.0);
@@ -506,18 +556,20 @@ struct Start {
             double acc[R];
             #pragma unroll
             for (int l = 0; l < R; ++l) acc[l] = 0.0;
-            for (int64_t c = 0; c < K; ++c) {
-                const double xv = x(j, c);
-                #pragma unroll
-                for (int l = 0; l < R; ++l) acc[l] += xv * C[c * R + l];
-            }
+            if (in_job(slab[j]))  // a slab outside the job: zeros, no pass over its X
+                for (int64_t c = 0; c < K; ++c) {
+                    const double xv = x(j, c);
+                    #pragma unroll
+                    for (int l = 0; l < R; ++l) acc[l] += xv * C[c * R + l];
+                }
             #pragma unroll
             for (int l = 0; l < R; ++l) XC[j * R + l] = acc[l];
         }
         __syncthreads();
     }
 
-    // (<X, model>, ||model||^2): from the A phase's rhs and Q (decomposition.py:445-449), or with a pass over X (:430-444)
+    // (<X, model>, ||model||^2): from the A phase's rhs and Q (decomposition.py:445-449), or with a pass over X (:430-444).
+    // WEIGHTED: sum_i w_i <X_i, model_i> and sum_i w_i ||model_i||^2 (rhs_A and Q carry w_i already)
     __device__ __forceinline__ void model_terms(bool from_A, double *inner, double *model) {
         const int t = threadIdx.x;
         double *Q = ws + sc.Q, *rhsA = ws + sc.rhsA;
@@ -544,7 +596,11 @@ struct Start {
         double s = 0.0;
         for (int64_t j = t; j < N; j += MS_THREADS) {
             const double *ai = A + (int64_t)slab[j] * R;
-            for (int l = 0; l < R; ++l) s += XC[j * R + l] * (B[j * R + l] * ai[l]);
+            for (int l = 0; l < R; ++l) {
+                double b = B[j * R + l] * ai[l];
+                if constexpr (WEIGHTED) b *= w[slab[j]];
+                s += XC[j * R + l] * b;
+            }
         }
         double m = 0.0;
         for (int64_t e = t; e < I * R * R; e += MS_THREADS) {
@@ -552,6 +608,7 @@ struct Start {
             const int ab = (int)(e % (R * R)), p = ab / R, q = ab % R;
             double g = 0.0;
             for (int64_t j = rp[i]; j < rp[i + 1]; ++j) g += (B[j * R + p] * A[i * R + p]) * (B[j * R + q] * A[i * R + q]);
+            if constexpr (WEIGHTED) g *= w[i];
             m += g * cc[ab];
         }
         *inner = wg_sum(s, red);
@@ -589,68 +646,94 @@ struct Start {
         }
         return feasible ? 1 : 0;
     }
+
+    // the whole fit of job s: the body of k_multistart and of k_multistart_weighted
+    __device__ __forceinline__ void fit(int64_t s) {
+        double *diag = a.diag + s * a.diag_stride;
+        const int t = threadIdx.x;
+
+        // ||X||^2 (every start: the same order, the same bits); WEIGHTED: sum_i w_i ||X_i||^2, in that order too
+        double xs = 0.0;
+        for (int64_t e = t; e < a.N * a.K; e += MS_THREADS) {
+            if constexpr (WEIGHTED) {
+                const double wi = w[slab[e / a.K]];
+                if (wi != 0.0) {
+                    const double v = (double)XL::ld1(X + e);
+                    xs += (wi * v) * v;
+                }
+            } else {
+                const double v = (double)XL::ld1(X + e);
+                xs += v * v;
+            }
+        }
+        const double x_sq = wg_sum(xs, red);
+
+        int f0 = diagnostics(false, x_sq, diag);
+        if (t == 0) diag[2] = (double)(f0 | 2);
+        __syncthreads();
+        const mcl_multistart_options &o = a.o;
+        const bool active = o.tol > 0.0 || o.absolute_tol > 0.0;
+        double prev = diag[1];
+        int it = 0, code = 0;
+        for (; it < o.n_iter_max && !code; ++it) {
+            if (o.update_B) phase_B();
+            if (o.update_C) phase_C();
+            if (o.update_A) phase_A();
+            double *row = diag + (int64_t)(it + 1) * MCL_MS_DIAG;
+            const int feasible = diagnostics(o.update_A != 0, x_sq, row);
+            __syncthreads();
+            const double loss = row[1];
+            const bool evaluated = !active || feasible || o.evaluate_loss_always;
+            if (active && evaluated && o.tol > 0.0 && feasible) {
+                if (fabs(prev - loss) < o.tol * prev) code = MCL_STOP_RELATIVE;
+                else if (loss < o.absolute_tol) code = MCL_STOP_ABSOLUTE;
+            }
+            if (evaluated) prev = loss;
+            __syncthreads();
+            if (t == 0) row[2] = (double)(feasible | (evaluated ? 2 : 0));
+        }
+        if (t == 0) a.n_iter[s] = it, a.stop[s] = code;
+    }
 };
+
+// The LDS, the arguments' LDS copy and the start object are declared in the kernels themselves, not in a function the two share:
+// where they are declared moves the register allocation of the unweighted instantiations (DESIGN.md sections 17 and 18).
+#define MS_START(WEIGHTED, WPTR)                                                                                              \
+    __shared__ double red[MS_THREADS];                                                                                        \
+    __shared__ double sys[MS_SYS_BYTES / 8];                                                                                  \
+    __shared__ double sh[4 * R * R + 16 + MCL_MAX_REGS * R * R];                                                              \
+    __shared__ MsArgs sa; /* the arguments in LDS: the helpers keep a reference to them (no private copy of the kernarg) */  \
+    if (threadIdx.x == 0) sa = a0;                                                                                            \
+    __syncthreads();                                                                                                          \
+    const int64_t s = blockIdx.x;                                                                                             \
+    if (a0.jobs) { /* a grid: this workgroup's own options replace the shared ones (uniform branch: a0 is the kernarg) */    \
+        const int32_t *src = reinterpret_cast<const int32_t *>(a0.jobs + s);                                                  \
+        int32_t *dst = reinterpret_cast<int32_t *>(&sa.o);                                                                    \
+        for (int e = threadIdx.x; e < (int)(sizeof(mcl_multistart_options) / sizeof(int32_t)); e += MS_THREADS) dst[e] = src[e]; \
+        __syncthreads();                                                                                                      \
+    }                                                                                                                         \
+    const MsArgs &a = sa;                                                                                                     \
+    Start<R, XL, WEIGHTED> st{a, static_cast<const typename XL::T *>(a.X), a.row_ptr, a.slab_of_row, a.I, a.N, a.K, WPTR};    \
+    st.A = a.state + s * a.state_len;                                                                                         \
+    st.B = st.A + a.I * R;                                                                                                    \
+    st.C = st.B + a.N * R;                                                                                                    \
+    st.ws = a.scratch + s * a.scratch_len;                                                                                    \
+    st.sc = ms_scratch(a.I, a.N, a.K, R);                                                                                     \
+    st.red = red, st.sys = sys, st.sh = sh;                                                                                   \
+    st.nb = std::min(MS_THREADS, MS_SYS_BYTES / (2 * R * R * 8));                                                             \
+    st.fit(s);
 
 template <int R, class XL>
 __global__ __launch_bounds__(MS_THREADS) void k_multistart(MsArgs a0) {
-    __shared__ double red[MS_THREADS];
-    __shared__ double sys[MS_SYS_BYTES / 8];
-    __shared__ double sh[4 * R * R + 16 + MCL_MAX_REGS * R * R];
-    __shared__ MsArgs sa;  // the arguments in LDS: the helpers keep a reference to them (no private copy of the kernarg)
-    if (threadIdx.x == 0) sa = a0;
-    __syncthreads();
-    const int64_t s = blockIdx.x;
-    if (a0.jobs) {  // a grid: this workgroup's own options replace the shared ones (uniform branch: a0 is the kernarg)
-        const int32_t *src = reinterpret_cast<const int32_t *>(a0.jobs + s);
-        int32_t *dst = reinterpret_cast<int32_t *>(&sa.o);
-        for (int e = threadIdx.x; e < (int)(sizeof(mcl_multistart_options) / sizeof(int32_t)); e += MS_THREADS) dst[e] = src[e];
-        __syncthreads();
-    }
-    const MsArgs &a = sa;
-    Start<R, XL> st{a, static_cast<const typename XL::T *>(a.X), a.row_ptr, a.slab_of_row, a.I, a.N, a.K};
-    st.A = a.state + s * a.state_len;
-    st.B = st.A + a.I * R;
-    st.C = st.B + a.N * R;
-    st.ws = a.scratch + s * a.scratch_len;
-    st.sc = ms_scratch(a.I, a.N, a.K, R);
-    st.red = red, st.sys = sys, st.sh = sh;
-    st.nb = std::min(MS_THREADS, MS_SYS_BYTES / (2 * R * R * 8));
-    double *diag = a.diag + s * a.diag_stride;
-    const int t = threadIdx.x;
-
-    double xs = 0.0;  // ||X||^2 (every start: the same order, the same bits)
-    for (int64_t e = t; e < a.N * a.K; e += MS_THREADS) {
-        const double v = (double)XL::ld1(st.X + e);
-        xs += v * v;
-    }
-    const double x_sq = wg_sum(xs, red);
-
-    int f0 = st.diagnostics(false, x_sq, diag);
-    if (t == 0) diag[2] = (double)(f0 | 2);
-    __syncthreads();
-    const mcl_multistart_options &o = a.o;
-    const bool active = o.tol > 0.0 || o.absolute_tol > 0.0;
-    double prev = diag[1];
-    int it = 0, code = 0;
-    for (; it < o.n_iter_max && !code; ++it) {
-        if (o.update_B) st.phase_B();
-        if (o.update_C) st.phase_C();
-        if (o.update_A) st.phase_A();
-        double *row = diag + (int64_t)(it + 1) * MCL_MS_DIAG;
-        const int feasible = st.diagnostics(o.update_A != 0, x_sq, row);
-        __syncthreads();
-        const double loss = row[1];
-        const bool evaluated = !active || feasible || o.evaluate_loss_always;
-        if (active && evaluated && o.tol > 0.0 && feasible) {
-            if (fabs(prev - loss) < o.tol * prev) code = MCL_STOP_RELATIVE;
-            else if (loss < o.absolute_tol) code = MCL_STOP_ABSOLUTE;
-        }
-        if (evaluated) prev = loss;
-        __syncthreads();
-        if (t == 0) row[2] = (double)(feasible | (evaluated ? 2 : 0));
-    }
-    if (t == 0) a.n_iter[s] = it, a.stop[s] = code;
+    MS_START(false, nullptr)
 }
+
+// job blockIdx.x under its own row of slab_weight [n_jobs, I] (fp64, device)
+template <int R, class XL>
+__global__ __launch_bounds__(MS_THREADS) void k_multistart_weighted(MsArgs a0, const double *slab_weight) {
+    MS_START(true, slab_weight + (int64_t)blockIdx.x * a0.I)
+}
+#undef MS_START
 
 struct MsPlan {
     int64_t N, state_len, scratch_len, off_rowptr, off_slab, off_scratch, total;
@@ -713,15 +796,16 @@ MsPlan ms_plan(const int64_t *row_ptr, int64_t I, int64_t K, int rank, const mcl
 }
 
 template <class XL, int R>
-void launch(const MsArgs &a, int n_starts, hipStream_t s) {
-    hipLaunchKernelGGL((k_multistart<R, XL>), dim3(n_starts), dim3(MS_THREADS), 0, s, a);
+void launch(const MsArgs &a, int n_starts, const double *slab_weight, hipStream_t s) {
+    if (slab_weight) hipLaunchKernelGGL((k_multistart_weighted<R, XL>), dim3(n_starts), dim3(MS_THREADS), 0, s, a, slab_weight);
+    else hipLaunchKernelGGL((k_multistart<R, XL>), dim3(n_starts), dim3(MS_THREADS), 0, s, a);
 }
 
 template <class XL>
-void launch_rank(int rank, const MsArgs &a, int n_starts, hipStream_t s) {
+void launch_rank(int rank, const MsArgs &a, int n_starts, const double *slab_weight, hipStream_t s) {
     switch (rank) {
 #define MS_CASE(R) \
-    case R: launch<XL, R>(a, n_starts, s); break;
+    case R: launch<XL, R>(a, n_starts, slab_weight, s); break;
         MS_CASE(1) MS_CASE(2) MS_CASE(3) MS_CASE(4) MS_CASE(5) MS_CASE(6) MS_CASE(7) MS_CASE(8)
         MS_CASE(9) MS_CASE(10) MS_CASE(11) MS_CASE(12) MS_CASE(13) MS_CASE(14) MS_CASE(15) MS_CASE(16)
 #undef MS_CASE
@@ -753,24 +837,47 @@ std::string ms_check_grid(const int64_t *row_ptr, int64_t I, int64_t K, int32_t 
     return "";
 }
 
-// mcl_multistart_run (per_job false: *opt for every workgroup, passed in the kernarg) and mcl_multistart_run_grid (per_job true:
-// opt[s] for workgroup s, uploaded to the workspace)
+// the weights of mcl_multistart_run_weighted in the workspace, behind the plan of mcl_multistart_run
+int64_t ms_weights_bytes(int32_t n_jobs, int64_t I) { return (int64_t(n_jobs) * I * 8 + 255) & ~int64_t(255); }
+
+// slab_weights [n_jobs, I] on the host: finite, >= 0, a positive one in every job
+std::string ms_check_weights(const double *w, int32_t n_jobs, int64_t I) {
+    if (!w) return "NULL slab_weights";
+    for (int32_t s = 0; s < n_jobs; ++s) {
+        bool any = false;
+        for (int64_t i = 0; i < I; ++i) {
+            const double v = w[int64_t(s) * I + i];
+            if (!std::isfinite(v) || v < 0.0)
+                return "slab_weights[" + std::to_string(s) + "][" + std::to_string(i) + "] is negative or not finite";
+            any = any || v > 0.0;
+        }
+        if (!any) return "job " + std::to_string(s) + " has no positive weight";
+    }
+    return "";
+}
+
+// mcl_multistart_run (per_job false: *opt for every workgroup, passed in the kernarg), mcl_multistart_run_grid (per_job true:
+// opt[s] for workgroup s, uploaded to the workspace) and mcl_multistart_run_weighted (weighted true: *opt for every workgroup
+// and the host array slab_weights [n_starts, I], uploaded to the workspace)
 int ms_run(const char *who, const void *X, int32_t x_type, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank,
-           const mcl_multistart_options *opt, int32_t n_starts, bool per_job, double *state, double *diag, int32_t *n_iter,
-           int32_t *stop, void *workspace, int64_t workspace_bytes, void *hip_stream) {
+           const mcl_multistart_options *opt, int32_t n_starts, bool per_job, bool weighted, const double *slab_weights,
+           double *state, double *diag, int32_t *n_iter, int32_t *stop, void *workspace, int64_t workspace_bytes, void *hip_stream) {
     auto fail = [who](const std::string &m) {
         g_ms_error = who + m;
         return 1;
     };
-    const std::string bad = per_job ? ms_check_grid(row_ptr, I, K, rank, opt, n_starts) : ms_check(row_ptr, I, K, rank, opt, n_starts);
+    std::string bad = per_job ? ms_check_grid(row_ptr, I, K, rank, opt, n_starts) : ms_check(row_ptr, I, K, rank, opt, n_starts);
+    if (bad.empty() && weighted) bad = ms_check_weights(slab_weights, n_starts, I);
     if (!bad.empty()) return fail(bad);
     if (!X || !state || !diag || !n_iter || !stop || !workspace) return fail("NULL argument");
     if (x_type != MCL_X_F32 && x_type != MCL_X_BF16 && x_type != MCL_X_F16)
         return fail("unknown x_type " + std::to_string(x_type) + " (MCL_X_F32 = 0, MCL_X_BF16 = 1, MCL_X_F16 = 2)");
     const MsPlan p = ms_plan(row_ptr, I, K, rank, opt, n_starts);
-    const int64_t jobs_bytes = per_job ? ms_jobs_bytes(n_starts) : 0;
+    const int64_t jobs_bytes = per_job ? ms_jobs_bytes(n_starts) : (weighted ? ms_weights_bytes(n_starts, I) : 0);
     if (workspace_bytes < p.total + jobs_bytes)
-        return fail(per_job ? "workspace too small (mcl_multistart_grid_workspace_bytes)" : "workspace too small (mcl_multistart_workspace_bytes)");
+        return fail(per_job    ? "workspace too small (mcl_multistart_grid_workspace_bytes)"
+                    : weighted ? "workspace too small (mcl_multistart_weighted_workspace_bytes)"
+                               : "workspace too small (mcl_multistart_workspace_bytes)");
     if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail("workspace must be 256-byte aligned");
     hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
     char *ws = static_cast<char *>(workspace);
@@ -781,8 +888,10 @@ int ms_run(const char *who, const void *X, int32_t x_type, const int64_t *row_pt
         (p.N && hipMemcpyAsync(ws + p.off_slab, slab.data(), p.N * 4, hipMemcpyHostToDevice, s) != hipSuccess) ||
         (per_job && hipMemcpyAsync(ws + p.total, opt, int64_t(n_starts) * sizeof(mcl_multistart_options), hipMemcpyHostToDevice, s) !=
                         hipSuccess) ||
+        (weighted && hipMemcpyAsync(ws + p.total, slab_weights, int64_t(n_starts) * I * 8, hipMemcpyHostToDevice, s) != hipSuccess) ||
         hipStreamSynchronize(s) != hipSuccess)
-        return fail(per_job ? "upload of row_ptr and the options failed" : "upload of row_ptr failed");
+        return fail(per_job ? "upload of row_ptr and the options failed"
+                            : (weighted ? "upload of row_ptr and the weights failed" : "upload of row_ptr failed"));
     int32_t n_iter_most = opt->n_iter_max;  // the diagnostics stride: that of the longest job
     for (int32_t j = 1; per_job && j < n_starts; ++j) n_iter_most = std::max(n_iter_most, opt[j].n_iter_max);
     MsArgs a{};
@@ -801,7 +910,7 @@ int ms_run(const char *who, const void *X, int32_t x_type, const int64_t *row_pt
     a.jobs = per_job ? reinterpret_cast<const mcl_multistart_options *>(ws + p.total) : nullptr;
     mcl_x_dispatch(x_type, [&](auto xl) {
         using XL = decltype(xl);
-        launch_rank<XL>(rank, a, n_starts, s);
+        launch_rank<XL>(rank, a, n_starts, weighted ? reinterpret_cast<const double *>(ws + p.total) : nullptr, s);
         return 0;
     });
     const hipError_t e = hipGetLastError();
@@ -824,8 +933,8 @@ int64_t mcl_multistart_workspace_bytes(const int64_t *row_ptr, int64_t I, int64_
 int mcl_multistart_run(const void *X, int32_t x_type, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank,
                        const mcl_multistart_options *opt, int32_t n_starts, double *state, double *diag, int32_t *n_iter, int32_t *stop,
                        void *workspace, int64_t workspace_bytes, void *hip_stream) {
-    return ms_run("mcl_multistart_run: ", X, x_type, row_ptr, I, K, rank, opt, n_starts, false, state, diag, n_iter, stop, workspace,
-                  workspace_bytes, hip_stream);
+    return ms_run("mcl_multistart_run: ", X, x_type, row_ptr, I, K, rank, opt, n_starts, false, false, nullptr, state, diag, n_iter,
+                  stop, workspace, workspace_bytes, hip_stream);
 }
 
 int64_t mcl_multistart_grid_workspace_bytes(const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank,
@@ -837,8 +946,22 @@ int64_t mcl_multistart_grid_workspace_bytes(const int64_t *row_ptr, int64_t I, i
 int mcl_multistart_run_grid(const void *X, int32_t x_type, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank,
                             const mcl_multistart_options *options, int32_t n_jobs, double *state, double *diag, int32_t *n_iter,
                             int32_t *stop, void *workspace, int64_t workspace_bytes, void *hip_stream) {
-    return ms_run("mcl_multistart_run_grid: ", X, x_type, row_ptr, I, K, rank, options, n_jobs, true, state, diag, n_iter, stop,
-                  workspace, workspace_bytes, hip_stream);
+    return ms_run("mcl_multistart_run_grid: ", X, x_type, row_ptr, I, K, rank, options, n_jobs, true, false, nullptr, state, diag,
+                  n_iter, stop, workspace, workspace_bytes, hip_stream);
+}
+
+int64_t mcl_multistart_weighted_workspace_bytes(const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank,
+                                                const mcl_multistart_options *opt, int32_t n_jobs) {
+    if (!ms_check(row_ptr, I, K, rank, opt, n_jobs).empty()) return -1;
+    return ms_plan(row_ptr, I, K, rank, opt, n_jobs).total + ms_weights_bytes(n_jobs, I);
+}
+
+int mcl_multistart_run_weighted(const void *X, int32_t x_type, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank,
+                                const mcl_multistart_options *opt, int32_t n_jobs, const double *slab_weights, double *state,
+                                double *diag, int32_t *n_iter, int32_t *stop, void *workspace, int64_t workspace_bytes,
+                                void *hip_stream) {
+    return ms_run("mcl_multistart_run_weighted: ", X, x_type, row_ptr, I, K, rank, opt, n_jobs, false, true, slab_weights, state,
+                  diag, n_iter, stop, workspace, workspace_bytes, hip_stream);
 }
 
 }  // extern "C"

@@ -1921,11 +1921,30 @@ def _multistart_options(kw, descs):
     return o
 
 
-def _multistart_fused(matrices, rank, random_states, kws, per_job_options=False):
+def _zero_weight_mask(row_ptr, K, rank, kinds, w):
+    """which doubles of a job's state slice (the layout of mcl_multistart_run) belong to a matrix of weight 0: its row of A, its
+    B_i and its rows of every aux and dual of modes 0 and 1 (its P_i for PARAFAC2; Delta and mode 2 are the whole job's)"""
+    I, N = len(row_ptr) - 1, int(row_ptr[-1])
+    dead_A = np.repeat(np.asarray(w) == 0, rank)
+    dead_B = np.repeat(np.repeat(np.asarray(w) == 0, np.diff(row_ptr)), rank)
+    dead = {0: dead_A, 1: dead_B, 2: np.zeros(K * rank, dtype=bool)}
+    parts = [dead_A, dead_B, dead[2]]
+    for mode in range(3):
+        for kind in kinds[mode]:
+            parts.append(dead[mode])
+            if kind == _engine.PEN_PARAFAC2:
+                parts.append(np.zeros(rank * rank, dtype=bool))
+            parts.append(dead[mode])
+    return np.concatenate(parts)
+
+
+def _multistart_fused(matrices, rank, random_states, kws, per_job_options=False, slab_weights=None):
     """every keyword set of `kws` (complete cmf_aoadmm keywords with one state layout) from every start, in one launch: job
     g * len(random_states) + s is kws[g] from random_states[s].  One set with per_job_options False is cmf_aoadmm_multistart
     (mcl_multistart_run, the options in the kernel's arguments); cmf_aoadmm_grid gives every job options of its own
-    (mcl_multistart_run_grid).  `kws` and `random_states` are not empty."""
+    (mcl_multistart_run_grid).  `kws` and `random_states` are not empty.  `slab_weights` [len(random_states), I] (one keyword
+    set): cmf_aoadmm_resample, job s fits under slab_weights[s] (mcl_multistart_run_weighted); the start is the full problem's
+    draw with the part of every zero-weight matrix set to zero afterwards."""
     device = _device()
     X, row_ptr = _pack(matrices, device)
     I, N, K = len(row_ptr) - 1, int(row_ptr[-1]), int(X.shape[1])
@@ -1952,8 +1971,14 @@ def _multistart_fused(matrices, rank, random_states, kws, per_job_options=False)
     L = _engine.multistart_state_len(I, N, K, rank, kinds)
     assert all(v.size == L for v in vectors), "multistart: state layout mismatch"
 
+    if slab_weights is not None:
+        assert len(kws) == 1 and not per_job_options and len(slab_weights) == len(vectors)
+        for v, w in zip(vectors, slab_weights):
+            v[_zero_weight_mask(row_ptr, K, rank, kinds, w)] = 0.0
     state = torch.from_numpy(np.stack(vectors)).to(device)
-    if per_job_options:
+    if slab_weights is not None:
+        diag, n_iter, stop = _engine.multistart_run_weighted(X, row_ptr, rank, job_options[0], slab_weights, state)
+    elif per_job_options:
         diag, n_iter, stop = _engine.multistart_run_grid(X, row_ptr, rank, job_options, state)
     else:
         assert len(kws) == 1
