@@ -25,6 +25,8 @@ Fixture families:
   G6  readme_example.npz   the call of the reference's README (README.rst:66-91: non_negative, L1 on C, L2 balls on
                           A and B_i, PARAFAC2, unimodality, constant feasibility penalty, random_state=0), 10 iterations
                           (`--only readme`)
+  G8  unimodal_edges.npz   unimodal_regression on the designed columns of tests/unimodal_cases.py (stack depths, ties, length
+                          edges), with and without non-negativity (`--only unimodal_edges`)
 
 Penalties are described by neutral JSON descriptors ({"kind": "l1", "reg_strength": 0.1, ...}) so
 that the fixtures do not depend on any class of the reference or of the product.
@@ -593,8 +595,28 @@ def gen_converters_inits():
     print("converters_inits:", len(arrays), "arrays")
 
 
+# ----------------------------------------------------------------------------------------------
+# G8: the designed columns of the unimodal kernel tests
+# ----------------------------------------------------------------------------------------------
+def gen_unimodal_edges():
+    """the reference's unimodal_regression on every designed column of tests/unimodal_cases.py, both non_negativity values:
+    y (the columns, concatenated), ptr (their extents), out, out_nn"""
+    sys.path.insert(0, REPO)
+    from tests import unimodal_cases as uc
+
+    cols = list(uc.all_columns().values())
+    ptr = np.concatenate([[0], np.cumsum([len(y) for y in cols])]).astype(np.int64)
+    out = np.concatenate([np.asarray(ref_unimodal(np.array(y), non_negativity=False), dtype=np.float64) for y in cols])
+    out_nn = np.concatenate([np.asarray(ref_unimodal(np.array(y), non_negativity=True), dtype=np.float64) for y in cols])
+    np.savez_compressed(os.path.join(OUT, "unimodal_edges.npz"), y=np.concatenate(cols), ptr=ptr, out=out, out_nn=out_nn)
+    print("unimodal_edges:", len(cols), "columns,", int(ptr[-1]), "elements")
+
+
 if __name__ == "__main__":
     print("reference version", matcouply.__version__)
+    if "--only" in sys.argv and sys.argv[sys.argv.index("--only") + 1] == "unimodal_edges":
+        gen_unimodal_edges()
+        sys.exit(0)
     if "--only" in sys.argv and sys.argv[sys.argv.index("--only") + 1] == "converters":
         gen_converters_inits()
         sys.exit(0)
@@ -611,5 +633,6 @@ if __name__ == "__main__":
     gen_more_penalties()
     gen_readme()
     gen_converters_inits()
+    gen_unimodal_edges()
     total = sum(os.path.getsize(os.path.join(OUT, f)) for f in os.listdir(OUT))
     print(f"total fixture bytes: {total}")

@@ -78,3 +78,26 @@ def engine_from_oracle_state(st, device="cuda:0"):
 
 def to_np(t):
     return t.detach().cpu().numpy().astype(np.float64)
+
+
+# ---- buffers with sentinel rows around the view a kernel may write (the prox-kernel tests) -------------------------------------------
+PAD_ROWS, SENTINEL = 3, -7.5
+
+
+def padded(values, unaligned, dev):
+    """-> (buffer, view): `values` [N, r] in a buffer PAD_ROWS rows longer, filled with SENTINEL; unaligned: the view starts one
+    float into the buffer"""
+    import torch
+
+    N, r = values.shape
+    buf = torch.full(((N + PAD_ROWS) * r + 1,), SENTINEL, dtype=torch.float32, device=dev)
+    off = 1 if unaligned else 0
+    view = buf[off: off + N * r].view(N, r)
+    view.copy_(torch.tensor(np.ascontiguousarray(values), dtype=torch.float32, device=dev))
+    assert view.is_contiguous() and view.data_ptr() % 16 == (4 if unaligned else 0)
+    return buf, view
+
+
+def untouched_outside(buf, view):
+    off = (view.data_ptr() - buf.data_ptr()) // 4
+    return bool((buf[:off] == SENTINEL).all()) and bool((buf[off + view.numel():] == SENTINEL).all())

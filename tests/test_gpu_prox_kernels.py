@@ -34,11 +34,11 @@ import numpy as np
 import pytest
 
 from tests import prox_cases as pc
+from tests.helpers import padded as _padded, untouched_outside as _untouched_outside
 
 pytestmark = pytest.mark.gpu
 
 BAR_AUX, BAR_DUAL, HALF_ULP = 2.4e-7, 1e-6, 2.0 ** -24
-PAD_ROWS, SENTINEL = 3, -7.5
 FP32_SUM = ("tv", "l2ball", "nn", "box", "l1")  # kinds whose fast kernel forms Y = F + U in fp32 (simplex, GL2: in fp64)
 
 
@@ -50,25 +50,6 @@ def _f32(a, dev):
 
 def _np64(t):
     return t.detach().cpu().numpy().astype(np.float64)
-
-
-def _padded(values, unaligned, dev):
-    """-> (buffer, view): `values` [N, r] in a buffer PAD_ROWS rows longer, filled with SENTINEL; unaligned: the view starts one
-    float into the buffer"""
-    import torch
-
-    N, r = values.shape
-    buf = torch.full(((N + PAD_ROWS) * r + 1,), SENTINEL, dtype=torch.float32, device=dev)
-    off = 1 if unaligned else 0
-    view = buf[off: off + N * r].view(N, r)
-    view.copy_(_f32(values, dev))
-    assert view.is_contiguous() and view.data_ptr() % 16 == (4 if unaligned else 0)
-    return buf, view
-
-
-def _untouched_outside(buf, view):
-    off = (view.data_ptr() - buf.data_ptr()) // 4
-    return bool((buf[:off] == SENTINEL).all()) and bool((buf[off + view.numel():] == SENTINEL).all())
 
 
 _REFERENCES = {}
