@@ -3,7 +3,7 @@
 `_compute_isotonic_from_index` (:73-81), `_get_best_unimodality_index` (:84-92), `_unimodal_regression` (:95-104) and
 `unimodal_regression` (:107-141).  Plain NumPy, fp64 - the plugin surface for penalty authors and post-processing.
 The solver never calls it: inside `cmf_aoadmm` the projection runs in the HIP kernel `k_slab_unimodal_v4`
-(`csrc/generic.hip`), one lane per column.
+(`csrc/unimodal.hip`), one lane per column.
 
 Only unit weights are implemented (the reference's decomposition never passes any others, penalties.py:1014-1015).
 """

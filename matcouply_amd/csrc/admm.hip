@@ -1889,10 +1889,7 @@ int mcl_launch_C_solve_f64(mcl_context *c) {
 template <int NBR, int NREG>
 static void launch_rows_fused_t(mcl_context *c, const TileMap &tm, const float *rhs, const float *Arows,
                                 const float *rho, const float *Linv, float *F, const RegSet &rs, double *diag) {
-    bool vec = (c->r % 4 == 0) && ((reinterpret_cast<uintptr_t>(rhs) & 15) == 0) &&
-               ((reinterpret_cast<uintptr_t>(F) & 15) == 0);
-    for (int k = 0; k < rs.n; ++k)
-        vec = vec && ((reinterpret_cast<uintptr_t>(rs.aux[k]) & 15) == 0) && ((reinterpret_cast<uintptr_t>(rs.dual[k]) & 15) == 0);
+    const bool vec = mcl_rows_vec_ok(c->r, rs, F, rhs);
     dim3 grid((unsigned)((tm.n_tiles + 3) / 4)), block(256);
     if (vec)
         hipLaunchKernelGGL((k_rows_fused<NBR, NREG, true>), grid, block, 0, c->stream, tm.slab, tm.row0, tm.nrows,
@@ -1956,9 +1953,7 @@ int mcl_launch_rows_fused(mcl_context *c, int mode) {
 template <int NBR, int NREG>
 static int launch_C_fused_t(mcl_context *c) {
     const RegSet &rs = c->regs[2];
-    bool vec = (c->r % 4 == 0) && ((reinterpret_cast<uintptr_t>(c->C) & 15) == 0) && ((c->r * c->r) % 4 == 0);
-    for (int k = 0; k < rs.n; ++k)
-        vec = vec && ((reinterpret_cast<uintptr_t>(rs.aux[k]) & 15) == 0) && ((reinterpret_cast<uintptr_t>(rs.dual[k]) & 15) == 0);
+    const bool vec = mcl_rows_vec_ok(c->r, rs, c->C) && ((c->r * c->r) % 4 == 0);
     const int rpw = c->K <= 256 ? 16 : (c->K <= 512 ? 32 : 64);
     const int n_waves = (int)((c->K + rpw - 1) / rpw);
     size_t sm = sizeof(float) * (size_t)(c->r * c->r + c->K * c->r);
@@ -2139,9 +2134,7 @@ int mcl_launch_ctc_fold(mcl_context *c) {
 template <int NREG>
 static int launch_C_multi_t(mcl_context *c) {
     const RegSet &rs = c->regs[2];
-    bool vec = (c->r % 4 == 0) && ((reinterpret_cast<uintptr_t>(c->C) & 15) == 0) && ((c->r * c->r) % 4 == 0);
-    for (int k = 0; k < rs.n; ++k)
-        vec = vec && ((reinterpret_cast<uintptr_t>(rs.aux[k]) & 15) == 0) && ((reinterpret_cast<uintptr_t>(rs.dual[k]) & 15) == 0);
+    const bool vec = mcl_rows_vec_ok(c->r, rs, c->C) && ((c->r * c->r) % 4 == 0);
     const int nblk = (int)((c->K + 63) / 64);
 #define MCL_CM(VEC_)                                                                                                   \
     hipLaunchKernelGGL((k_C_finish_multi<NREG, VEC_>), dim3(nblk), dim3(256), 0, c->stream, c->GR, (int)c->K, c->r,       \
@@ -2270,10 +2263,10 @@ int mcl_launch_A_e1(mcl_context *c, bool btb_is_q) {
 int mcl_launch_rows_diag(mcl_context *c, int mode) {
     ProfScope prof_(c, MCL_PROF_DIAG);
     c->variant[MCL_PROF_DIAG] = "k_diag_final";
-    const TileMap &tm = (mode == 1) ? c->tilesB : (mode == 2 ? c->tilesC : c->tilesA);
+    const TileMap &tm = mcl_tiles(c, mode);
     if (tm.n_tiles == 0) return 0;
     const float *F = (mode == 1) ? c->B : (mode == 2 ? c->C : c->A);
-    double *diag = (mode == 1) ? c->diagB_tile : (mode == 2 ? c->diagC_tile : c->diagA_tile);
+    double *diag = mcl_diag_tile(c, mode);
     bool vec = (c->r % 4 == 0) && ((reinterpret_cast<uintptr_t>(F) & 15) == 0);
     for (int k = 0; k < c->regs[mode].n; ++k) vec = vec && ((reinterpret_cast<uintptr_t>(c->regs[mode].aux[k]) & 15) == 0);
     dim3 grid((unsigned)((tm.n_tiles + 3) / 4)), block(256);

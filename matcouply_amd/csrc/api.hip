@@ -9,8 +9,6 @@
 
 #include "mcl_internal.h"
 
-int mcl_launch_generic_prox_local(mcl_context *c, int mode, int k);   // generic.hip
-int mcl_launch_generic_prox_finish(mcl_context *c, int mode, int k);  // generic.hip
 int mcl_rows_fused_dispatch(mcl_context *c, int mode, double *diag);  // admm.hip
 
 static std::string g_create_error;

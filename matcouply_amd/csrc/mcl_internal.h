@@ -65,7 +65,7 @@ struct TileMap {
     int *nrows = nullptr;  // device int32[n_tiles]
 };
 
-// One mode's factor as the row kernels see it (generic.hip: view_of; passed by value)
+// One mode's factor as the row kernels see it (rows_launch.h: view_of; passed by value)
 struct ModeView {
     const int *tile_slab, *tile_row0, *tile_nrows;
     int n_tiles;
@@ -324,6 +324,19 @@ static inline int mcl_xc_chunks(const mcl_context *c, int *kct) {
 
 static inline int mcl_pad_rank(int r) { return r <= 4 ? 4 : r <= 8 ? 8 : r <= 16 ? 16 : r <= 32 ? 32 : 64; }
 
+// the row tiling and the per-tile diagnostics table of a mode (0: A, 1: the B_i, 2: C)
+static inline const TileMap &mcl_tiles(const mcl_context *c, int mode) { return mode == 1 ? c->tilesB : (mode == 2 ? c->tilesC : c->tilesA); }
+static inline double *mcl_diag_tile(const mcl_context *c, int mode) { return mode == 1 ? c->diagB_tile : (mode == 2 ? c->diagC_tile : c->diagA_tile); }
+
+// Rows of r floats can move 16 bytes at a time (the VEC forms of the row kernels): r % 4 == 0 and the factor, `extra` (the
+// right-hand side; may be NULL) and every auxiliary and dual array of the penalty list are 16-byte aligned.
+static inline bool mcl_rows_vec_ok(int r, const RegSet &rs, const void *F, const void *extra = nullptr) {
+    bool vec = (r % 4 == 0) && ((reinterpret_cast<uintptr_t>(F) & 15) == 0) && ((reinterpret_cast<uintptr_t>(extra) & 15) == 0);
+    for (int k = 0; k < rs.n; ++k)
+        vec = vec && ((reinterpret_cast<uintptr_t>(rs.aux[k]) & 15) == 0) && ((reinterpret_cast<uintptr_t>(rs.dual[k]) & 15) == 0);
+    return vec;
+}
+
 // ---- launchers implemented in contract.hip ---------------------------------------------------------
 int mcl_launch_build_cfrag(mcl_context *c);
 int mcl_launch_contract_xc(mcl_context *c);                      // XC = X @ C
@@ -353,8 +366,6 @@ int mcl_launch_B_rho(mcl_context *c);
 int mcl_launch_B_systems(mcl_context *c);
 int mcl_launch_B_solve_f64(mcl_context *c);                      // penalty-free B: B_i = ((X_i C) o a_i) L_i^-1 in fp64
 int mcl_launch_rows_fused(mcl_context *c, int mode);             // fused inner ADMM loop, row-separable penalties
-int mcl_launch_rows_solve(mcl_context *c, int mode, double *change_part = nullptr);
-int mcl_launch_inner_check(mcl_context *c, int mode, bool begin);  // generic.hip: the inner stopping test on the device
 int mcl_launch_rows_prox(mcl_context *c, int mode, int k);       // generic prox step of penalty k (local part)
 int mcl_launch_rows_prox_finish(mcl_context *c, int mode, int k);
 int mcl_launch_C_prepare(mcl_context *c);
@@ -362,7 +373,6 @@ int mcl_launch_C_solve_f64(mcl_context *c);                      // penalty-free
 int mcl_launch_C_finish_fused(mcl_context *c);
 int mcl_launch_A_rho(mcl_context *c);
 int mcl_launch_A_finish(mcl_context *c, bool fused_inner);
-int mcl_launch_A_rows_solve(mcl_context *c, double *change_part = nullptr);
 int mcl_launch_A_e1(mcl_context *c, bool btb_is_q);
 int mcl_launch_rows_diag(mcl_context *c, int mode);
 int mcl_launch_diag_final(mcl_context *c, double *out, int include_replicated, bool a_from_rows);
@@ -374,20 +384,12 @@ int mcl_launch_verdict(mcl_context *c, const double *vec, const mcl_stop_rule *r
                        int *status_dev);  // the stopping test on an already reduced vector (sharded loop)
 int mcl_launch_x_sq(mcl_context *c);
 bool mcl_mode_is_row_separable(const mcl_context *c, int mode);
-bool mcl_stack_can_fuse(const mcl_context *c, int mode);          // generic.hip
-bool mcl_rows64(const mcl_context *c);                            // generic.hip
-int mcl_launch_rows_finish_fused(mcl_context *c, int mode, bool want_diag);  // generic.hip
-bool mcl_stats_can_ride_in_solve(const mcl_context *c, int mode);  // generic.hip
-bool mcl_stats_reduce_in_algebra(const mcl_context *c);            // generic.hip
-int mcl_launch_rows_finish_solve_stats(mcl_context *c);           // generic.hip: finish of iteration t + solve / stats of t + 1
-int mcl_launch_rows_solve_stats(mcl_context *c);                  // generic.hip: B solve + per-tile statistics + reduce
 bool mcl_wide_applies(const mcl_context *c, int mode);          // wide.hip: the fp64 inner loop of small problems takes the mode
 int mcl_wide_phase(mcl_context *c, int mode);                    // wide.hip
 bool mcl_exact_mode(const mcl_context *c);                      // contract.hip
 int mcl_launch_exact_xc(mcl_context *c);                         // contract.hip: XC64 (+ its fp32 image) = X C, exact products
 int mcl_launch_exact_gr(mcl_context *c);                         // contract.hip: GR = [G | R] of this rank's slabs, exact products
 int mcl_launch_unimodal(mcl_context *c, const int *ext, int n_slabs, float *F, const RegSet &rs, int mode, int k);  // unimodal.hip
-int mcl_launch_gl2_value(mcl_context *c, int mode, int k, double *out);  // generic.hip: sum over slabs of trace(F^T M F)
 int mcl_try_contract_xc_lds(mcl_context *c, int gram);  // xclds.hip: X C with the fragment image of C resident in LDS
 int mcl_try_rows_chain_mid(mcl_context *c, const ModeView &mv, const float *rhs, bool vec, bool rows64);  // rowchain.hip
 int mcl_try_rows_chain_first(mcl_context *c, const ModeView &mv, const float *rhs, bool vec, bool rows64);
@@ -395,6 +397,37 @@ int mcl_try_rows_chain_last(mcl_context *c, const ModeView &mv, bool vec, bool r
 int mcl_launch_pf2_cond_track(mcl_context *c);                         // cond.hip: monitor slot 3 <- worst polar-factor conditioning of the last PARAFAC2 inner iteration
 int64_t mcl_cond_part_doubles(const mcl_context *c);                    // cond.hip
 int mcl_launch_cond_probe(mcl_context *c, int want, double *out, bool accumulate = false);  // cond.hip: kappa of the penalty-free modes' systems -> out[3]
+
+// ---- rows.hip: the row passes of the un-fused inner loop --------------------------------------------------------
+bool mcl_rows64(const mcl_context *c);
+bool mcl_stack_can_fuse(const mcl_context *c, int mode);
+bool mcl_stats_can_ride_in_solve(const mcl_context *c, int mode);
+int mcl_launch_inner_check(mcl_context *c, int mode, bool begin);  // the inner stopping test on the device
+int mcl_launch_inner_check_raw(mcl_context *c, bool begin, const double *change_part, int n_change, const double *tab, int n_rows,
+                               int n_regs);
+int mcl_launch_rows_solve(mcl_context *c, int mode, double *change_part = nullptr);
+int mcl_launch_A_rows_solve(mcl_context *c, double *change_part = nullptr);
+int mcl_launch_rows_solve_stats(mcl_context *c);         // B solve + per-tile statistics + reduce
+int mcl_launch_rows_finish_solve_stats(mcl_context *c);  // finish of iteration t + solve / stats of t + 1
+int mcl_launch_rows_finish_fused(mcl_context *c, int mode, bool want_diag);
+int mcl_launch_generic_prox_local(mcl_context *c, int mode, int k);   // prox of penalty k: dispatches on its kind into the files below
+int mcl_launch_generic_prox_finish(mcl_context *c, int mode, int k);  // ... and what has to wait for a multi-GPU host's all-reduce
+
+// ---- slabprox.hip: the slab-coupled proxes of the rarer penalties (enqueue only: the caller checks the launch error) --------
+void mcl_launch_prox_l2ball(mcl_context *c, const ModeView &mv, const RegSet &rs, int k, bool vec);  // column norms (+ scale and dual step when the stack is not fused)
+void mcl_launch_prox_tv(mcl_context *c, const ModeView &mv, const RegSet &rs, int k);       // aux only: k_rows_dual follows
+void mcl_launch_prox_gl2(mcl_context *c, const ModeView &mv, const RegSet &rs, int k);      // aux and dual
+void mcl_launch_prox_simplex(mcl_context *c, const ModeView &mv, const RegSet &rs, int k);  // aux only: k_rows_dual follows
+int mcl_launch_gl2_value(mcl_context *c, int mode, int k, double *out);  // sum over slabs of trace(F^T M F)
+int mcl_launch_gl2_wide(mcl_context *c, int mode, int k, const double *F64, double *Z64, double *D64);  // the same kernels on the fp64 state of wide.hip
+int mcl_launch_simplex_wide(mcl_context *c, int mode, int k, const double *F64, const double *D64, double *Z64);
+
+// ---- pf2polar.hip: the PARAFAC2 prox of mode 1 around its row passes ------------------------------------------------------
+bool mcl_stats_reduce_in_algebra(const mcl_context *c);
+int mcl_launch_pf2_polar(mcl_context *c, int k);  // S_i (unless the solve pass left it), then T_i and rho_i T_i^T S_i of every slab
+void mcl_launch_pf2_sum(mcl_context *c, int k);   // ... summed over the slabs (single process: and the new Delta); enqueue only
+void mcl_launch_pf2_delta(mcl_context *c, int k);  // Delta from the (all-reduced) sums; enqueue only
+int mcl_launch_pf2_jacobi_wide(mcl_context *c, int k, const double *F64, const double *U64, const double *D64);  // T_i from the fp64 state of wide.hip
 
 // ---- svdinit.hip: pieces of init="svd" that the CP initialiser (alsinit.hip) shares ------------------------------------------
 // C of mcl_svd_init_typed (bit for bit) without the per-matrix vectors; the workspace is mcl_svd_init's

@@ -1,8 +1,8 @@
 // The chained B-mode row pass of a fused penalty stack with its loads SOFTWARE-PIPELINED: k_rows_chain_first / _mid / _last are
-// the pipelined forms of k_rows_solve_stats / k_rows_finish_solve_stats / k_rows_finish_fused (generic.hip).
+// the pipelined forms of k_rows_solve_stats / k_rows_finish_solve_stats / k_rows_finish_fused (rows.hip).
 //
 // The arithmetic of a pass - column scale, right-hand side, prox and dual of every penalty class, the Gram and column-square
-// statistics, the diagnostics - is the shared code of rows_stack.h, the same functions the kernels of generic.hip call: there is
+// statistics, the diagnostics - is the shared code of rows_stack.h, the same functions the kernels of rows.hip call: there is
 // one definition of every operation, its order and its rounding.  What this file adds is the pipeline around it.
 //
 // The un-pipelined pass reads the rows of a 16-row block (factor, right-hand side, the dual of every penalty, the auxiliary rows
@@ -13,8 +13,8 @@
 // let the block's wait cover exactly its own loads (s_waitcnt vmcnt(N) with N = everything younger), the number of memory
 // operations between two waits has to be a compile-time constant:
 //   * the composition of the stack (how many penalties, which of them PARAFAC2 / unimodality / L2 ball) is a TEMPLATE
-//     argument - the stacks of the BASELINE configurations are instantiated, every other stack keeps the kernel of generic.hip;
-//     the class of penalty k reaches the shared code as the constant sig_cls(SIG, k), where generic.hip passes class_of(kind);
+//     argument - the stacks of the BASELINE configurations are instantiated, every other stack keeps the kernel of rows.hip;
+//     the class of penalty k reaches the shared code as the constant sig_cls(SIG, k), where rows.hip passes class_of(kind);
 //   * loads are unconditional at clamped addresses into a Blk and masked at use, stores are unconditional with the lanes outside
 //     the matrix writing to a per-lane sink;
 //   * a block is entered only from its predecessor (unrolled loop with an early exit).
@@ -347,7 +347,7 @@ static int chain_signature(const mcl_context *c, bool vec) {
     } while (0)
 
 // The software-pipelined forms of the three kernels of the chained B row pass.  Each returns 1 when it has launched, 0 when the
-// stack / shape is not covered (the caller launches the kernel of generic.hip).
+// stack / shape is not covered (the caller launches the kernel of rows.hip).
 int mcl_try_rows_chain_mid(mcl_context *c, const ModeView &mv, const float *rhs, bool vec, bool rows64) {
     const int sig = chain_signature(c, vec);
     if (!sig) return 0;

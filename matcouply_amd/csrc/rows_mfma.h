@@ -20,7 +20,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // z = y * s of the L2-ball projection, rounded to fp32 before the dual update u = f - (z - u) uses it.  Left to the
 // compiler, the product is fused into that subtraction (v_fma_f32 with -u) in some kernels and not in others, which
-// broke the bit-identity of the software-pipelined row passes (rowchain.hip) with the kernels of generic.hip
+// broke the bit-identity of the software-pipelined row passes (rowchain.hip) with the kernels of rows.hip
 // (tests/test_gpu_rowchain.py); the reference, too, subtracts the stored auxiliary variable.
 static __device__ __forceinline__ float l2_scaled(float y, float s) {
 #pragma clang fp contract(off)
@@ -146,7 +146,7 @@ static __device__ __forceinline__ void row_st4(float *__restrict__ base, long j,
     }
 }
 
-// ---- the same row algebra in fp64 (PARAFAC2 stacks of rank <= 16, generic.hip) ----------------------------------------
+// ---- the same row algebra in fp64 (PARAFAC2 stacks of rank <= 16, rows.hip) ----------------------------------------
 // v_mfma_f64_16x16x4_f64 has the operand layouts of the fp32 instruction (A[i = l & 15][k = l >> 4], B[k = l >> 4][j = l & 15])
 // but ANOTHER result layout: lane l, register v holds D[i = (l >> 4) + 4 v][j = l & 15].  For the transposed problem
 // out^T = M^T t^T the row index i of D is an output COLUMN, so loading the A operand with the columns of M permuted by

@@ -1,8 +1,8 @@
 // The arithmetic of the B-mode row pass of a fused penalty stack, written ONCE.
 //
-// Seven kernels run it: k_rows_solve, k_rows_solve_stats, k_rows_finish_fused and k_rows_finish_solve_stats of generic.hip, and
+// Seven kernels run it: k_rows_solve, k_rows_solve_stats, k_rows_finish_fused and k_rows_finish_solve_stats of rows.hip, and
 // their software-pipelined forms k_rows_chain_first / _mid / _last of rowchain.hip.  The kernels own what differs between them:
-// how rows are loaded, masked and stored (masked row_ld4 / row_st4 in generic.hip; unconditional loads at clamped addresses,
+// how rows are loaded, masked and stored (masked row_ld4 / row_st4 in rows.hip; unconditional loads at clamped addresses,
 // masks at use and sink stores in rowchain.hip) and whether the class of a penalty is a run-time or a compile-time value.  The
 // parts below take rows that are already loaded and masked (zeros for padding rows / columns) as f32x4[NBR] in the fragment
 // layout of rows_mfma.h and return rows to store; the only global memory they touch themselves are the r x r matrices of the

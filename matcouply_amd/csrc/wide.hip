@@ -20,12 +20,6 @@
 #include "mcl_internal.h"
 #include "rows_mfma.h"
 
-int mcl_launch_pf2_jacobi_wide(mcl_context *c, int k, const double *F64, const double *U64, const double *D64);  // generic.hip
-int mcl_launch_gl2_wide(mcl_context *c, int mode, int k, const double *F64, double *Z64, double *D64);             // generic.hip
-int mcl_launch_simplex_wide(mcl_context *c, int mode, int k, const double *F64, const double *D64, double *Z64);  // generic.hip
-int mcl_launch_inner_check_raw(mcl_context *c, bool begin, const double *change_part, int n_change, const double *tab, int n_rows,
-                               int n_regs);  // generic.hip
-
 namespace {
 
 struct WideRows {  // the rows of one mode, as tiles of <= 64 rows of one slab
@@ -320,7 +314,7 @@ __global__ __launch_bounds__(64) void k_wide_A_solve(WideState S, const double *
 
 // The sums of the inner stopping test (decomposition.py:100-116) from the fp64 state, one table row per workgroup in the
 // layout of the diagnostics tables (column 0: ||F||^2, columns 2 + k: ||Z_k - F||^2, Z_k = P Delta for the PARAFAC2 member):
-// k_inner_check (generic.hip) takes it from there
+// k_inner_check (rows.hip) takes it from there
 __global__ __launch_bounds__(64) void k_wide_sums(WideRows W, WideState S, int n, int r, double *__restrict__ tab) {
     MCL_GATE(W.gate);
     constexpr int RW = WIDE_RW;
@@ -525,7 +519,7 @@ __global__ __launch_bounds__(64) void k_wide_unimodal(WideRows W, WideState S, R
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// Total variation (penalties.py:750-841; L. Condat's direct algorithm as in generic.hip: k_slab_tv) on the fp64 state
+// Total variation (penalties.py:750-841; L. Condat's direct algorithm as in slabprox.hip: k_slab_tv) on the fp64 state
 // ---------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(64) void k_wide_tv(WideRows W, WideState S, RegSet regs, int kreg, int r) {
     MCL_GATE(W.gate);
@@ -607,7 +601,7 @@ __global__ __launch_bounds__(64) void k_wide_tv(WideRows W, WideState S, RegSet 
 
 // ---------------------------------------------------------------------------------------------------------
 // PARAFAC2 (penalties.py:1224-1250, 1280-1281) on the fp64 state: S_i = Y_i^T Y_i, Y = F + U; the polar factors through the
-// Jacobi / QR kernels of generic.hip (fp64 throughout; mcl_launch_pf2_jacobi_wide); P_i = Y_i T_i; Delta; dual step
+// Jacobi / QR kernels of pf2polar.hip (fp64 throughout; mcl_launch_pf2_jacobi_wide); P_i = Y_i T_i; Delta; dual step
 // ---------------------------------------------------------------------------------------------------------
 constexpr int WIDE_GRAM_ROWS = 64;
 __global__ __launch_bounds__(256) void k_wide_gram(WideRows W, WideState S, int k, int r, double *__restrict__ Sout) {
@@ -728,7 +722,7 @@ __global__ __launch_bounds__(64) void k_wide_pf2_dual(WideRows W, WideState S, R
 
 WideRows rows_of(const mcl_context *c, int mode) {
     WideRows W{};
-    const TileMap &tm = (mode == 1) ? c->tilesB : (mode == 2 ? c->tilesC : c->tilesA);
+    const TileMap &tm = mcl_tiles(c, mode);
     W.tile_slab = tm.slab, W.tile_row0 = tm.row0, W.tile_nrows = tm.nrows, W.n_tiles = tm.n_tiles;
     if (mode == 1) W.ext = c->row_ptr_dev, W.n_slabs = (int)c->I, W.rho = c->rhoB;
     else if (mode == 2) W.ext = c->ext_C, W.n_slabs = 1, W.rho = c->rhoC;

@@ -192,7 +192,7 @@ ROWCHAIN_NO_PASS_CHAIN_CASES = {"pf2_l2_r4": 5, "pf2_l2_r20": 3, "pf2_uni_l2_r12
                                 "pf2_nn_r24": 5}
 # two full outer iterations through the public call against the oracle (every signature x bucket)
 ROWCHAIN_TRAJECTORY_CASES = ["pf2_l2_r4", "pf2_l2_r20", "pf2_uni_l2_r8", "pf2_uni_l2_r32", "pf2_box_r12", "pf2_l1nn_r28"]
-# stacks and shapes the chain does not serve: the kernels of generic.hip (or checked_inner_loop) must take them
+# stacks and shapes the chain does not serve: the kernels of rows.hip (or checked_inner_loop) must take them
 ROWCHAIN_OTHER_CASES = {
     "r6_not_multiple_of_4": dict(J=[18, 40, 65, 100], K=48, rank=6, B=[PF2, _L2], inner=3, seed=20),
     "pf2_l2_r36_nb4": dict(J=[108, 150, 200], K=96, rank=36, B=[PF2, _L2], inner=3, seed=21),

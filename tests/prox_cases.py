@@ -1,5 +1,5 @@
-"""Inputs and fp64 references of the prox-kernel tests (csrc/generic.hip: k_slab_tv, k_slab_simplex, k_gl2_pass, k_gl2_value,
-k_slab_colsq + k_rows_l2ball, k_rows_prox_rowsep, k_rows_dual; csrc/wide.hip: their k_wide_* forms).  Shared by the GPU tests
+"""Inputs and fp64 references of the prox-kernel tests (csrc/slabprox.hip: k_slab_tv, k_slab_simplex, k_gl2_pass, k_gl2_value,
+k_slab_colsq + k_rows_l2ball; csrc/rows.hip: k_rows_prox_rowsep, k_rows_dual; csrc/wide.hip: their k_wide_* forms).  Shared by the GPU tests
 (tests/test_gpu_prox_kernels.py) and the CPU checks that the references solve the problems they stand for and that the inputs
 leave the easy regime (tests/test_prox_cases_host.py).  No GPU, no torch.
 

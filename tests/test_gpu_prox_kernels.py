@@ -2,8 +2,8 @@
 tests/test_prox_cases_host.py), at the slab, rank and alignment edges of its tiling.
 
 (a) test_kernel_alone_*: mode 1 through the step API without a solve (mcl_B_begin, mcl_B_factor, mcl_B_prox_local): the stack is not
-    fused, so the call runs exactly k_rows_prox_rowsep | k_slab_colsq + k_rows_l2ball | k_slab_tv + k_rows_dual | k_gl2_pass (both
-    directions) | k_slab_simplex + k_rows_dual of csrc/generic.hip, on designed Y = B + U (exact in fp32 and fp64) at the
+    fused, so the call runs exactly k_rows_prox_rowsep (csrc/rows.hip) | k_slab_colsq + k_rows_l2ball | k_slab_tv + k_rows_dual |
+    k_gl2_pass (both directions) | k_slab_simplex + k_rows_dual (csrc/slabprox.hip; k_rows_dual: rows.hip), on designed Y = B + U (exact in fp32 and fp64) at the
     feasibility penalties the device computed (eight decades over the eleven slabs).
     Bar on aux: |got - want| <= 2.4e-7 max(1, max |Y| of the slab column, threshold) - four half-units of fp32 (4 x 2^-24 =
     2.4e-7), the bar of tests/test_gpu_unimodal_kernels.py.  fp32 roundings between Y and the stored value, everything else

@@ -3,7 +3,7 @@
 
   (a) one B-phase against the oracle, every case, and two outer iterations of one case per signature x bucket through the public
       call (the B-mode feasibility gaps k_rows_chain_last writes into its diagnostics tiles);
-  (b) the pipelined kernels against the un-pipelined ones of generic.hip (MCL_NO_ROW_PREFETCH=1), bit for bit;
+  (b) the pipelined kernels against the un-pipelined ones of rows.hip (MCL_NO_ROW_PREFETCH=1), bit for bit;
   (c) the fp32 NB = 1 forms (MCL_NO_ROWS64=1) and first + last in every inner iteration (MCL_NO_PASS_CHAIN=1);
   (d) stacks and shapes the chain does not serve, which must take other kernels and still meet the bars of (a).
 

@@ -1,12 +1,16 @@
 """Section timing of k_pf2_algebra_ns on BASELINE config 4 (GPU box).  Needs an instrumented library:
-    MCL_BUILD_DEFS=-DMCL_NS_STAMPS python matcouply_amd/_build.py --force && python tools/ns_stamps.py
-(rebuild without the define afterwards).  Prints, over the slabs of the last inner iteration: cycles (s_memtime, 100 MHz
-on gfx950) of the statistics prologue, G = Delta S Delta^T, the Newton-Schulz loop, the epilogue, and the steps taken."""
+    python - <<<'from matcouply_amd import _build; _build.build_library(defs=["-DMCL_NS_STAMPS"], out_lib="build_ab/libmatcouply_hip_nsstamps.so", build_dir="build_ab", only=["pf2polar.hip", "api.hip"])'
+    MCL_TEST_LIB=build_ab/libmatcouply_hip_nsstamps.so python tools/ns_stamps.py
+(pf2polar.hip holds the stamped kernel, api.hip reserves the stamps' scratch; the in-tree library stays as it is).  Prints, over
+the slabs of the last inner iteration: cycles (s_memtime, 100 MHz on gfx950) of the statistics prologue, G = Delta S Delta^T,
+the Newton-Schulz loop, the epilogue, and the steps taken."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
-import bench
 from matcouply_amd import _engine
+if os.environ.get("MCL_TEST_LIB"):
+    _engine.LIB_PATH = os.path.abspath(os.environ["MCL_TEST_LIB"])
+import bench
 
 cfg = bench.CONFIGS[os.environ.get("CFG", "c4")]
 dev = torch.device("cuda", 0)

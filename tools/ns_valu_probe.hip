@@ -15,7 +15,7 @@
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 typedef double f64x2 __attribute__((ext_vector_type(2)));
 
-// ---- MFMA form (generic.hip: mm_t / tr_lds at NB = 1)
+// ---- MFMA form (pf2polar.hip: mm_t / tr_lds at NB = 1)
 static __device__ __forceinline__ f64x4 mm_t(const f64x4 &A, const f64x4 &B) {  // A^T B, operands and result in D layout
     f64x4 acc = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
