@@ -1030,7 +1030,7 @@ int mcl_A_begin(mcl_context *c) {
         if (int rc = monitor_condition(c, 0)) return rc;
     // C^T C still in the partial blocks of k_C_finish_multi: the rows kernels of the A-phase finish sum them themselves (and
     // write the totals); anything else - the constant-rho pre-pass, the column-layout finish - gets them folded first
-    const bool rows_finish = !(c->RP == 64 || c->RP == 4 || c->sw.a_finish_cols) && !c->opt.constant_A;
+    const bool rows_finish = mcl_a_finish_rows(c) && !c->opt.constant_A;
     if (!(c->ctc_valid && c->ctc_parts > 0 && rows_finish))
         if (int rc = ensure_ctc(c)) return rc;
     // When X C has to be recomputed anyway (C changed), the per-slab reductions ride in its epilogue; the
@@ -1048,7 +1048,7 @@ int mcl_A_begin(mcl_context *c) {
         // the system (k_A_finish_rows_wide; one wave alone took 27 us for 8 partials, against 5 + 13 us apart); one partial
         // per slab on big problems: the finishing wave streams it (16 KB at K = 256) in front of its Gauss-Jordan; more
         // than 8: the separate kernel
-        const bool fusable = (c->RP == 8 || c->RP == 16 || c->RP == 32) && !c->sw.a_finish_cols && !c->sw.no_a_fusion;
+        const bool fusable = mcl_a_finish_rows(c) && !c->sw.no_a_fusion;
         // (with one partial per slab only while all the workgroups are resident at once - two per CU: beyond 512 slabs a
         // second round of workgroups would cost more than the overlap returns, config 3: +4 us)
         c->a_rhs_wide = fusable && c->n_parts <= 8 * c->I && (c->n_parts > c->I || c->I <= 512) && !c->sw.no_a_wide;

@@ -47,7 +47,7 @@ struct RegSet {
     } while (0)
 
 // The per-row / per-tile fp64 diagnostic tables of the three modes and what else the MCL_DIAG_LEN vector is made of
-// (k_diag_final, and the spare workgroup of k_reduce_frag that takes over a DEFERRED reduction: admm.hip / sweep.hip).
+// (k_diag_final, and the spare workgroup of k_reduce_frag that takes over a DEFERRED reduction: diag.hip / sweep.hip).
 struct DiagTables {
     const double *tab[3];
     int rows[3];
@@ -224,7 +224,7 @@ struct mcl_context {
     DiagTables diag_pending_T{};
     double *diag_pending_out = nullptr;
     int diag_pending_incl = 1;
-    // launch fusion of the A-phase finish (admm.hip: AFuse)
+    // launch fusion of the A-phase finish (afinish.h: AFuse)
     bool a_rhs_from_M = false;       // k_A_finish_rows forms rhs_i from the sweep's M_bseg itself
     bool a_rhs_wide = false;         // ... with one workgroup (four waves) per slab: k_A_finish_rows_wide
     bool a_rhs_pairs = false;        // ... or two slabs per workgroup (one system + one streaming wave each)
@@ -359,7 +359,7 @@ int mcl_launch_sweep(mcl_context *c);            // B-phase + per-bseg X^T B, B^
 int mcl_launch_reduce_weighted(mcl_context *c);  // GR = sum of the sweep blocks' a-weighted partials
 int mcl_launch_A_rhs_from_M(mcl_context *c);     // seg_rhs[bseg] = coldot(M_bseg, C)
 
-// ---- launchers implemented in admm.hip ---------------------------------------------------------------
+// ---- launchers implemented in admm.hip: B systems, exact fp64 solves, fused row loop, C-phase finish ----
 int mcl_launch_ctc(mcl_context *c);
 int mcl_launch_ctc_fold(mcl_context *c);
 int mcl_launch_B_rho(mcl_context *c);
@@ -371,9 +371,14 @@ int mcl_launch_rows_prox_finish(mcl_context *c, int mode, int k);
 int mcl_launch_C_prepare(mcl_context *c);
 int mcl_launch_C_solve_f64(mcl_context *c);                      // penalty-free C: C = R G^-1 in fp64
 int mcl_launch_C_finish_fused(mcl_context *c);
+bool mcl_mode_is_row_separable(const mcl_context *c, int mode);
+// ---- afinish.h: the A-phase finish ------------------------------------------------------------------
+// the finish runs a row-split kernel (k_A_finish_rows*: sums the C^T C partials and can form rhs_i itself), not k_A_finish
+static inline bool mcl_a_finish_rows(const mcl_context *c) { return !(c->RP == 64 || c->RP == 4 || c->sw.a_finish_cols); }
 int mcl_launch_A_rho(mcl_context *c);
 int mcl_launch_A_finish(mcl_context *c, bool fused_inner);
 int mcl_launch_A_e1(mcl_context *c, bool btb_is_q);
+// ---- diag.hip: diagnostics tables and the device stopping rule ------------------------------------------
 int mcl_launch_rows_diag(mcl_context *c, int mode);
 int mcl_launch_diag_final(mcl_context *c, double *out, int include_replicated, bool a_from_rows);
 DiagTables mcl_diag_tables(const mcl_context *c, bool a_from_rows);  // the tables as they stand now
@@ -383,7 +388,7 @@ int mcl_launch_diag_verdict(mcl_context *c, double *out, const mcl_stop_rule *ru
 int mcl_launch_verdict(mcl_context *c, const double *vec, const mcl_stop_rule *rule, int it, double *verdict_row,
                        int *status_dev);  // the stopping test on an already reduced vector (sharded loop)
 int mcl_launch_x_sq(mcl_context *c);
-bool mcl_mode_is_row_separable(const mcl_context *c, int mode);
+// ---- other files ----------------------------------------------------------------------------------------
 bool mcl_wide_applies(const mcl_context *c, int mode);          // wide.hip: the fp64 inner loop of small problems takes the mode
 int mcl_wide_phase(mcl_context *c, int mode);                    // wide.hip
 bool mcl_exact_mode(const mcl_context *c);                      // contract.hip

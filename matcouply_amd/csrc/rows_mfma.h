@@ -49,6 +49,14 @@ static __device__ __forceinline__ double wave_sum(double v) {
     return (readlane_f64_u(v, 0) + readlane_f64_u(v, 16)) + (readlane_f64_u(v, 32) + readlane_f64_u(v, 48));
 }
 
+// one row of a mode's diagnostics table (DIAG_COLS doubles): ||F||^2, sum|F|, ||Z_k - F||^2 per penalty
+static __device__ __forceinline__ void diag_row_store(double *o, double nf, double na, const double (&gap)[MCL_MAX_REGS]) {
+    o[0] = nf;
+    o[1] = na;
+#pragma unroll
+    for (int k = 0; k < MCL_MAX_REGS; ++k) o[2 + k] = gap[k];
+}
+
 // elementwise prox of the row-separable penalties (penalties.py:503-586)
 static __device__ __forceinline__ float prox_elem(int kind, int nonneg, float p0, float p1, float thr, float y) {
     switch (kind) {
@@ -81,7 +89,7 @@ struct ProxClamp {
     }
 };
 
-// the same operator in fp64 (the A-phase finish of small problems keeps its inner loop in double: admm.hip, wide_inner)
+// the same operator in fp64 (the A-phase finish of small problems keeps its inner loop in double: afinish.h, wide_inner)
 struct ProxClampD {
     double pa, pb, plo, phi;
     __device__ __forceinline__ void set(int kind, int nonneg, double p0, double p1, double thr) {
