@@ -241,6 +241,65 @@ class EngineError(RuntimeError):
     pass
 
 
+def _aligned_workspace(nbytes, device):
+    """(address, nbytes) of a 256-byte aligned workspace of nbytes bytes on `device`, and the tensor that owns it"""
+    import torch
+
+    ws = torch.empty(int(nbytes) + 256, dtype=torch.uint8, device=device)
+    return (ws.data_ptr() + (-ws.data_ptr()) % 256, int(nbytes)), ws
+
+
+def _call(device, fn, last_error, *args):
+    """fn(*args, stream) on `device` and its current stream; EngineError with last_error() (a callable that returns the message)
+    when it does not return 0"""
+    import torch
+
+    with torch.cuda.device(device):
+        rc = fn(*args, ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream))
+    if rc != 0:
+        raise EngineError(last_error())
+
+
+class _Packed:
+    """What the bindings of the stand-alone entry points on packed matrices share: the checks on X and row_ptr, the leading
+    arguments (X, x_type, row_ptr, I, K) of the library's functions, the aligned workspace and the call on X's device."""
+
+    def __init__(self, X, row_ptr, two_dim=False):
+        self.xt = x_type_of(X.dtype)
+        if not (X.is_cuda and X.is_contiguous() and (not two_dim or X.dim() == 2)):
+            raise EngineError("X must be a contiguous CUDA tensor" + (" [sum J_i, K]" if two_dim else ""))
+        self.row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int64)
+        self.I, self.K, self.N, self.dev = len(self.row_ptr) - 1, int(X.shape[1]), int(X.shape[0]), X.device
+        if two_dim and int(self.row_ptr[-1]) != self.N:
+            raise EngineError("row_ptr must end at X.shape[0]")
+        self.rp = self.row_ptr.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+        self.X = X
+
+    @property
+    def head(self):
+        return self.X.data_ptr(), self.xt, self.rp, self.I, self.K
+
+    def empty(self, shape, dtype):
+        import torch
+
+        return torch.empty(shape, dtype=dtype, device=self.dev)
+
+    def zeros(self, shape, dtype):
+        import torch
+
+        return torch.zeros(shape, dtype=dtype, device=self.dev)
+
+    def workspace(self, nbytes, sizer=None):
+        """the (address, nbytes) arguments; a negative size: EngineError naming `sizer`, or 0 bytes for the run call to refuse"""
+        if nbytes < 0 and sizer is not None:
+            raise EngineError(f"{sizer}: bad arguments")
+        args, self._ws = _aligned_workspace(max(int(nbytes), 0), self.dev)
+        return args
+
+    def call(self, fn, last_error, *args):
+        _call(self.dev, fn, lambda: last_error().decode(), *args)
+
+
 def cmf_to_packed(A, B, C, row_ptr, weights=None):
     """Dense reconstruction on the device: packed [sum J_i, K] float32 tensor with rows row_ptr[i] .. row_ptr[i+1] equal to
     (B_i diag(weights o a_i)) C^T.  A [I, r], B packed [N, r], C [K, r]: contiguous float32 CUDA tensors."""
@@ -257,12 +316,8 @@ def cmf_to_packed(A, B, C, row_ptr, weights=None):
     counts = torch.as_tensor(np.diff(row_ptr), device=B.device)
     slab = torch.repeat_interleave(torch.arange(len(row_ptr) - 1, device=B.device, dtype=torch.int32), counts)
     out = torch.empty((N, K), dtype=torch.float32, device=B.device)
-    with torch.cuda.device(B.device):
-        stream = torch.cuda.current_stream(B.device).cuda_stream
-        rc = lib.mcl_cmf_to_packed(A.data_ptr(), B.data_ptr(), C.data_ptr(), weights.data_ptr() if weights is not None else None,
-                                   slab.data_ptr(), N, K, r, out.data_ptr(), ctypes.c_void_p(stream))
-    if rc != 0:
-        raise EngineError("mcl_cmf_to_packed failed")
+    _call(B.device, lib.mcl_cmf_to_packed, lambda: "mcl_cmf_to_packed failed", A.data_ptr(), B.data_ptr(), C.data_ptr(),
+          weights.data_ptr() if weights is not None else None, slab.data_ptr(), N, K, r, out.data_ptr())
     return out
 
 
@@ -290,26 +345,12 @@ def svd_init(X, row_ptr, rank, threshold=False):
     import torch
 
     lib = load_library()
-    xt = x_type_of(X.dtype)
-    if not (X.is_cuda and X.is_contiguous()):
-        raise EngineError("X must be a contiguous CUDA tensor")
-    row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int64)
-    I, K, N = len(row_ptr) - 1, int(X.shape[1]), int(X.shape[0])
-    rp = row_ptr.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
-    nbytes = lib.mcl_svd_init_workspace_bytes(rp, I, K, int(rank))
-    if nbytes < 0:
-        raise EngineError("mcl_svd_init_workspace_bytes: bad arguments")
-    ws = torch.empty(int(nbytes) + 256, dtype=torch.uint8, device=X.device)
-    off = (-ws.data_ptr()) % 256
-    B = torch.empty((N, int(rank)), dtype=torch.float32, device=X.device)
-    C = torch.empty((K, int(rank)), dtype=torch.float32, device=X.device)
-    info = torch.zeros(I + 1, dtype=torch.int32, device=X.device)
-    with torch.cuda.device(X.device):
-        stream = torch.cuda.current_stream(X.device).cuda_stream
-        rc = lib.mcl_svd_init_typed(X.data_ptr(), xt, rp, I, K, int(rank), int(bool(threshold)), B.data_ptr(), C.data_ptr(),
-                                    ws.data_ptr() + off, nbytes, info.data_ptr(), ctypes.c_void_p(stream))
-    if rc != 0:
-        raise EngineError(lib.mcl_svd_init_last_error().decode())
+    p, r = _Packed(X, row_ptr), int(rank)
+    ws = p.workspace(lib.mcl_svd_init_workspace_bytes(p.rp, p.I, p.K, r), "mcl_svd_init_workspace_bytes")
+    B, C = p.empty((p.N, r), torch.float32), p.empty((p.K, r), torch.float32)
+    info = p.zeros(p.I + 1, torch.int32)
+    p.call(lib.mcl_svd_init_typed, lib.mcl_svd_init_last_error, *p.head, r, int(bool(threshold)), B.data_ptr(), C.data_ptr(), *ws,
+           info.data_ptr())
     return B, C, info
 
 
@@ -324,29 +365,13 @@ def als_init(X, row_ptr, rank, method, n_iter_max, tol):
     import torch
 
     lib = load_library()
-    xt = x_type_of(X.dtype)
-    if not (X.is_cuda and X.is_contiguous()):
-        raise EngineError("X must be a contiguous CUDA tensor")
-    row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int64)
-    I, K, N = len(row_ptr) - 1, int(X.shape[1]), int(X.shape[0])
-    rp = row_ptr.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
-    nbytes = lib.mcl_als_init_workspace_bytes(rp, I, K, int(rank))
-    if nbytes < 0:
-        raise EngineError("mcl_als_init_workspace_bytes: bad arguments")
-    ws = torch.empty(int(nbytes) + 256, dtype=torch.uint8, device=X.device)
-    off = (-ws.data_ptr()) % 256
-    A = torch.empty((I, int(rank)), dtype=torch.float32, device=X.device)
-    B = torch.empty((N, int(rank)), dtype=torch.float32, device=X.device)
-    C = torch.empty((K, int(rank)), dtype=torch.float32, device=X.device)
-    errors = torch.zeros(max(int(n_iter_max), 1), dtype=torch.float64, device=X.device)
-    info = torch.zeros(1, dtype=torch.int32, device=X.device)
-    with torch.cuda.device(X.device):
-        stream = torch.cuda.current_stream(X.device).cuda_stream
-        rc = lib.mcl_als_init_typed(X.data_ptr(), xt, rp, I, K, int(rank), int(method), int(n_iter_max), float(tol), A.data_ptr(),
-                                    B.data_ptr(), C.data_ptr(), errors.data_ptr(), info.data_ptr(), ws.data_ptr() + off, nbytes,
-                                    ctypes.c_void_p(stream))
-    if rc != 0:
-        raise EngineError(lib.mcl_als_init_last_error().decode())
+    p, r = _Packed(X, row_ptr), int(rank)
+    ws = p.workspace(lib.mcl_als_init_workspace_bytes(p.rp, p.I, p.K, r), "mcl_als_init_workspace_bytes")
+    A, B, C = (p.empty((n, r), torch.float32) for n in (p.I, p.N, p.K))
+    errors = p.zeros(max(int(n_iter_max), 1), torch.float64)
+    info = p.zeros(1, torch.int32)
+    p.call(lib.mcl_als_init_typed, lib.mcl_als_init_last_error, *p.head, r, int(method), int(n_iter_max), float(tol), A.data_ptr(),
+           B.data_ptr(), C.data_ptr(), errors.data_ptr(), info.data_ptr(), *ws)
     return A, B, C, errors[: int(info.item())]
 
 
@@ -361,37 +386,23 @@ def parafac2_als(X, row_ptr, rank, start, n_iter_max, n_iter_parafac, tol, absol
     import torch
 
     lib = load_library()
-    xt = x_type_of(X.dtype)
-    if not (X.is_cuda and X.is_contiguous()):
-        raise EngineError("X must be a contiguous CUDA tensor")
-    row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int64)
-    I, K, N, r = len(row_ptr) - 1, int(X.shape[1]), int(X.shape[0]), int(rank)
-    rp = row_ptr.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
-    nbytes = lib.mcl_parafac2_als_workspace_bytes(rp, I, K, r)
+    p, r = _Packed(X, row_ptr), int(rank)
+    I, K = p.I, p.K
+    nbytes = lib.mcl_parafac2_als_workspace_bytes(p.rp, I, K, r)
     if nbytes < 0:
         raise EngineError("mcl_parafac2_als_workspace_bytes: bad arguments")
-    dev = X.device
     if start is not None:
-        start = [torch.as_tensor(t, dtype=torch.float64, device=dev).contiguous() for t in start]
+        start = [torch.as_tensor(t, dtype=torch.float64, device=p.dev).contiguous() for t in start]
         if [tuple(t.shape) for t in start] != [(I, r), (r, r), (K, r)]:
             raise EngineError("start factors must be [I, rank], [rank, rank], [K, rank]")
-    ws = torch.empty(int(nbytes) + 256, dtype=torch.uint8, device=dev)
-    off = (-ws.data_ptr()) % 256
-    A = torch.empty((I, r), dtype=torch.float32, device=dev)
-    B = torch.empty((r, r), dtype=torch.float32, device=dev)
-    C = torch.empty((K, r), dtype=torch.float32, device=dev)
-    P = torch.empty((N, r), dtype=torch.float32, device=dev)
-    errors = torch.zeros(max(int(n_iter_max), 1), dtype=torch.float64, device=dev)
-    info = torch.zeros(1, dtype=torch.int32, device=dev)
+    ws = p.workspace(nbytes)
+    A, B, C, P = (p.empty((n, r), torch.float32) for n in (I, r, K, p.N))
+    errors = p.zeros(max(int(n_iter_max), 1), torch.float64)
+    info = p.zeros(1, torch.int32)
     mask = sum(1 << int(m) for m in (nn_modes or ()))
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = lib.mcl_parafac2_als_typed(X.data_ptr(), xt, rp, I, K, r, *(t.data_ptr() for t in start) if start is not None else
-                                        (None, None, None), int(n_iter_max), int(n_iter_parafac), float(tol), float(absolute_tol),
-                                        int(mask), A.data_ptr(), B.data_ptr(), C.data_ptr(), P.data_ptr(), errors.data_ptr(),
-                                        info.data_ptr(), ws.data_ptr() + off, nbytes, ctypes.c_void_p(stream))
-    if rc != 0:
-        raise EngineError(lib.mcl_parafac2_als_last_error().decode())
+    p.call(lib.mcl_parafac2_als_typed, lib.mcl_parafac2_als_last_error, *p.head, r,
+           *(t.data_ptr() for t in start) if start is not None else (None, None, None), int(n_iter_max), int(n_iter_parafac), float(tol),
+           float(absolute_tol), int(mask), A.data_ptr(), B.data_ptr(), C.data_ptr(), P.data_ptr(), errors.data_ptr(), info.data_ptr(), *ws)
     used = int(info.item())
     return A, B, C, P, errors[: used if tol > 0 else 0]
 
@@ -446,37 +457,24 @@ def _pf2als_multistart_launch(X, row_ptr, rank, factors, slab_scale, n_iter_max,
     import torch
 
     lib = load_library()
-    xt = x_type_of(X.dtype)
-    if not (X.is_cuda and X.is_contiguous()):
-        raise EngineError("X must be a contiguous CUDA tensor")
-    row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int64)
-    I, K, N, r = len(row_ptr) - 1, int(X.shape[1]), int(X.shape[0]), int(rank)
+    p, r = _Packed(X, row_ptr), int(rank)
     if not (factors.is_cuda and factors.dtype == torch.float64 and factors.is_contiguous() and factors.dim() == 2
-            and factors.shape[1] == (I + r + K) * r):
+            and factors.shape[1] == (p.I + r + p.K) * r):
         raise EngineError("factors must be a contiguous float64 CUDA tensor [n_starts, (I + rank + K) * rank]")
     S = int(factors.shape[0])
-    rp = row_ptr.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
-    nbytes = lib.mcl_pf2als_multistart_workspace_bytes(rp, I, K, r, S)
-    if nbytes < 0:
-        lib.mcl_pf2als_multistart_run(None, xt, rp, I, K, r, S, 1, 1, 0.0, 0.0, 0, None, None, None, None, None, 0, None)
+    nbytes = lib.mcl_pf2als_multistart_workspace_bytes(p.rp, p.I, p.K, r, S)
+    if nbytes < 0:  # the library's sentence: the run call with nothing to run on
+        lib.mcl_pf2als_multistart_run(None, p.xt, p.rp, p.I, p.K, r, S, 1, 1, 0.0, 0.0, 0, None, None, None, None, None, 0, None)
         raise EngineError(lib.mcl_pf2als_multistart_last_error().decode())
-    dev = X.device
-    ws = torch.empty(int(nbytes) + 256, dtype=torch.uint8, device=dev)
-    off = (-ws.data_ptr()) % 256
-    P = torch.empty((S, N, r), dtype=torch.float64, device=dev)
-    errors = torch.zeros((S, max(int(n_iter_max), 1)), dtype=torch.float64, device=dev)
-    n_iter = torch.zeros(S, dtype=torch.int32, device=dev)
+    P = p.empty((S, p.N, r), torch.float64)
+    errors = p.zeros((S, max(int(n_iter_max), 1)), torch.float64)
+    n_iter = p.zeros(S, torch.int32)
     mask = sum(1 << int(m) for m in (nn_modes or ()))
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        tail = (int(n_iter_max), int(n_iter_parafac), float(tol), float(absolute_tol), int(mask), factors.data_ptr(), P.data_ptr(),
-                errors.data_ptr(), n_iter.data_ptr(), ws.data_ptr() + off, nbytes, ctypes.c_void_p(stream))
-        if slab_scale is None:
-            rc = lib.mcl_pf2als_multistart_run(X.data_ptr(), xt, rp, I, K, r, S, *tail)
-        else:
-            rc = lib.mcl_pf2als_multistart_run_weighted(X.data_ptr(), xt, rp, I, K, r, S, slab_scale.data_ptr(), *tail)
-    if rc != 0:
-        raise EngineError(lib.mcl_pf2als_multistart_last_error().decode())
+    run, scale = lib.mcl_pf2als_multistart_run, ()
+    if slab_scale is not None:
+        run, scale = lib.mcl_pf2als_multistart_run_weighted, (slab_scale.data_ptr(),)
+    p.call(run, lib.mcl_pf2als_multistart_last_error, *p.head, r, S, *scale, int(n_iter_max), int(n_iter_parafac), float(tol),
+           float(absolute_tol), int(mask), factors.data_ptr(), P.data_ptr(), errors.data_ptr(), n_iter.data_ptr(), *p.workspace(nbytes))
     return P, errors, n_iter
 
 
@@ -502,19 +500,12 @@ def fms_scores(models, I, N, K, rank, weights, pairs, flags, skip_mode, want_per
     pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
     n_pairs = int(pairs.shape[0])
     dev = models.device
-    nbytes = lib.mcl_fms_workspace_bytes(n_models, r)
-    ws = torch.empty(max(int(nbytes), 0) + 256, dtype=torch.uint8, device=dev)
-    off = (-ws.data_ptr()) % 256
+    (ws, _), keep = _aligned_workspace(max(int(lib.mcl_fms_workspace_bytes(n_models, r)), 0), dev)
     score = torch.empty(n_pairs, dtype=torch.float64, device=dev)
     perm = torch.empty((n_pairs, r), dtype=torch.int32, device=dev) if want_perm else None
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = lib.mcl_fms_scores(models.data_ptr(), n_models, int(I), int(N), int(K), r, weights.data_ptr() if weights is not None
-                                else None, pairs.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), n_pairs, int(flags), int(skip_mode),
-                                score.data_ptr(), perm.data_ptr() if want_perm else None, ws.data_ptr() + off,
-                                ctypes.c_void_p(stream))
-    if rc != 0:
-        raise EngineError(lib.mcl_fms_last_error().decode())
+    _call(dev, lib.mcl_fms_scores, lambda: lib.mcl_fms_last_error().decode(), models.data_ptr(), n_models, int(I), int(N), int(K), r,
+          weights.data_ptr() if weights is not None else None, pairs.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), n_pairs, int(flags),
+          int(skip_mode), score.data_ptr(), perm.data_ptr() if want_perm else None, ws)
     return score, perm
 
 
@@ -537,30 +528,15 @@ def eval_tables(X, row_ptr, rank, models):
     import torch
 
     lib = load_library()
-    xt = x_type_of(X.dtype)
-    if not (X.is_cuda and X.is_contiguous() and X.dim() == 2):
-        raise EngineError("X must be a contiguous CUDA tensor [sum J_i, K]")
-    row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int64)
-    I, K, N, r = len(row_ptr) - 1, int(X.shape[1]), int(X.shape[0]), int(rank)
-    if int(row_ptr[-1]) != N:
-        raise EngineError("row_ptr must end at X.shape[0]")
-    _eval_models_check(models, I, N, K, r)
+    p, r = _Packed(X, row_ptr, two_dim=True), int(rank)
+    I = p.I
+    _eval_models_check(models, I, p.N, p.K, r)
     n = int(models.shape[0])
-    rp = row_ptr.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
-    nbytes = lib.mcl_eval_workspace_bytes(rp, I, K, r, n)
-    dev = X.device
-    ws = torch.empty(max(int(nbytes), 0) + 256, dtype=torch.uint8, device=dev)
-    off = (-ws.data_ptr()) % 256
-    S = torch.empty((n, I, r, r), dtype=torch.float64, device=dev)
-    BtB = torch.empty((n, I, r, r), dtype=torch.float64, device=dev)
-    sse = torch.empty((n, I), dtype=torch.float64, device=dev)
-    norm = torch.empty(I, dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = lib.mcl_eval_tables_typed(X.data_ptr(), xt, rp, I, K, r, models.data_ptr(), n, S.data_ptr(), BtB.data_ptr(), sse.data_ptr(),
-                                       norm.data_ptr(), ws.data_ptr() + off, max(int(nbytes), 0), ctypes.c_void_p(stream))
-    if rc != 0:
-        raise EngineError(lib.mcl_eval_last_error().decode())
+    ws = p.workspace(lib.mcl_eval_workspace_bytes(p.rp, I, p.K, r, n))
+    S, BtB = p.empty((n, I, r, r), torch.float64), p.empty((n, I, r, r), torch.float64)
+    sse, norm = p.empty((n, I), torch.float64), p.empty(I, torch.float64)
+    p.call(lib.mcl_eval_tables_typed, lib.mcl_eval_last_error, *p.head, r, models.data_ptr(), n, S.data_ptr(), BtB.data_ptr(),
+           sse.data_ptr(), norm.data_ptr(), *ws)
     return S, BtB, sse, norm
 
 
@@ -580,12 +556,8 @@ def eval_core(models, I, N, K, rank, S, BtB):
     core = torch.empty((n, r, r, r), dtype=torch.float64, device=dev)
     cc = torch.empty(n, dtype=torch.float64, device=dev)
     ccn = torch.empty(n, dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = lib.mcl_eval_core(models.data_ptr(), n, I, N, K, r, S.data_ptr(), BtB.data_ptr(), core.data_ptr(), cc.data_ptr(),
-                               ccn.data_ptr(), ctypes.c_void_p(stream))
-    if rc != 0:
-        raise EngineError(lib.mcl_eval_last_error().decode())
+    _call(dev, lib.mcl_eval_core, lambda: lib.mcl_eval_last_error().decode(), models.data_ptr(), n, I, N, K, r, S.data_ptr(), BtB.data_ptr(),
+          core.data_ptr(), cc.data_ptr(), ccn.data_ptr())
     return core, cc, ccn
 
 
@@ -601,35 +573,20 @@ def pf2_project(X, row_ptr, rank, Delta, C, a_init, n_iter_max, tol, absolute_to
     import torch
 
     lib = load_library()
-    xt = x_type_of(X.dtype)
-    if not (X.is_cuda and X.is_contiguous() and X.dim() == 2):
-        raise EngineError("X must be a contiguous CUDA tensor [sum J_i, K]")
-    row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int64)
-    I, K, N, r = len(row_ptr) - 1, int(X.shape[1]), int(X.shape[0]), int(rank)
-    if int(row_ptr[-1]) != N:
-        raise EngineError("row_ptr must end at X.shape[0]")
+    p, r = _Packed(X, row_ptr, two_dim=True), int(rank)
+    I, K, N = p.I, p.K, p.N
     for name, t, shp in (("Delta", Delta, (r, r)), ("C", C, (K, r)), ("a_init", a_init, (I, r))):
         if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == shp):
             raise EngineError(f"{name} must be a contiguous float64 CUDA tensor {list(shp)}")
-    rp = row_ptr.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
-    nbytes = lib.mcl_pf2_project_workspace_bytes(rp, I, K, r)
-    dev = X.device
-    ws = torch.empty(max(int(nbytes), 0) + 256, dtype=torch.uint8, device=dev)
-    off = (-ws.data_ptr()) % 256
-    A = torch.empty((I, r), dtype=torch.float64, device=dev)
-    B = torch.empty((N, r), dtype=torch.float32, device=dev)
-    Pm = torch.empty((N, r), dtype=torch.float32, device=dev)
-    stats = torch.empty((I, 2), dtype=torch.float64, device=dev)
-    n_iter = torch.empty(I, dtype=torch.int32, device=dev)
-    errors = torch.empty((I, int(n_iter_max)), dtype=torch.float64, device=dev) if want_errors else None
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = lib.mcl_pf2_project_typed(X.data_ptr(), xt, rp, I, K, r, Delta.data_ptr(), C.data_ptr(), a_init.data_ptr(), int(n_iter_max),
-                                       float(tol), float(absolute_tol), A.data_ptr(), B.data_ptr(), Pm.data_ptr(), stats.data_ptr(),
-                                       n_iter.data_ptr(), errors.data_ptr() if want_errors else None, ws.data_ptr() + off,
-                                       max(int(nbytes), 0), ctypes.c_void_p(stream))
-    if rc != 0:
-        raise EngineError(lib.mcl_pf2_project_last_error().decode())
+    ws = p.workspace(lib.mcl_pf2_project_workspace_bytes(p.rp, I, K, r))
+    A = p.empty((I, r), torch.float64)
+    B, Pm = p.empty((N, r), torch.float32), p.empty((N, r), torch.float32)
+    stats = p.empty((I, 2), torch.float64)
+    n_iter = p.empty(I, torch.int32)
+    errors = p.empty((I, int(n_iter_max)), torch.float64) if want_errors else None
+    p.call(lib.mcl_pf2_project_typed, lib.mcl_pf2_project_last_error, *p.head, r, Delta.data_ptr(), C.data_ptr(), a_init.data_ptr(),
+           int(n_iter_max), float(tol), float(absolute_tol), A.data_ptr(), B.data_ptr(), Pm.data_ptr(), stats.data_ptr(), n_iter.data_ptr(),
+           errors.data_ptr() if want_errors else None, *ws)
     return A, B, Pm, stats, n_iter, errors
 
 
@@ -653,34 +610,22 @@ def multistart_scratch_len(I, N, K, rank):
 def _multistart_launch(X, row_ptr, rank, options, n_options, state, workspace_bytes, run):
     import torch
 
-    xt = x_type_of(X.dtype)
-    if not (X.is_cuda and X.is_contiguous()):
-        raise EngineError("X must be a contiguous CUDA tensor")
+    p, r = _Packed(X, row_ptr), int(rank)
     if not (state.is_cuda and state.dtype == torch.float64 and state.is_contiguous() and state.dim() == 2):
         raise EngineError("state must be a contiguous float64 CUDA tensor [n_starts, state_len]")
-    row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int64)
-    I, K = len(row_ptr) - 1, int(X.shape[1])
     S = int(state.shape[0])
     if n_options is not None and n_options != S:
         raise EngineError(f"{n_options} options for {S} state slices")
     opt = options if n_options is not None else ctypes.byref(options)
-    rp = row_ptr.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
-    nbytes = workspace_bytes(rp, I, K, int(rank), opt, S)
-    if nbytes < 0:
-        run(None, xt, rp, I, K, int(rank), opt, S, None, None, None, None, None, 0, None)
-        raise EngineError(load_library().mcl_multistart_last_error().decode())
-    ws = torch.empty(int(nbytes) + 256, dtype=torch.uint8, device=X.device)
-    off = (-ws.data_ptr()) % 256
+    last_error = load_library().mcl_multistart_last_error
+    nbytes = workspace_bytes(p.rp, p.I, p.K, r, opt, S)
+    if nbytes < 0:  # the library's sentence: the run call with nothing to run on
+        run(None, p.xt, p.rp, p.I, p.K, r, opt, S, None, None, None, None, None, 0, None)
+        raise EngineError(last_error().decode())
     n_iter_most = int(options.n_iter_max) if n_options is None else max(int(o.n_iter_max) for o in options)
-    diag = torch.zeros((S, n_iter_most + 1, MS_DIAG), dtype=torch.float64, device=X.device)
-    n_iter = torch.zeros(S, dtype=torch.int32, device=X.device)
-    stop = torch.zeros(S, dtype=torch.int32, device=X.device)
-    with torch.cuda.device(X.device):
-        stream = torch.cuda.current_stream(X.device).cuda_stream
-        rc = run(X.data_ptr(), xt, rp, I, K, int(rank), opt, S, state.data_ptr(), diag.data_ptr(), n_iter.data_ptr(),
-                 stop.data_ptr(), ws.data_ptr() + off, nbytes, ctypes.c_void_p(stream))
-    if rc != 0:
-        raise EngineError(load_library().mcl_multistart_last_error().decode())
+    diag = p.zeros((S, n_iter_most + 1, MS_DIAG), torch.float64)
+    n_iter, stop = p.zeros(S, torch.int32), p.zeros(S, torch.int32)
+    p.call(run, last_error, *p.head, r, opt, S, state.data_ptr(), diag.data_ptr(), n_iter.data_ptr(), stop.data_ptr(), *p.workspace(nbytes))
     return diag, n_iter, stop
 
 

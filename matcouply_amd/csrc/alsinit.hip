@@ -26,7 +26,7 @@
 
 namespace {
 
-static std::string g_als_error;
+static ErrorSlot g_als_error{"mcl_als_init: "};
 constexpr int ALS_TARGET_WG = 1024;  // workgroups of pass 2 (row chunks x 64-column blocks)
 enum { OP_LOAD = 0, OP_ALS = 1, OP_HALS = 2 };
 
@@ -345,12 +345,16 @@ __global__ __launch_bounds__(256) void k_als_out(const double *__restrict__ A64,
 struct AlsPlan {
     int64_t N, Jm;
     int nseg, nchunk, nkb, ngrp, NB, KH, wgA, wgB, wgC;
-    int64_t off_segs, off_slab_seg, off_chunk_seg, off_ext, off_bgrp, off_A, off_B, off_C, off_Cfrag, off_XC, off_Pa, off_Pb, off_Mb,
-        off_Pc, off_Mc, off_Ma, off_Gp, off_Ep, off_Gram, off_Gm, off_small, off_info, off_scratch;
-    int64_t svd_ws, gv_ws, scratch, total;
+    int4 *segs;
+    int *slab_seg, *chunk_seg, *ext, *bgrp, *info;
+    double *A, *B, *C, *Pa, *Pb, *Mb, *Pc, *Mc, *Ma, *Gp, *Ep, *Gram, *Gm, *small;
+    float *Cfrag, *XC;
+    char *scratch;
+    int64_t svd_ws, gv_ws, total;
 };
 
-AlsPlan als_plan(const int64_t *row_ptr, int64_t I, int64_t K, int rank) {
+// workspace NULL: the parts are null and `total` is the size (mcl_als_init_workspace_bytes)
+AlsPlan als_plan(void *workspace, const int64_t *row_ptr, int64_t I, int64_t K, int rank) {
     AlsPlan p{};
     p.N = row_ptr[I];
     p.Jm = 0;
@@ -365,37 +369,36 @@ AlsPlan als_plan(const int64_t *row_ptr, int64_t I, int64_t K, int rank) {
     p.KH = 4 * (int)((K + 63) / 64);  // 16-row blocks of the C fragments, whole 64-column chunks (zero past K)
     p.wgA = (int)((I + 63) / 64), p.wgB = (int)((p.Jm + 63) / 64), p.wgC = (int)((K + 63) / 64);
     const int wgmax = std::max(p.wgA, std::max(p.wgB, p.wgC));
-    WsCursor ws;
-    p.off_segs = ws.take(std::max<int64_t>(nseg, 1) * 16);
-    p.off_slab_seg = ws.take((I + 1) * 4);
-    p.off_chunk_seg = ws.take((int64_t)(p.nchunk + 1) * 4);
-    p.off_ext = ws.take((I + 1) * 4);
-    p.off_bgrp = ws.take((int64_t)(p.ngrp + 1) * 4);
-    p.off_A = ws.take(I * r * 8);
-    p.off_B = ws.take(p.Jm * r * 8);
-    p.off_C = ws.take(K * r * 8);
-    p.off_Cfrag = ws.take((int64_t)p.KH * p.NB * 64 * 4 * 4);
-    p.off_XC = ws.take(p.N * r * 4);
-    p.off_Pa = ws.take(std::max<int64_t>(nseg, 1) * r * 8);
-    p.off_Pb = ws.take((int64_t)p.ngrp * p.Jm * r * 8);
-    p.off_Mb = ws.take(p.Jm * r * 8);
-    p.off_Pc = ws.take((int64_t)p.nchunk * K * r * 8);
-    p.off_Mc = ws.take(K * r * 8);
-    p.off_Ma = ws.take(I * r * 8);
-    p.off_Gp = ws.take((int64_t)3 * wgmax * r * r * 8);
-    p.off_Ep = ws.take((int64_t)p.wgC * 8);
-    p.off_Gram = ws.take(3 * r * r * 8);
-    p.off_Gm = ws.take(r * r * 8);
-    p.off_small = ws.take(4 * 8);  // |X|^2, e_t
-    p.off_info = ws.take((I + 2) * 4);
-    p.off_scratch = ws.off;
+    WsCursor ws(workspace);
+    p.segs = ws.take<int4>(std::max<int64_t>(nseg, 1) * 16);
+    p.slab_seg = ws.take<int>((I + 1) * 4);
+    p.chunk_seg = ws.take<int>((int64_t)(p.nchunk + 1) * 4);
+    p.ext = ws.take<int>((I + 1) * 4);
+    p.bgrp = ws.take<int>((int64_t)(p.ngrp + 1) * 4);
+    p.A = ws.take<double>(I * r * 8);
+    p.B = ws.take<double>(p.Jm * r * 8);
+    p.C = ws.take<double>(K * r * 8);
+    p.Cfrag = ws.take<float>((int64_t)p.KH * p.NB * 64 * 4 * 4);
+    p.XC = ws.take<float>(p.N * r * 4);
+    p.Pa = ws.take<double>(std::max<int64_t>(nseg, 1) * r * 8);
+    p.Pb = ws.take<double>((int64_t)p.ngrp * p.Jm * r * 8);
+    p.Mb = ws.take<double>(p.Jm * r * 8);
+    p.Pc = ws.take<double>((int64_t)p.nchunk * K * r * 8);
+    p.Mc = ws.take<double>(K * r * 8);
+    p.Ma = ws.take<double>(I * r * 8);
+    p.Gp = ws.take<double>((int64_t)3 * wgmax * r * r * 8);
+    p.Ep = ws.take<double>((int64_t)p.wgC * 8);
+    p.Gram = ws.take<double>(3 * r * r * 8);
+    p.Gm = ws.take<double>(r * r * 8);
+    p.small = ws.take<double>(4 * 8);  // |X|^2, e_t
+    p.info = ws.take<int>((I + 2) * 4);
     // the start: mcl_svd_init's workspace + C0 (fp32), then P [Jmax, Jmax] + the subspace iteration's + B0 (fp32)
     p.svd_ws = (mcl_svd_stack_workspace_bytes(row_ptr, I, K, rank) + 255) & ~int64_t(255);
     p.gv_ws = (mcl_gram_vectors_workspace_bytes(p.Jm, rank) + 255) & ~int64_t(255);
-    const int64_t s1 = p.svd_ws + ((K * r * 4 + 255) & ~int64_t(255));
-    const int64_t s2 = ((p.Jm * p.Jm * 8 + 255) & ~int64_t(255)) + p.gv_ws + ((p.Jm * r * 4 + 255) & ~int64_t(255));
-    p.scratch = std::max(s1, s2);
-    p.total = ws.off + p.scratch;
+    const int64_t s1 = p.svd_ws + K * r * 4;
+    const int64_t s2 = ((p.Jm * p.Jm * 8 + 255) & ~int64_t(255)) + p.gv_ws + p.Jm * r * 4;
+    p.scratch = ws.take<char>(std::max(s1, s2));
+    p.total = ws.off;
     return p;
 }
 
@@ -410,53 +413,14 @@ void update(AlsUpd u, hipStream_t s) {
     else launch_update<64>(u, s);
 }
 
-template <class XL, int NB, bool VEC>
-void launch_passes(bool second, const typename XL::T *X, const AlsPlan &p, const int4 *segs, const int *chunk_seg, int K, int r,
-                   const float *Cfrag, const double *A64, const double *B64, float *XC, double *Pa, double *Pc, hipStream_t s) {
-    if (!second)
-        hipLaunchKernelGGL((k_als_xc<XL, NB, VEC>), dim3((unsigned)((p.nseg + 3) / 4)), dim3(256), 0, s, X, segs, p.nseg, K, r, Cfrag,
-                           B64, XC, Pa);
-    else
-        hipLaunchKernelGGL((k_als_xtw<XL, NB, VEC>), dim3((unsigned)p.nchunk, (unsigned)p.nkb), dim3(256), 0, s, X, segs, chunk_seg, K,
-                           r, A64, B64, Pc);
-}
-
-template <class XL, int NB>
-void passes_nb(bool second, bool vec, const typename XL::T *X, const AlsPlan &p, const int4 *segs, const int *chunk_seg, int K, int r,
-               const float *Cfrag, const double *A64, const double *B64, float *XC, double *Pa, double *Pc, hipStream_t s) {
-    if (vec) launch_passes<XL, NB, true>(second, X, p, segs, chunk_seg, K, r, Cfrag, A64, B64, XC, Pa, Pc, s);
-    else launch_passes<XL, NB, false>(second, X, p, segs, chunk_seg, K, r, Cfrag, A64, B64, XC, Pa, Pc, s);
-}
-
 template <class XL>
 int als_init(const typename XL::T *X, int32_t x_type, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank, int32_t method,
-             int32_t n_iter_max, double tol, float *A, float *B, float *C, double *errors, int32_t *info, void *workspace,
-             int64_t workspace_bytes, void *hip_stream) {
-    auto fail = [](const std::string &msg) {
-        g_als_error = msg;
-        return 1;
-    };
-    const AlsPlan p = als_plan(row_ptr, I, K, rank);
-    if (workspace_bytes < p.total) return fail("mcl_als_init: workspace too small (mcl_als_init_workspace_bytes)");
-    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail("mcl_als_init: workspace must be 256-byte aligned");
-    hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
-    char *ws = static_cast<char *>(workspace);
-    auto at = [&](int64_t off) { return static_cast<void *>(ws + off); };
-    int4 *segs = static_cast<int4 *>(at(p.off_segs));
-    int *slab_seg = static_cast<int *>(at(p.off_slab_seg)), *chunk_seg = static_cast<int *>(at(p.off_chunk_seg));
-    int *ext = static_cast<int *>(at(p.off_ext)), *bgrp = static_cast<int *>(at(p.off_bgrp));
-    double *A64 = static_cast<double *>(at(p.off_A)), *B64 = static_cast<double *>(at(p.off_B)), *C64 = static_cast<double *>(at(p.off_C));
-    float *Cfrag = static_cast<float *>(at(p.off_Cfrag)), *XC = static_cast<float *>(at(p.off_XC));
-    double *Pa = static_cast<double *>(at(p.off_Pa)), *Pb = static_cast<double *>(at(p.off_Pb)), *Mb = static_cast<double *>(at(p.off_Mb));
-    double *Pc = static_cast<double *>(at(p.off_Pc)), *Mc = static_cast<double *>(at(p.off_Mc)), *Ma = static_cast<double *>(at(p.off_Ma));
-    double *Gp = static_cast<double *>(at(p.off_Gp)), *Ep = static_cast<double *>(at(p.off_Ep));
-    double *Gram = static_cast<double *>(at(p.off_Gram)), *Gm = static_cast<double *>(at(p.off_Gm));
-    double *nx2 = static_cast<double *>(at(p.off_small)), *ews = nx2 + 1;
-    int *sinfo = static_cast<int *>(at(p.off_info));
-    char *scr = ws + p.off_scratch;
+             int32_t n_iter_max, double tol, float *A, float *B, float *C, double *errors, int32_t *info, const AlsPlan &p, hipStream_t s) {
+    auto fail = [](const std::string &msg) { return g_als_error.as_is(msg); };  // (a HIP call's or the svd start's message)
+    double *nx2 = p.small, *ews = nx2 + 1;
     const int r = rank, Jm = (int)p.Jm, N = (int)p.N;
     const int wgmax = std::max(p.wgA, std::max(p.wgB, p.wgC));
-    double *GpM[3] = {Gp, Gp + (int64_t)wgmax * r * r, Gp + (int64_t)2 * wgmax * r * r};
+    double *GpM[3] = {p.Gp, p.Gp + (int64_t)wgmax * r * r, p.Gp + (int64_t)2 * wgmax * r * r};
     const int nwg[3] = {p.wgA, p.wgB, p.wgC};
 
     // host-built tables: segments, per-slab segment ranges, row chunks of pass 2, slab groups of M_B
@@ -465,34 +429,32 @@ int als_init(const typename XL::T *X, int32_t x_type, const int64_t *row_ptr, in
     if (h.segs.empty()) h.segs.push_back(int4{0, 0, 0, 0});
     for (int c = 0; c <= p.nchunk; ++c) h_chunk[(size_t)c] = (int)((int64_t)p.nseg * c / p.nchunk);
     for (int g = 0; g <= p.ngrp; ++g) h_bgrp[(size_t)g] = (int)(I * g / p.ngrp);
-    CP_HIP(hipMemcpyAsync(segs, h.segs.data(), sizeof(int4) * h.segs.size(), hipMemcpyHostToDevice, s));
-    CP_HIP(hipMemcpyAsync(slab_seg, h.slab_seg.data(), sizeof(int) * h.slab_seg.size(), hipMemcpyHostToDevice, s));
-    CP_HIP(hipMemcpyAsync(ext, h.ext.data(), sizeof(int) * h.ext.size(), hipMemcpyHostToDevice, s));
-    CP_HIP(hipMemcpyAsync(chunk_seg, h_chunk.data(), sizeof(int) * h_chunk.size(), hipMemcpyHostToDevice, s));
-    CP_HIP(hipMemcpyAsync(bgrp, h_bgrp.data(), sizeof(int) * h_bgrp.size(), hipMemcpyHostToDevice, s));
-    CP_HIP(hipMemsetAsync(Cfrag, 0, (size_t)p.KH * p.NB * 64 * 4 * 4, s));
+    CP_HIP(upload_tables(h, p.segs, p.slab_seg, p.ext, s));
+    CP_HIP(upload(p.chunk_seg, h_chunk, s));
+    CP_HIP(upload(p.bgrp, h_bgrp, s));
+    CP_HIP(hipMemsetAsync(p.Cfrag, 0, (size_t)p.KH * p.NB * 64 * 4 * 4, s));
     CP_HIP(hipStreamSynchronize(s));  // (the tables are locals)
 
     const int hals = method == MCL_ALS_CP_HALS;
     // ---- start.  C0: the C of mcl_svd_init
-    float *C32 = reinterpret_cast<float *>(scr + p.svd_ws);
+    float *C32 = reinterpret_cast<float *>(p.scratch + p.svd_ws);
     std::string err;
-    if (mcl_svd_stack_right(X, x_type, row_ptr, I, K, rank, hals, C32, scr, p.svd_ws, sinfo, s, err)) return fail(err);
+    if (mcl_svd_stack_right(X, x_type, row_ptr, I, K, rank, hals, C32, p.scratch, p.svd_ws, p.info, s, err)) return fail(err);
     AlsUpd u{};
     u.r = r, u.NB = p.NB, u.op = OP_LOAD;
-    u.mode = 2, u.n = (int)K, u.F32 = C32, u.F64 = C64, u.Gp = GpM[2], u.Ep = Ep, u.Cfrag = Cfrag;
+    u.mode = 2, u.n = (int)K, u.F32 = C32, u.F64 = p.C, u.Gp = GpM[2], u.Ep = p.Ep, u.Cfrag = p.Cfrag;
     update(u, s);
     // B0: the leading eigenvectors of the padded-row Gram matrix
-    double *P = reinterpret_cast<double *>(scr);
-    char *gv = scr + ((p.Jm * p.Jm * 8 + 255) & ~int64_t(255));
+    double *P = reinterpret_cast<double *>(p.scratch);
+    char *gv = p.scratch + ((p.Jm * p.Jm * 8 + 255) & ~int64_t(255));
     float *B32 = reinterpret_cast<float *>(gv + p.gv_ws);
     const unsigned tj = (unsigned)((Jm + 31) / 32);
-    hipLaunchKernelGGL(k_als_rowgram<XL>, dim3(tj, tj), dim3(256), 0, s, X, (const int *)ext, (int)I, (int)K, Jm, P);
+    hipLaunchKernelGGL(k_als_rowgram<XL>, dim3(tj, tj), dim3(256), 0, s, X, (const int *)p.ext, (int)I, (int)K, Jm, P);
     hipLaunchKernelGGL(k_als_trace, dim3(1), dim3(64), 0, s, (const double *)P, Jm, nx2);
-    if (mcl_gram_vectors(P, p.Jm, rank, hals, B32, gv, sinfo, (int)I + 1, s, err)) return fail(err);
-    u.mode = 1, u.n = Jm, u.F32 = B32, u.F64 = B64, u.Gp = GpM[1];
+    if (mcl_gram_vectors(P, p.Jm, rank, hals, B32, gv, p.info, (int)I + 1, s, err)) return fail(err);
+    u.mode = 1, u.n = Jm, u.F32 = B32, u.F64 = p.B, u.Gp = GpM[1];
     update(u, s);
-    u.mode = 0, u.n = (int)I, u.F32 = nullptr, u.F64 = A64, u.Gp = GpM[0];  // A0 = 1
+    u.mode = 0, u.n = (int)I, u.F32 = nullptr, u.F64 = p.A, u.Gp = GpM[0];  // A0 = 1
     update(u, s);
 
     const int rr = r * r;
@@ -501,7 +463,7 @@ int als_init(const typename XL::T *X, int32_t x_type, const int64_t *row_ptr, in
     auto prep = [&](int prev, int next, int t) {
         AlsPrep q{};
         q.prev = prev, q.nprev = prev >= 0 ? nwg[prev] : 0, q.next = next, q.method = hals, q.t = t, q.r = r, q.nEp = p.wgC;
-        q.Gp = prev >= 0 ? GpM[prev] : nullptr, q.Gram = Gram, q.Gm = Gm, q.Ep = Ep, q.nx2 = nx2, q.ews = ews, q.errors = errors;
+        q.Gp = prev >= 0 ? GpM[prev] : nullptr, q.Gram = p.Gram, q.Gm = p.Gm, q.Ep = p.Ep, q.nx2 = nx2, q.ews = ews, q.errors = errors;
         hipLaunchKernelGGL(k_als_prep, dim3(1), dim3(256), psm, s, q);
     };
     prep(1, -1, -1);
@@ -510,34 +472,46 @@ int als_init(const typename XL::T *X, int32_t x_type, const int64_t *row_ptr, in
     CP_HIP(hipGetLastError());
 
     const bool vec = K % 4 == 0 && mcl_x_vec_aligned(X, x_type);
+    auto pass_nb = [&](bool second, auto nb) {  // XC and the M_A partials, or the M_C partials
+        vec_dispatch(vec, [&](auto v) {
+            constexpr int NB = decltype(nb)::value;
+            constexpr bool VEC = decltype(v)::value;
+            if (!second)
+                hipLaunchKernelGGL((k_als_xc<XL, NB, VEC>), dim3((unsigned)((p.nseg + 3) / 4)), dim3(256), 0, s, X, (const int4 *)p.segs, p.nseg,
+                                   (int)K, r, (const float *)p.Cfrag, (const double *)p.B, p.XC, p.Pa);
+            else
+                hipLaunchKernelGGL((k_als_xtw<XL, NB, VEC>), dim3((unsigned)p.nchunk, (unsigned)p.nkb), dim3(256), 0, s, X, (const int4 *)p.segs,
+                                   (const int *)p.chunk_seg, (int)K, r, (const double *)p.A, (const double *)p.B, p.Pc);
+        });
+    };
     auto pass = [&](bool second) {
-        if (p.NB == 1) passes_nb<XL, 1>(second, vec, X, p, segs, chunk_seg, (int)K, r, Cfrag, A64, B64, XC, Pa, Pc, s);
-        else if (p.NB == 2) passes_nb<XL, 2>(second, vec, X, p, segs, chunk_seg, (int)K, r, Cfrag, A64, B64, XC, Pa, Pc, s);
-        else passes_nb<XL, 4>(second, vec, X, p, segs, chunk_seg, (int)K, r, Cfrag, A64, B64, XC, Pa, Pc, s);
+        if (p.NB == 1) pass_nb(second, std::integral_constant<int, 1>{});
+        else if (p.NB == 2) pass_nb(second, std::integral_constant<int, 2>{});
+        else pass_nb(second, std::integral_constant<int, 4>{});
     };
     const int op = hals ? OP_HALS : OP_ALS;
     double e_prev = 0.0;
     int used = 0;
     for (int t = 0; t < n_iter_max; ++t) {
-        pass(false);  // XC, M_A partials
+        pass(false);
         u = AlsUpd{};
-        u.r = r, u.NB = p.NB, u.op = op, u.Gm = Gm, u.Ep = Ep, u.Cfrag = Cfrag;
-        hipLaunchKernelGGL(k_als_segsum, dim3((unsigned)((I * r + 255) / 256)), dim3(256), 0, s, (const double *)Pa, (const int *)slab_seg,
-                           (int)I, r, Ma);
-        u.mode = 0, u.n = (int)I, u.M = Ma, u.F64 = A64, u.Gp = GpM[0];
+        u.r = r, u.NB = p.NB, u.op = op, u.Gm = p.Gm, u.Ep = p.Ep, u.Cfrag = p.Cfrag;
+        hipLaunchKernelGGL(k_als_segsum, dim3((unsigned)((I * r + 255) / 256)), dim3(256), 0, s, (const double *)p.Pa, (const int *)p.slab_seg,
+                           (int)I, r, p.Ma);
+        u.mode = 0, u.n = (int)I, u.M = p.Ma, u.F64 = p.A, u.Gp = GpM[0];
         update(u, s);
         const long EB = (long)Jm * r;
-        hipLaunchKernelGGL(k_als_mb, dim3((unsigned)((EB * p.ngrp + 255) / 256)), dim3(256), 0, s, (const float *)XC, (const double *)A64,
-                           (const int *)ext, (const int *)bgrp, p.ngrp, Jm, r, Pb);
-        hipLaunchKernelGGL(k_als_reduce, dim3((unsigned)((EB + 63) / 64)), dim3(256), 0, s, (const double *)Pb, p.ngrp, EB, Mb);
+        hipLaunchKernelGGL(k_als_mb, dim3((unsigned)((EB * p.ngrp + 255) / 256)), dim3(256), 0, s, (const float *)p.XC, (const double *)p.A,
+                           (const int *)p.ext, (const int *)p.bgrp, p.ngrp, Jm, r, p.Pb);
+        hipLaunchKernelGGL(k_als_reduce, dim3((unsigned)((EB + 63) / 64)), dim3(256), 0, s, (const double *)p.Pb, p.ngrp, EB, p.Mb);
         prep(0, 1, -1);
-        u.mode = 1, u.n = Jm, u.M = Mb, u.F64 = B64, u.Gp = GpM[1];
+        u.mode = 1, u.n = Jm, u.M = p.Mb, u.F64 = p.B, u.Gp = GpM[1];
         update(u, s);
         prep(1, 2, -1);
-        pass(true);  // M_C partials
+        pass(true);
         const long EC = (long)K * r;
-        hipLaunchKernelGGL(k_als_reduce, dim3((unsigned)((EC + 63) / 64)), dim3(256), 0, s, (const double *)Pc, p.nchunk, EC, Mc);
-        u.mode = 2, u.n = (int)K, u.M = Mc, u.F64 = C64, u.Gp = GpM[2];
+        hipLaunchKernelGGL(k_als_reduce, dim3((unsigned)((EC + 63) / 64)), dim3(256), 0, s, (const double *)p.Pc, p.nchunk, EC, p.Mc);
+        u.mode = 2, u.n = (int)K, u.M = p.Mc, u.F64 = p.C, u.Gp = GpM[2];
         update(u, s);
         prep(2, 0, t);
         CP_HIP(hipGetLastError());
@@ -551,17 +525,18 @@ int als_init(const typename XL::T *X, int32_t x_type, const int64_t *row_ptr, in
         }
     }
     const long big = std::max<long>((long)N, std::max<long>((long)I, (long)K)) * r;
-    hipLaunchKernelGGL(k_als_out, dim3((unsigned)((big + 255) / 256), 3), dim3(256), 0, s, (const double *)A64, (const double *)B64,
-                       (const double *)C64, (const int *)ext, (int)I, N, (int)K, r, A, B, C);
+    hipLaunchKernelGGL(k_als_out, dim3((unsigned)((big + 255) / 256), 3), dim3(256), 0, s, (const double *)p.A, (const double *)p.B,
+                       (const double *)p.C, (const int *)p.ext, (int)I, N, (int)K, r, A, B, C);
     CP_HIP(hipGetLastError());
     CP_HIP(hipMemcpyAsync(info, &used, sizeof(int32_t), hipMemcpyHostToDevice, s));
     CP_HIP(hipStreamSynchronize(s));  // (`used` is a local)
     return 0;
 }
 
+// (a matrix may have fewer rows than the rank: the padded tensor has Jmax rows in every slab)
 std::string check_args(const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank) {
-    if (!row_ptr || I < 1 || K < 1) return "need row_ptr, I >= 1, K >= 1";
-    if (rank < 1 || rank > MCL_MAX_RANK) return "need 1 <= rank <= 64";
+    const std::string bad = packed_args_error(row_ptr, I, K, rank, MCL_MAX_RANK);
+    if (!bad.empty()) return bad;
     if (row_ptr[0] != 0) return "row_ptr[0] must be 0";
     int64_t Jm = 0;
     for (int64_t i = 0; i < I; ++i) {
@@ -582,37 +557,27 @@ const char *mcl_als_init_last_error(void) { return g_als_error.c_str(); }
 
 int64_t mcl_als_init_workspace_bytes(const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank) {
     if (!check_args(row_ptr, I, K, rank).empty()) return -1;
-    return als_plan(row_ptr, I, K, rank).total;
+    return als_plan(nullptr, row_ptr, I, K, rank).total;
 }
 
 int mcl_als_init_typed(const void *X, int32_t x_type, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank, int32_t method,
                        int32_t n_iter_max, double tol, float *A, float *B, float *C, double *errors, int32_t *info, void *workspace,
                        int64_t workspace_bytes, void *hip_stream) {
+    ErrorSlot &fail = g_als_error;
     const std::string bad = check_args(row_ptr, I, K, rank);
-    if (!bad.empty()) {
-        g_als_error = "mcl_als_init: " + bad;
-        return 1;
-    }
-    if (!X || !A || !B || !C || !info || !workspace) {
-        g_als_error = "mcl_als_init: NULL argument";
-        return 1;
-    }
-    if (!x_type_error(x_type).empty()) {
-        g_als_error = "mcl_als_init: " + x_type_error(x_type);
-        return 1;
-    }
-    if (method != MCL_ALS_CP && method != MCL_ALS_CP_HALS) {
-        g_als_error = "mcl_als_init: unknown method " + std::to_string(method) + " (MCL_ALS_CP = 0, MCL_ALS_CP_HALS = 1)";
-        return 1;
-    }
-    if (n_iter_max < 0 || !(tol >= 0.0)) {
-        g_als_error = "mcl_als_init: need n_iter_max >= 0 and tol >= 0";
-        return 1;
-    }
+    if (!bad.empty()) return fail(bad);
+    if (!X || !A || !B || !C || !info || !workspace) return fail("NULL argument");
+    if (!x_type_error(x_type).empty()) return fail(x_type_error(x_type));
+    if (method != MCL_ALS_CP && method != MCL_ALS_CP_HALS)
+        return fail("unknown method " + std::to_string(method) + " (MCL_ALS_CP = 0, MCL_ALS_CP_HALS = 1)");
+    if (n_iter_max < 0 || !(tol >= 0.0)) return fail("need n_iter_max >= 0 and tol >= 0");
+    const AlsPlan p = als_plan(workspace, row_ptr, I, K, rank);
+    if (workspace_refused(fail, workspace, workspace_bytes, p.total, "mcl_als_init_workspace_bytes")) return 1;
+    hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
     return mcl_x_dispatch(x_type, [&](auto xl) {
         using XL = decltype(xl);
-        return als_init<XL>(static_cast<const typename XL::T *>(X), x_type, row_ptr, I, K, rank, method, n_iter_max, tol, A, B, C, errors,
-                            info, workspace, workspace_bytes, hip_stream);
+        return als_init<XL>(static_cast<const typename XL::T *>(X), x_type, row_ptr, I, K, rank, method, n_iter_max, tol, A, B, C, errors, info,
+                            p, s);
     });
 }
 

@@ -1,20 +1,19 @@
 // What the CP initialisers (alsinit.hip) and parafac2_als (parafac2als.hip) share: the two passes over X on the fp32 MFMA, the
-// fragment layout of C they multiply with, the r x r algebra of a mode's update, the fixed-order sum of fp64 partials, and the
-// host tables that drive the passes.  The layout decisions of both kernel families are here and nowhere else: the LDS swizzle
-// of pass 1, the address of C[k][s] in Cfrag, the order of the wave sum of pass 2 and of the partial sums (two runs are
-// bitwise equal because of them), the 1e-12 eigenvalue cut of the pseudo-inverse.  What differs between the callers comes in
-// as a callable (the weights of pass 2, the sink of its sums, the entries of G).
+// fragment layout of C they multiply with, the r x r algebra of a mode's update, the fixed-order sum of fp64 partials.  The
+// layout decisions of both kernel families are here and nowhere else: the LDS swizzle of pass 1, the address of C[k][s] in
+// Cfrag, the order of the wave sum of pass 2 and of the partial sums (two runs are bitwise equal because of them), the 1e-12
+// eigenvalue cut of the pseudo-inverse.  What differs between the callers comes in as a callable (the weights of pass 2, the
+// sink of its sums, the entries of G).  The host tables that drive the passes (segments of CP_SEG rows) are in entry_host.h.
 #pragma once
 #include <algorithm>
 #include <string>
 #include <vector>
 
+#include "entry_host.h"
 #include "mcl_internal.h"
 #include "rows_mfma.h"
 #include "symeig_lds.h"
 #include "xload.h"
-
-constexpr int CP_SEG = 64;  // rows of one slab per segment (one wave of pass 1)
 
 // four consecutive elements of X as fp32, zero past column K (VEC: K % 4 == 0 and an aligned base)
 template <class XL, bool VEC>
@@ -283,51 +282,3 @@ static __device__ __forceinline__ int slab_of_row(const int *ext, int I, int row
     }
     return lo;
 }
-
-// ---- host side --------------------------------------------------------------------------------------------------------------
-// the tables the passes walk: segs = {slab, first packed row, rows, first row in slab} per segment of <= CP_SEG rows, the
-// segments of slab i = [slab_seg[i], slab_seg[i + 1]), ext = row_ptr as int
-struct SegTables {
-    std::vector<int4> segs;
-    std::vector<int> slab_seg, ext;
-};
-static inline SegTables seg_tables(const int64_t *row_ptr, int64_t I) {
-    SegTables t;
-    t.slab_seg.assign(1, 0);
-    t.ext.resize((size_t)I + 1);
-    for (int64_t i = 0; i < I; ++i) {
-        const int J = (int)(row_ptr[i + 1] - row_ptr[i]);
-        for (int j0 = 0; j0 < J; j0 += CP_SEG) t.segs.push_back(int4{(int)i, (int)row_ptr[i] + j0, std::min(CP_SEG, J - j0), j0});
-        t.slab_seg.push_back((int)t.segs.size());
-    }
-    for (int64_t i = 0; i <= I; ++i) t.ext[(size_t)i] = (int)row_ptr[i];
-    return t;
-}
-static inline int64_t seg_count(const int64_t *row_ptr, int64_t I) {
-    int64_t nseg = 0;
-    for (int64_t i = 0; i < I; ++i) nseg += (row_ptr[i + 1] - row_ptr[i] + CP_SEG - 1) / CP_SEG;
-    return nseg;
-}
-
-// offsets of a workspace's parts: every part starts on a 256-byte boundary and has at least one byte
-struct WsCursor {
-    int64_t off = 0;
-    int64_t take(int64_t bytes) {
-        const int64_t o = off;
-        off = (off + std::max<int64_t>(bytes, 1) + 255) & ~int64_t(255);
-        return o;
-    }
-};
-
-// "" for a known element type of X, else the message the entry points report after their own name
-static inline std::string x_type_error(int32_t x_type) {
-    if (x_type == MCL_X_F32 || x_type == MCL_X_BF16 || x_type == MCL_X_F16) return "";
-    return "unknown x_type " + std::to_string(x_type) + " (MCL_X_F32 = 0, MCL_X_BF16 = 1, MCL_X_F16 = 2)";
-}
-
-// returns fail(message) from the enclosing function (a `fail` in scope) when a HIP call does not succeed
-#define CP_HIP(expr)                                                                    \
-    do {                                                                                \
-        const hipError_t e_ = (expr);                                                   \
-        if (e_ != hipSuccess) return fail(std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)

@@ -25,7 +25,7 @@
 
 namespace {
 
-static std::string g_eval_error;
+static ErrorSlot g_eval_error;
 constexpr int EV_MAX_RANK = 32;
 typedef double ev_f64x4 __attribute__((ext_vector_type(4)));
 
@@ -290,23 +290,28 @@ __global__ __launch_bounds__(RMAX * RMAX) void k_eval_core(const double *__restr
 struct EvPlan {
     int nseg, nwg, KC, NB;
     int64_t cper;  // floats of one model's Cfrag (and of its Cmod)
-    int64_t off_segs, off_slab_seg, off_cfrag, off_cmod, off_part, total;
+    int4 *segs;
+    int *slab_seg;
+    float *Cfrag, *Cmod;
+    double *part;
+    int64_t total;
 };
 
-EvPlan ev_plan(const int64_t *row_ptr, int64_t I, int64_t K, int rank, int64_t n_models) {
+// ws NULL: the parts are null and `total` is the size (mcl_eval_workspace_bytes)
+EvPlan ev_plan(void *ws, const int64_t *row_ptr, int64_t I, int64_t K, int rank, int64_t n_models) {
     EvPlan p{};
     p.nseg = (int)seg_count(row_ptr, I);
     p.nwg = (p.nseg + 3) / 4;
     p.KC = (int)((K + 63) / 64);
     p.NB = rank <= 16 ? 1 : 2;
     p.cper = (int64_t)p.KC * 64 * 16 * p.NB;
-    WsCursor ws;
-    p.off_segs = ws.take((int64_t)p.nseg * 16);
-    p.off_slab_seg = ws.take((I + 1) * 4);
-    p.off_cfrag = ws.take(n_models * p.cper * 4);
-    p.off_cmod = ws.take(n_models * p.cper * 4);
-    p.off_part = ws.take(n_models * p.nseg * (2 * (int64_t)rank * rank + 2) * 8);
-    p.total = ws.off;
+    WsCursor c(ws);
+    p.segs = c.take<int4>((int64_t)p.nseg * 16);
+    p.slab_seg = c.take<int>((I + 1) * 4);
+    p.Cfrag = c.take<float>(n_models * p.cper * 4);
+    p.Cmod = c.take<float>(n_models * p.cper * 4);
+    p.part = c.take<double>(n_models * p.nseg * (2 * (int64_t)rank * rank + 2) * 8);
+    p.total = c.off;
     return p;
 }
 
@@ -349,31 +354,20 @@ std::string ev_models_finite(const double *models, int64_t n_models, int64_t len
 
 template <class XL, int NB>
 int ev_tables(const typename XL::T *X, int32_t x_type, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank, const double *models,
-              int64_t n_models, double *S, double *BtB, double *sse, double *norm, char *ws, const EvPlan &p, hipStream_t s) {
-    auto fail = [](const std::string &m) {
-        g_eval_error = "mcl_eval_tables_typed: " + m;
-        return 1;
-    };
-    int4 *segs = reinterpret_cast<int4 *>(ws + p.off_segs);
-    int *slab_seg = reinterpret_cast<int *>(ws + p.off_slab_seg);
-    float *Cfrag = reinterpret_cast<float *>(ws + p.off_cfrag), *Cmod = reinterpret_cast<float *>(ws + p.off_cmod);
-    double *part = reinterpret_cast<double *>(ws + p.off_part);
+              int64_t n_models, double *S, double *BtB, double *sse, double *norm, const EvPlan &p, hipStream_t s) {
+    ErrorSlot &fail = g_eval_error;
     const SegTables h = seg_tables(row_ptr, I);
-    CP_HIP(hipMemcpyAsync(segs, h.segs.data(), sizeof(int4) * h.segs.size(), hipMemcpyHostToDevice, s));
-    CP_HIP(hipMemcpyAsync(slab_seg, h.slab_seg.data(), sizeof(int) * h.slab_seg.size(), hipMemcpyHostToDevice, s));
+    CP_HIP(upload_tables(h, p.segs, p.slab_seg, nullptr, s));
     CP_HIP(hipStreamSynchronize(s));  // (the tables are locals)
     const int64_t N = row_ptr[I];
     const long len = (long)(I + N + K) * rank;
     hipLaunchKernelGGL(k_eval_prep<NB>, dim3((unsigned)((p.cper + 255) / 256), (unsigned)n_models), dim3(256), 0, s, models, len,
-                       (long)(I + N) * rank, (int)K, (int)rank, p.KC, Cfrag, Cmod);
-    const dim3 grid((unsigned)(p.nwg * n_models));
-    if (K % 4 == 0 && mcl_x_vec_aligned(X, x_type))
-        hipLaunchKernelGGL((k_eval_tables<XL, NB, true>), grid, dim3(256), 0, s, X, (const int4 *)segs, p.nseg, p.nwg, (int)K, (int)rank, (int)I,
-                           models, len, (const float *)Cfrag, (const float *)Cmod, (long)p.cper, part);
-    else
-        hipLaunchKernelGGL((k_eval_tables<XL, NB, false>), grid, dim3(256), 0, s, X, (const int4 *)segs, p.nseg, p.nwg, (int)K, (int)rank, (int)I,
-                           models, len, (const float *)Cfrag, (const float *)Cmod, (long)p.cper, part);
-    hipLaunchKernelGGL(k_eval_reduce, dim3((unsigned)I, (unsigned)n_models), dim3(256), 0, s, (const double *)part, (const int *)slab_seg, p.nseg,
+                       (long)(I + N) * rank, (int)K, (int)rank, p.KC, p.Cfrag, p.Cmod);
+    vec_dispatch(K % 4 == 0 && mcl_x_vec_aligned(X, x_type), [&](auto vec) {
+        hipLaunchKernelGGL((k_eval_tables<XL, NB, decltype(vec)::value>), dim3((unsigned)(p.nwg * n_models)), dim3(256), 0, s, X, (const int4 *)p.segs,
+                           p.nseg, p.nwg, (int)K, (int)rank, (int)I, models, len, (const float *)p.Cfrag, (const float *)p.Cmod, (long)p.cper, p.part);
+    });
+    hipLaunchKernelGGL(k_eval_reduce, dim3((unsigned)I, (unsigned)n_models), dim3(256), 0, s, (const double *)p.part, (const int *)p.slab_seg, p.nseg,
                        (int)I, (int)rank, S, BtB, sse, norm);
     CP_HIP(hipGetLastError());
     return 0;
@@ -387,39 +381,33 @@ const char *mcl_eval_last_error(void) { return g_eval_error.c_str(); }
 
 int64_t mcl_eval_workspace_bytes(const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank, int64_t n_models) {
     if (!ev_check(row_ptr, I, K, rank, n_models).empty()) return -1;
-    return ev_plan(row_ptr, I, K, rank, n_models).total;
+    return ev_plan(nullptr, row_ptr, I, K, rank, n_models).total;
 }
 
 int mcl_eval_tables_typed(const void *X, int32_t x_type, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank, const double *models,
                           int64_t n_models, double *S, double *BtB, double *sse, double *norm, void *ws, int64_t ws_bytes, void *stream) {
-    auto fail = [](const std::string &m) {
-        g_eval_error = "mcl_eval_tables_typed: " + m;
-        return 1;
-    };
+    ErrorSlot &fail = g_eval_error.named("mcl_eval_tables_typed: ");
     const std::string bad = ev_check(row_ptr, I, K, rank, n_models);
     if (!bad.empty()) return fail(bad);
     if (!x_type_error(x_type).empty()) return fail(x_type_error(x_type));
     if (!X || !models || !S || !BtB || !sse || !norm || !ws) return fail("NULL argument");
-    const EvPlan p = ev_plan(row_ptr, I, K, rank, n_models);
-    if (ws_bytes < p.total) return fail("workspace too small (mcl_eval_workspace_bytes)");
-    if (reinterpret_cast<uintptr_t>(ws) & 255) return fail("workspace must be 256-byte aligned");
+    const EvPlan p = ev_plan(ws, row_ptr, I, K, rank, n_models);
+    if (workspace_refused(fail, ws, ws_bytes, p.total, "mcl_eval_workspace_bytes")) return 1;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const std::string inf = ev_models_finite(models, n_models, (I + row_ptr[I] + K) * rank, s);
     if (!inf.empty()) return fail(inf);
     return mcl_x_dispatch(x_type, [&](auto xl) {
         using XL = decltype(xl);
-        const auto *Xt = static_cast<const typename XL::T *>(X);
-        if (rank <= 16) return ev_tables<XL, 1>(Xt, x_type, row_ptr, I, K, rank, models, n_models, S, BtB, sse, norm, static_cast<char *>(ws), p, s);
-        return ev_tables<XL, 2>(Xt, x_type, row_ptr, I, K, rank, models, n_models, S, BtB, sse, norm, static_cast<char *>(ws), p, s);
+        return rank_bucket(rank, [&](auto rmax) {
+            return ev_tables<XL, decltype(rmax)::value / 16>(static_cast<const typename XL::T *>(X), x_type, row_ptr, I, K, rank, models, n_models,
+                                                            S, BtB, sse, norm, p, s);
+        });
     });
 }
 
 int mcl_eval_core(const double *models, int64_t n_models, int64_t I, int64_t N, int64_t K, int32_t rank, const double *S, const double *BtB,
                   double *core, double *cc, double *cc_normalised, void *stream) {
-    auto fail = [](const std::string &m) {
-        g_eval_error = "mcl_eval_core: " + m;
-        return 1;
-    };
+    ErrorSlot &fail = g_eval_error.named("mcl_eval_core: ");
     const std::string bad = ev_check_shape(I, K, rank, n_models);
     if (!bad.empty()) return fail(bad);
     if (N < I || N >= (int64_t(1) << 31) / EV_MAX_RANK) return fail("need I <= N < 2^26 packed rows");
@@ -428,12 +416,12 @@ int mcl_eval_core(const double *models, int64_t n_models, int64_t I, int64_t N, 
     const long len = (long)(I + N + K) * rank;
     const std::string inf = ev_models_finite(models, n_models, len, s);
     if (!inf.empty()) return fail(inf);
-    if (rank <= 16)
-        hipLaunchKernelGGL(k_eval_core<16>, dim3((unsigned)n_models), dim3(256), 0, s, models, len, (int)I, (long)N, (int)K, (int)rank, S, BtB,
-                           core, cc, cc_normalised);
-    else
-        hipLaunchKernelGGL(k_eval_core<32>, dim3((unsigned)n_models), dim3(1024), 0, s, models, len, (int)I, (long)N, (int)K, (int)rank, S, BtB,
-                           core, cc, cc_normalised);
+    rank_bucket(rank, [&](auto rmax) {
+        constexpr int RMAX = decltype(rmax)::value;
+        hipLaunchKernelGGL(k_eval_core<RMAX>, dim3((unsigned)n_models), dim3(RMAX * RMAX), 0, s, models, len, (int)I, (long)N, (int)K,
+                           (int)rank, S, BtB, core, cc, cc_normalised);
+        return 0;
+    });
     CP_HIP(hipGetLastError());
     return 0;
 }

@@ -33,13 +33,14 @@
 #include <string>
 #include <vector>
 
+#include "entry_host.h"
 #include "mcl_internal.h"
 #include "wg_fp64.h"
 #include "xload.h"
 
 namespace {
 
-static std::string g_ms_error;
+static ErrorSlot g_ms_error;
 constexpr int MS_MAX_RANK = 16;
 constexpr int MS_SYS_BYTES = 40960;  // LDS for a batch of r x r systems (two r x r matrices per thread)
 
@@ -735,11 +736,6 @@ __global__ __launch_bounds__(MS_THREADS) void k_multistart_weighted(MsArgs a0, c
 }
 #undef MS_START
 
-struct MsPlan {
-    int64_t N, state_len, scratch_len, off_rowptr, off_slab, off_scratch, total;
-    int64_t off_aux[3][MCL_MAX_REGS], off_dual[3][MCL_MAX_REGS], off_delta[3][MCL_MAX_REGS];
-};
-
 std::string ms_check(const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank, const mcl_multistart_options *o, int32_t n_starts) {
     if (!row_ptr || !o || I < 1 || K < 1) return "need row_ptr, options, I >= 1, K >= 1";
     if (rank < 1 || rank > MS_MAX_RANK) return "need 1 <= rank <= 16";
@@ -769,47 +765,26 @@ std::string ms_check(const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank,
     return "";
 }
 
-MsPlan ms_plan(const int64_t *row_ptr, int64_t I, int64_t K, int rank, const mcl_multistart_options *o, int32_t n_starts) {
-    MsPlan p{};
-    p.N = row_ptr[I];
-    const int64_t r = rank, rows[3] = {I, p.N, K};
-    int64_t off = (I + p.N + K) * r;
+// the state slice of one start, in doubles: A, B, C, then aux (+ Delta for PARAFAC2) and dual of every penalty
+void ms_state_layout(MsArgs &a, int rank, const mcl_multistart_options *o) {
+    const int64_t r = rank, rows[3] = {a.I, a.N, a.K};
+    int64_t off = (a.I + a.N + a.K) * r;
     for (int m = 0; m < 3; ++m)
         for (int k = 0; k < o->n_regs[m]; ++k) {
-            p.off_aux[m][k] = off;
+            a.off_aux[m][k] = off;
             off += rows[m] * r;
             if (o->regs[m][k].kind == MCL_PEN_PARAFAC2) {
-                p.off_delta[m][k] = off;
+                a.off_delta[m][k] = off;
                 off += r * r;
             }
-            p.off_dual[m][k] = off;
+            a.off_dual[m][k] = off;
             off += rows[m] * r;
         }
-    p.state_len = off;
-    p.scratch_len = ms_scratch(I, p.N, K, rank).total;
-    auto al = [](int64_t b) { return (b + 255) & ~int64_t(255); };
-    p.off_rowptr = 0;
-    p.off_slab = al((I + 1) * 8);
-    p.off_scratch = p.off_slab + al(p.N * 4);
-    p.total = p.off_scratch + al(p.scratch_len * 8 * int64_t(n_starts));
-    return p;
+    a.state_len = off;
 }
 
-template <class XL, int R>
-void launch(const MsArgs &a, int n_starts, const double *slab_weight, hipStream_t s) {
-    if (slab_weight) hipLaunchKernelGGL((k_multistart_weighted<R, XL>), dim3(n_starts), dim3(MS_THREADS), 0, s, a, slab_weight);
-    else hipLaunchKernelGGL((k_multistart<R, XL>), dim3(n_starts), dim3(MS_THREADS), 0, s, a);
-}
-
-template <class XL>
-void launch_rank(int rank, const MsArgs &a, int n_starts, const double *slab_weight, hipStream_t s) {
-    switch (rank) {
-#define MS_CASE(R) \
-    case R: launch<XL, R>(a, n_starts, slab_weight, s); break;
-        MS_CASE(1) MS_CASE(2) MS_CASE(3) MS_CASE(4) MS_CASE(5) MS_CASE(6) MS_CASE(7) MS_CASE(8)
-        MS_CASE(9) MS_CASE(10) MS_CASE(11) MS_CASE(12) MS_CASE(13) MS_CASE(14) MS_CASE(15) MS_CASE(16)
-#undef MS_CASE
-    }
+StartsPlan ms_plan(void *workspace, const int64_t *row_ptr, int64_t I, int64_t K, int rank, int32_t n_starts) {
+    return starts_plan(workspace, row_ptr, I, ms_scratch(I, row_ptr[I], K, rank).total, n_starts);
 }
 
 // the options of a grid's jobs in the workspace, behind the plan of mcl_multistart_run
@@ -859,36 +834,24 @@ std::string ms_check_weights(const double *w, int32_t n_jobs, int64_t I) {
 // mcl_multistart_run (per_job false: *opt for every workgroup, passed in the kernarg), mcl_multistart_run_grid (per_job true:
 // opt[s] for workgroup s, uploaded to the workspace) and mcl_multistart_run_weighted (weighted true: *opt for every workgroup
 // and the host array slab_weights [n_starts, I], uploaded to the workspace)
-int ms_run(const char *who, const void *X, int32_t x_type, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank,
+int ms_run(const char *who, const char *sizer, const void *X, int32_t x_type, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank,
            const mcl_multistart_options *opt, int32_t n_starts, bool per_job, bool weighted, const double *slab_weights,
            double *state, double *diag, int32_t *n_iter, int32_t *stop, void *workspace, int64_t workspace_bytes, void *hip_stream) {
-    auto fail = [who](const std::string &m) {
-        g_ms_error = who + m;
-        return 1;
-    };
+    ErrorSlot &fail = g_ms_error.named(who);
     std::string bad = per_job ? ms_check_grid(row_ptr, I, K, rank, opt, n_starts) : ms_check(row_ptr, I, K, rank, opt, n_starts);
     if (bad.empty() && weighted) bad = ms_check_weights(slab_weights, n_starts, I);
     if (!bad.empty()) return fail(bad);
     if (!X || !state || !diag || !n_iter || !stop || !workspace) return fail("NULL argument");
-    if (x_type != MCL_X_F32 && x_type != MCL_X_BF16 && x_type != MCL_X_F16)
-        return fail("unknown x_type " + std::to_string(x_type) + " (MCL_X_F32 = 0, MCL_X_BF16 = 1, MCL_X_F16 = 2)");
-    const MsPlan p = ms_plan(row_ptr, I, K, rank, opt, n_starts);
+    if (!x_type_error(x_type).empty()) return fail(x_type_error(x_type));
+    const StartsPlan p = ms_plan(workspace, row_ptr, I, K, rank, n_starts);
     const int64_t jobs_bytes = per_job ? ms_jobs_bytes(n_starts) : (weighted ? ms_weights_bytes(n_starts, I) : 0);
-    if (workspace_bytes < p.total + jobs_bytes)
-        return fail(per_job    ? "workspace too small (mcl_multistart_grid_workspace_bytes)"
-                    : weighted ? "workspace too small (mcl_multistart_weighted_workspace_bytes)"
-                               : "workspace too small (mcl_multistart_workspace_bytes)");
-    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail("workspace must be 256-byte aligned");
+    if (workspace_refused(fail, workspace, workspace_bytes, p.total + jobs_bytes, sizer)) return 1;
     hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
-    char *ws = static_cast<char *>(workspace);
-    std::vector<int32_t> slab(p.N);
-    for (int64_t i = 0; i < I; ++i)
-        for (int64_t j = row_ptr[i]; j < row_ptr[i + 1]; ++j) slab[j] = (int32_t)i;
-    if (hipMemcpyAsync(ws + p.off_rowptr, row_ptr, (I + 1) * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
-        (p.N && hipMemcpyAsync(ws + p.off_slab, slab.data(), p.N * 4, hipMemcpyHostToDevice, s) != hipSuccess) ||
-        (per_job && hipMemcpyAsync(ws + p.total, opt, int64_t(n_starts) * sizeof(mcl_multistart_options), hipMemcpyHostToDevice, s) !=
-                        hipSuccess) ||
-        (weighted && hipMemcpyAsync(ws + p.total, slab_weights, int64_t(n_starts) * I * 8, hipMemcpyHostToDevice, s) != hipSuccess) ||
+    char *extra = static_cast<char *>(workspace) + p.total;  // the jobs' options or weights, behind the plan
+    std::vector<int32_t> slab;
+    if (upload_starts(p, row_ptr, I, slab, s) != hipSuccess ||
+        (per_job && hipMemcpyAsync(extra, opt, int64_t(n_starts) * sizeof(mcl_multistart_options), hipMemcpyHostToDevice, s) != hipSuccess) ||
+        (weighted && hipMemcpyAsync(extra, slab_weights, int64_t(n_starts) * I * 8, hipMemcpyHostToDevice, s) != hipSuccess) ||
         hipStreamSynchronize(s) != hipSuccess)
         return fail(per_job ? "upload of row_ptr and the options failed"
                             : (weighted ? "upload of row_ptr and the weights failed" : "upload of row_ptr failed"));
@@ -896,21 +859,24 @@ int ms_run(const char *who, const void *X, int32_t x_type, const int64_t *row_pt
     for (int32_t j = 1; per_job && j < n_starts; ++j) n_iter_most = std::max(n_iter_most, opt[j].n_iter_max);
     MsArgs a{};
     a.X = X;
-    a.row_ptr = reinterpret_cast<const int64_t *>(ws + p.off_rowptr);
-    a.slab_of_row = reinterpret_cast<const int32_t *>(ws + p.off_slab);
+    a.row_ptr = p.row_ptr;
+    a.slab_of_row = p.slab_of_row;
     a.I = I, a.N = p.N, a.K = K;
-    a.state_len = p.state_len, a.scratch_len = p.scratch_len;
+    ms_state_layout(a, rank, opt);
+    a.scratch_len = ms_scratch(I, p.N, K, rank).total;
     a.diag_stride = int64_t(n_iter_most + 1) * MCL_MS_DIAG;
-    a.state = state, a.scratch = reinterpret_cast<double *>(ws + p.off_scratch), a.diag = diag;
+    a.state = state, a.scratch = p.scratch, a.diag = diag;
     a.n_iter = n_iter, a.stop = stop;
-    for (int m = 0; m < 3; ++m)
-        for (int k = 0; k < MCL_MAX_REGS; ++k)
-            a.off_aux[m][k] = p.off_aux[m][k], a.off_dual[m][k] = p.off_dual[m][k], a.off_delta[m][k] = p.off_delta[m][k];
     a.o = *opt;
-    a.jobs = per_job ? reinterpret_cast<const mcl_multistart_options *>(ws + p.total) : nullptr;
+    a.jobs = per_job ? reinterpret_cast<const mcl_multistart_options *>(extra) : nullptr;
+    const double *slab_weight = weighted ? reinterpret_cast<const double *>(extra) : nullptr;
     mcl_x_dispatch(x_type, [&](auto xl) {
         using XL = decltype(xl);
-        launch_rank<XL>(rank, a, n_starts, weighted ? reinterpret_cast<const double *>(ws + p.total) : nullptr, s);
+        rank_exact<MS_MAX_RANK>(rank, [&](auto rc) {
+            constexpr int R = decltype(rc)::value;
+            if (slab_weight) hipLaunchKernelGGL((k_multistart_weighted<R, XL>), dim3(n_starts), dim3(MS_THREADS), 0, s, a, slab_weight);
+            else hipLaunchKernelGGL((k_multistart<R, XL>), dim3(n_starts), dim3(MS_THREADS), 0, s, a);
+        });
         return 0;
     });
     const hipError_t e = hipGetLastError();
@@ -927,41 +893,41 @@ const char *mcl_multistart_last_error(void) { return g_ms_error.c_str(); }
 int64_t mcl_multistart_workspace_bytes(const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank, const mcl_multistart_options *opt,
                                        int32_t n_starts) {
     if (!ms_check(row_ptr, I, K, rank, opt, n_starts).empty()) return -1;
-    return ms_plan(row_ptr, I, K, rank, opt, n_starts).total;
+    return ms_plan(nullptr, row_ptr, I, K, rank, n_starts).total;
 }
 
 int mcl_multistart_run(const void *X, int32_t x_type, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank,
                        const mcl_multistart_options *opt, int32_t n_starts, double *state, double *diag, int32_t *n_iter, int32_t *stop,
                        void *workspace, int64_t workspace_bytes, void *hip_stream) {
-    return ms_run("mcl_multistart_run: ", X, x_type, row_ptr, I, K, rank, opt, n_starts, false, false, nullptr, state, diag, n_iter,
-                  stop, workspace, workspace_bytes, hip_stream);
+    return ms_run("mcl_multistart_run: ", "mcl_multistart_workspace_bytes", X, x_type, row_ptr, I, K, rank, opt, n_starts, false, false,
+                  nullptr, state, diag, n_iter, stop, workspace, workspace_bytes, hip_stream);
 }
 
 int64_t mcl_multistart_grid_workspace_bytes(const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank,
                                             const mcl_multistart_options *options, int32_t n_jobs) {
     if (!ms_check_grid(row_ptr, I, K, rank, options, n_jobs).empty()) return -1;
-    return ms_plan(row_ptr, I, K, rank, options, n_jobs).total + ms_jobs_bytes(n_jobs);
+    return ms_plan(nullptr, row_ptr, I, K, rank, n_jobs).total + ms_jobs_bytes(n_jobs);
 }
 
 int mcl_multistart_run_grid(const void *X, int32_t x_type, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank,
                             const mcl_multistart_options *options, int32_t n_jobs, double *state, double *diag, int32_t *n_iter,
                             int32_t *stop, void *workspace, int64_t workspace_bytes, void *hip_stream) {
-    return ms_run("mcl_multistart_run_grid: ", X, x_type, row_ptr, I, K, rank, options, n_jobs, true, false, nullptr, state, diag,
-                  n_iter, stop, workspace, workspace_bytes, hip_stream);
+    return ms_run("mcl_multistart_run_grid: ", "mcl_multistart_grid_workspace_bytes", X, x_type, row_ptr, I, K, rank, options, n_jobs, true,
+                  false, nullptr, state, diag, n_iter, stop, workspace, workspace_bytes, hip_stream);
 }
 
 int64_t mcl_multistart_weighted_workspace_bytes(const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank,
                                                 const mcl_multistart_options *opt, int32_t n_jobs) {
     if (!ms_check(row_ptr, I, K, rank, opt, n_jobs).empty()) return -1;
-    return ms_plan(row_ptr, I, K, rank, opt, n_jobs).total + ms_weights_bytes(n_jobs, I);
+    return ms_plan(nullptr, row_ptr, I, K, rank, n_jobs).total + ms_weights_bytes(n_jobs, I);
 }
 
 int mcl_multistart_run_weighted(const void *X, int32_t x_type, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank,
                                 const mcl_multistart_options *opt, int32_t n_jobs, const double *slab_weights, double *state,
                                 double *diag, int32_t *n_iter, int32_t *stop, void *workspace, int64_t workspace_bytes,
                                 void *hip_stream) {
-    return ms_run("mcl_multistart_run_weighted: ", X, x_type, row_ptr, I, K, rank, opt, n_jobs, false, true, slab_weights, state,
-                  diag, n_iter, stop, workspace, workspace_bytes, hip_stream);
+    return ms_run("mcl_multistart_run_weighted: ", "mcl_multistart_weighted_workspace_bytes", X, x_type, row_ptr, I, K, rank, opt, n_jobs,
+                  false, true, slab_weights, state, diag, n_iter, stop, workspace, workspace_bytes, hip_stream);
 }
 
 }  // extern "C"

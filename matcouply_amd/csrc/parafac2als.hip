@@ -27,7 +27,7 @@
 
 namespace {
 
-static std::string g_pf2als_error;
+static ErrorSlot g_pf2als_error{"mcl_parafac2_als: "};
 constexpr int PA_BLOCK = 16;   // iterations enqueued between two reads of the stop flag
 constexpr int PA_MAX_RANK = 32;
 
@@ -583,12 +583,16 @@ __global__ __launch_bounds__(256) void k_pf2als_out(const float *__restrict__ W,
 struct PaPlan {
     int64_t N;
     int nseg, nkb, NB, KH, RMAX, ngrp_ab, ngrp_mc, wgC;
-    int64_t off_segs, off_slab_seg, off_ext, off_A, off_B, off_C, off_Cfrag, off_W, off_T, off_PtP, off_Y, off_Pab, off_Pc, off_Pcc,
-        off_Pdot, off_Pfit, off_nxp, off_Gram, off_Gm, off_small, off_gate, off_info, off_scratch;
-    int64_t svd_ws, scratch, total;
+    int4 *segs;
+    int *slab_seg, *ext, *gate, *info;
+    double *A, *B, *C, *T, *PtP, *Y, *Pab, *Pc, *Pcc, *Pdot, *Pfit, *nxp, *Gram, *Gm, *small;
+    float *Cfrag, *W;
+    char *scratch;
+    int64_t svd_ws, total;
 };
 
-PaPlan pa_plan(const int64_t *row_ptr, int64_t I, int64_t K, int rank) {
+// workspace NULL: the parts are null and `total` is the size (mcl_parafac2_als_workspace_bytes)
+PaPlan pa_plan(void *workspace, const int64_t *row_ptr, int64_t I, int64_t K, int rank) {
     PaPlan p{};
     p.N = row_ptr[I];
     const int64_t nseg = seg_count(row_ptr, I);
@@ -601,155 +605,125 @@ PaPlan pa_plan(const int64_t *row_ptr, int64_t I, int64_t K, int rank) {
     p.ngrp_ab = (int)std::max<int64_t>(1, std::min<int64_t>(128, (I + 7) / 8));
     p.ngrp_mc = (int)std::max<int64_t>(1, std::min<int64_t>(I, std::max<int64_t>(1, 256 / p.nkb)));
     p.wgC = (int)((K + (256 / p.RMAX) - 1) / (256 / p.RMAX));
-    WsCursor ws;
-    p.off_segs = ws.take(std::max<int64_t>(nseg, 1) * 16);
-    p.off_slab_seg = ws.take((I + 1) * 4);
-    p.off_ext = ws.take((I + 1) * 4);
-    p.off_A = ws.take(I * r * 8);
-    p.off_B = ws.take(r * r * 8);
-    p.off_C = ws.take(K * r * 8);
-    p.off_Cfrag = ws.take((int64_t)p.KH * p.NB * 64 * 4 * 4);
-    p.off_W = ws.take(p.N * r * 4);
-    p.off_T = ws.take(I * r * r * 8);
-    p.off_PtP = ws.take(I * r * r * 8);
-    p.off_Y = ws.take(I * K * r * 8);
-    p.off_Pab = ws.take((int64_t)p.ngrp_ab * 2 * r * r * 8);
-    p.off_Pc = ws.take((int64_t)p.ngrp_mc * K * r * 8);
-    p.off_Pcc = ws.take((int64_t)p.wgC * r * r * 8);
-    p.off_Pdot = ws.take((int64_t)p.wgC * 8);
-    p.off_Pfit = ws.take((int64_t)p.ngrp_ab * 8);
-    p.off_nxp = ws.take(I * 8);
-    p.off_Gram = ws.take(3 * r * r * 8);
-    p.off_Gm = ws.take(r * r * 8);
-    p.off_small = ws.take(4 * 8);  // |X|^2, <M_C, C>, e_{t-1}^2
-    p.off_gate = ws.take(4 * 4);   // stop flag, iterations used
-    p.off_info = ws.take((I + 2) * 4);
-    p.off_scratch = ws.off;
+    WsCursor ws(workspace);
+    p.segs = ws.take<int4>(std::max<int64_t>(nseg, 1) * 16);
+    p.slab_seg = ws.take<int>((I + 1) * 4);
+    p.ext = ws.take<int>((I + 1) * 4);
+    p.A = ws.take<double>(I * r * 8);
+    p.B = ws.take<double>(r * r * 8);
+    p.C = ws.take<double>(K * r * 8);
+    p.Cfrag = ws.take<float>((int64_t)p.KH * p.NB * 64 * 4 * 4);
+    p.W = ws.take<float>(p.N * r * 4);
+    p.T = ws.take<double>(I * r * r * 8);
+    p.PtP = ws.take<double>(I * r * r * 8);
+    p.Y = ws.take<double>(I * K * r * 8);
+    p.Pab = ws.take<double>((int64_t)p.ngrp_ab * 2 * r * r * 8);
+    p.Pc = ws.take<double>((int64_t)p.ngrp_mc * K * r * 8);
+    p.Pcc = ws.take<double>((int64_t)p.wgC * r * r * 8);
+    p.Pdot = ws.take<double>((int64_t)p.wgC * 8);
+    p.Pfit = ws.take<double>((int64_t)p.ngrp_ab * 8);
+    p.nxp = ws.take<double>(I * 8);
+    p.Gram = ws.take<double>(3 * r * r * 8);
+    p.Gm = ws.take<double>(r * r * 8);
+    p.small = ws.take<double>(4 * 8);  // |X|^2, <M_C, C>, e_{t-1}^2
+    p.gate = ws.take<int>(4 * 4);      // stop flag, iterations used
+    p.info = ws.take<int>((I + 2) * 4);
     // the svd start: mcl_svd_init's workspace + C0 (fp32)
     p.svd_ws = (mcl_svd_stack_workspace_bytes(row_ptr, I, K, rank) + 255) & ~int64_t(255);
-    p.scratch = p.svd_ws + ((K * r * 4 + 255) & ~int64_t(255));
-    p.total = ws.off + p.scratch;
+    p.scratch = ws.take<char>(p.svd_ws + K * r * 4);
+    p.total = ws.off;
     return p;
 }
-
-template <class XL, int NB>
-struct PaLaunch {
-    template <bool VEC>
-    static void passes(bool second, const typename XL::T *X, const PaPlan &p, const int4 *segs, const int *slab_seg, int I, int K, int r,
-                       const float *Cfrag, float *W, const double *T, double *Y, const int *gate, hipStream_t s) {
-        if (!second)
-            hipLaunchKernelGGL((k_pf2als_xc<XL, NB, VEC>), dim3((unsigned)((p.nseg + 3) / 4)), dim3(256), 0, s, X, segs, p.nseg, K, r, Cfrag, W,
-                               gate);
-        else
-            hipLaunchKernelGGL((k_pf2als_y<XL, NB, VEC>), dim3((unsigned)I, (unsigned)p.nkb), dim3(256), 0, s, X, segs, slab_seg, K, r,
-                               (const float *)W, T, Y, gate);
-    }
-};
 
 template <class XL, int RMAX>
 int pf2als_run(const typename XL::T *X, int32_t x_type, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank, const double *A0,
                const double *B0, const double *C0, int32_t n_iter_max, int32_t n_iter_parafac, double tol, double absolute_tol,
-               int32_t nn_modes, float *A, float *B, float *C, float *P, double *errors, int32_t *info, void *workspace,
-               int64_t workspace_bytes, void *hip_stream) {
+               int32_t nn_modes, float *A, float *B, float *C, float *P, double *errors, int32_t *info, const PaPlan &p, hipStream_t s) {
     constexpr int NB = RMAX / 16;
-    auto fail = [](const std::string &msg) {
-        g_pf2als_error = msg;
-        return 1;
-    };
-    const PaPlan p = pa_plan(row_ptr, I, K, rank);
-    if (workspace_bytes < p.total) return fail("mcl_parafac2_als: workspace too small (mcl_parafac2_als_workspace_bytes)");
-    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail("mcl_parafac2_als: workspace must be 256-byte aligned");
-    hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
-    char *ws = static_cast<char *>(workspace);
-    auto at = [&](int64_t off) { return static_cast<void *>(ws + off); };
-    int4 *segs = static_cast<int4 *>(at(p.off_segs));
-    int *slab_seg = static_cast<int *>(at(p.off_slab_seg)), *ext = static_cast<int *>(at(p.off_ext));
-    double *A64 = static_cast<double *>(at(p.off_A)), *B64 = static_cast<double *>(at(p.off_B)), *C64 = static_cast<double *>(at(p.off_C));
-    float *Cfrag = static_cast<float *>(at(p.off_Cfrag)), *W = static_cast<float *>(at(p.off_W));
-    double *Tm = static_cast<double *>(at(p.off_T)), *PtP = static_cast<double *>(at(p.off_PtP)), *Y = static_cast<double *>(at(p.off_Y));
-    double *Pab = static_cast<double *>(at(p.off_Pab)), *Pc = static_cast<double *>(at(p.off_Pc)), *Pcc = static_cast<double *>(at(p.off_Pcc));
-    double *Pdot = static_cast<double *>(at(p.off_Pdot)), *Pfit = static_cast<double *>(at(p.off_Pfit)), *nxp = static_cast<double *>(at(p.off_nxp));
-    double *Gram = static_cast<double *>(at(p.off_Gram)), *Gm = static_cast<double *>(at(p.off_Gm)), *small = static_cast<double *>(at(p.off_small));
-    int *gate = static_cast<int *>(at(p.off_gate)), *sinfo = static_cast<int *>(at(p.off_info));
-    char *scr = ws + p.off_scratch;
+    auto fail = [](const std::string &msg) { return g_pf2als_error.as_is(msg); };  // (a HIP call's or the svd start's message)
     const int r = rank, N = (int)p.N;
     const bool hals_a = nn_modes & 1, hals_c = (nn_modes >> 2) & 1;
 
     const SegTables h = seg_tables(row_ptr, I);
-    CP_HIP(hipMemcpyAsync(segs, h.segs.data(), sizeof(int4) * h.segs.size(), hipMemcpyHostToDevice, s));
-    CP_HIP(hipMemcpyAsync(slab_seg, h.slab_seg.data(), sizeof(int) * h.slab_seg.size(), hipMemcpyHostToDevice, s));
-    CP_HIP(hipMemcpyAsync(ext, h.ext.data(), sizeof(int) * h.ext.size(), hipMemcpyHostToDevice, s));
-    CP_HIP(hipMemsetAsync(Cfrag, 0, (size_t)p.KH * p.NB * 64 * 4 * 4, s));
-    CP_HIP(hipMemsetAsync(gate, 0, 4 * sizeof(int), s));
+    CP_HIP(upload_tables(h, p.segs, p.slab_seg, p.ext, s));
+    CP_HIP(hipMemsetAsync(p.Cfrag, 0, (size_t)p.KH * p.NB * 64 * 4 * 4, s));
+    CP_HIP(hipMemsetAsync(p.gate, 0, 4 * sizeof(int), s));
     CP_HIP(hipStreamSynchronize(s));  // (the tables are locals)
 
     // ---- start: the given factors, or A = 1, B = I, C = the C of mcl_svd_init
     if (A0) {
-        CP_HIP(hipMemcpyAsync(A64, A0, sizeof(double) * I * r, hipMemcpyDeviceToDevice, s));
-        CP_HIP(hipMemcpyAsync(B64, B0, sizeof(double) * r * r, hipMemcpyDeviceToDevice, s));
-        CP_HIP(hipMemcpyAsync(C64, C0, sizeof(double) * K * r, hipMemcpyDeviceToDevice, s));
+        CP_HIP(hipMemcpyAsync(p.A, A0, sizeof(double) * I * r, hipMemcpyDeviceToDevice, s));
+        CP_HIP(hipMemcpyAsync(p.B, B0, sizeof(double) * r * r, hipMemcpyDeviceToDevice, s));
+        CP_HIP(hipMemcpyAsync(p.C, C0, sizeof(double) * K * r, hipMemcpyDeviceToDevice, s));
     } else {
-        float *C32 = reinterpret_cast<float *>(scr + p.svd_ws);
+        float *C32 = reinterpret_cast<float *>(p.scratch + p.svd_ws);
         std::string err;
-        if (mcl_svd_stack_right(X, x_type, row_ptr, I, K, rank, 0, C32, scr, p.svd_ws, sinfo, s, err)) return fail(err);
+        if (mcl_svd_stack_right(X, x_type, row_ptr, I, K, rank, 0, C32, p.scratch, p.svd_ws, p.info, s, err)) return fail(err);
         std::vector<double> h_A((size_t)I * r, 1.0), h_B((size_t)r * r, 0.0);
         for (int q = 0; q < r; ++q) h_B[(size_t)q * r + q] = 1.0;
-        CP_HIP(hipMemcpyAsync(A64, h_A.data(), sizeof(double) * h_A.size(), hipMemcpyHostToDevice, s));
-        CP_HIP(hipMemcpyAsync(B64, h_B.data(), sizeof(double) * h_B.size(), hipMemcpyHostToDevice, s));
+        CP_HIP(upload(p.A, h_A, s));
+        CP_HIP(upload(p.B, h_B, s));
         std::vector<float> h_C((size_t)K * r);
         std::vector<double> h_C64((size_t)K * r);
         CP_HIP(hipMemcpyAsync(h_C.data(), C32, sizeof(float) * h_C.size(), hipMemcpyDeviceToHost, s));
         CP_HIP(hipStreamSynchronize(s));
         for (size_t e = 0; e < h_C.size(); ++e) h_C64[e] = (double)h_C[e];
-        CP_HIP(hipMemcpyAsync(C64, h_C64.data(), sizeof(double) * h_C64.size(), hipMemcpyHostToDevice, s));
+        CP_HIP(upload(p.C, h_C64, s));
         CP_HIP(hipStreamSynchronize(s));  // (the host copies are locals)
     }
-    hipLaunchKernelGGL(k_pf2als_norm<XL>, dim3((unsigned)I), dim3(256), 0, s, X, (const int *)ext, (int)K, nxp);
-    hipLaunchKernelGGL(k_pf2als_start<RMAX>, dim3(1), dim3(1024), 0, s, (const double *)nxp, (int)I, (int)K, r, NB, (int)hals_a,
-                       (const double *)B64, (const double *)C64, Cfrag, Gram, Gm, small, gate);
+    hipLaunchKernelGGL(k_pf2als_norm<XL>, dim3((unsigned)I), dim3(256), 0, s, X, (const int *)p.ext, (int)K, p.nxp);
+    hipLaunchKernelGGL(k_pf2als_start<RMAX>, dim3(1), dim3(1024), 0, s, (const double *)p.nxp, (int)I, (int)K, r, NB, (int)hals_a,
+                       (const double *)p.B, (const double *)p.C, p.Cfrag, p.Gram, p.Gm, p.small, p.gate);
     CP_HIP(hipGetLastError());
 
     const bool vec = K % 4 == 0 && mcl_x_vec_aligned(X, x_type);
-    auto pass = [&](bool second) {
-        if (vec) PaLaunch<XL, NB>::template passes<true>(second, X, p, segs, slab_seg, (int)I, (int)K, r, Cfrag, W, Tm, Y, gate, s);
-        else PaLaunch<XL, NB>::template passes<false>(second, X, p, segs, slab_seg, (int)I, (int)K, r, Cfrag, W, Tm, Y, gate, s);
+    auto pass = [&](bool second) {  // W = X C, or Y = T^T W^T X
+        vec_dispatch(vec, [&](auto v) {
+            constexpr bool VEC = decltype(v)::value;
+            if (!second)
+                hipLaunchKernelGGL((k_pf2als_xc<XL, NB, VEC>), dim3((unsigned)((p.nseg + 3) / 4)), dim3(256), 0, s, X, (const int4 *)p.segs, p.nseg,
+                                   (int)K, r, (const float *)p.Cfrag, p.W, (const int *)p.gate);
+            else
+                hipLaunchKernelGGL((k_pf2als_y<XL, NB, VEC>), dim3((unsigned)I, (unsigned)p.nkb), dim3(256), 0, s, X, (const int4 *)p.segs,
+                                   (const int *)p.slab_seg, (int)K, r, (const float *)p.W, (const double *)p.T, p.Y, (const int *)p.gate);
+        });
     };
     const bool check = tol > 0.0;
     int used = n_iter_max;
     for (int t = 0; t < n_iter_max; ++t) {
-        pass(false);  // W = X C
-        hipLaunchKernelGGL(k_pf2als_polar<RMAX>, dim3((unsigned)I), dim3(256), 0, s, (const float *)W, (const int *)ext, r,
-                           (const double *)A64, (const double *)B64, Tm, PtP, (const int *)gate);
-        pass(true);  // Y = T^T W^T X
+        pass(false);
+        hipLaunchKernelGGL(k_pf2als_polar<RMAX>, dim3((unsigned)I), dim3(256), 0, s, (const float *)p.W, (const int *)p.ext, r,
+                           (const double *)p.A, (const double *)p.B, p.T, p.PtP, (const int *)p.gate);
+        pass(true);
         for (int sw = 0; sw < n_iter_parafac; ++sw) {
-            hipLaunchKernelGGL(k_pf2als_ab<RMAX>, dim3((unsigned)p.ngrp_ab), dim3(256), 0, s, (const double *)Y, (const double *)C64, A64,
-                               (const double *)B64, (const double *)Gm, (int)I, (int)K, r, p.ngrp_ab, (int)hals_a, Pab, (const int *)gate);
-            hipLaunchKernelGGL(k_pf2als_b<RMAX>, dim3(1), dim3(1024), 0, s, (const double *)Pab, p.ngrp_ab, r, (int)hals_c, B64, Gram, Gm,
-                               (const int *)gate);
-            hipLaunchKernelGGL(k_pf2als_mc<RMAX>, dim3((unsigned)p.nkb, (unsigned)p.ngrp_mc), dim3(256), 0, s, (const double *)Y,
-                               (const double *)A64, (const double *)B64, (int)I, (int)K, r, p.ngrp_mc, Pc, (const int *)gate);
-            hipLaunchKernelGGL(k_pf2als_c<RMAX>, dim3((unsigned)p.wgC), dim3(256), 0, s, (const double *)Pc, p.ngrp_mc, (int)K, r, NB, (int)hals_c,
-                               (const double *)Gm, C64, Cfrag, Pcc, Pdot, (const int *)gate);
-            hipLaunchKernelGGL(k_pf2als_prep<RMAX>, dim3(1), dim3(1024), 0, s, (const double *)Pcc, (const double *)Pdot, p.wgC, r, (int)hals_a,
-                               Gram, Gm, small, (const int *)gate);
+            hipLaunchKernelGGL(k_pf2als_ab<RMAX>, dim3((unsigned)p.ngrp_ab), dim3(256), 0, s, (const double *)p.Y, (const double *)p.C, p.A,
+                               (const double *)p.B, (const double *)p.Gm, (int)I, (int)K, r, p.ngrp_ab, (int)hals_a, p.Pab, (const int *)p.gate);
+            hipLaunchKernelGGL(k_pf2als_b<RMAX>, dim3(1), dim3(1024), 0, s, (const double *)p.Pab, p.ngrp_ab, r, (int)hals_c, p.B, p.Gram, p.Gm,
+                               (const int *)p.gate);
+            hipLaunchKernelGGL(k_pf2als_mc<RMAX>, dim3((unsigned)p.nkb, (unsigned)p.ngrp_mc), dim3(256), 0, s, (const double *)p.Y,
+                               (const double *)p.A, (const double *)p.B, (int)I, (int)K, r, p.ngrp_mc, p.Pc, (const int *)p.gate);
+            hipLaunchKernelGGL(k_pf2als_c<RMAX>, dim3((unsigned)p.wgC), dim3(256), 0, s, (const double *)p.Pc, p.ngrp_mc, (int)K, r, NB, (int)hals_c,
+                               (const double *)p.Gm, p.C, p.Cfrag, p.Pcc, p.Pdot, (const int *)p.gate);
+            hipLaunchKernelGGL(k_pf2als_prep<RMAX>, dim3(1), dim3(1024), 0, s, (const double *)p.Pcc, (const double *)p.Pdot, p.wgC, r, (int)hals_a,
+                               p.Gram, p.Gm, p.small, (const int *)p.gate);
         }
         if (check) {
-            hipLaunchKernelGGL(k_pf2als_fit<RMAX>, dim3((unsigned)p.ngrp_ab), dim3(256), 0, s, (const double *)PtP, (const double *)A64,
-                               (const double *)B64, (const double *)Gram, (int)I, r, p.ngrp_ab, Pfit, (const int *)gate);
-            hipLaunchKernelGGL(k_pf2als_err, dim3(1), dim3(64), 0, s, (const double *)Pfit, p.ngrp_ab, t, tol, absolute_tol, small, errors, gate);
+            hipLaunchKernelGGL(k_pf2als_fit<RMAX>, dim3((unsigned)p.ngrp_ab), dim3(256), 0, s, (const double *)p.PtP, (const double *)p.A,
+                               (const double *)p.B, (const double *)p.Gram, (int)I, r, p.ngrp_ab, p.Pfit, (const int *)p.gate);
+            hipLaunchKernelGGL(k_pf2als_err, dim3(1), dim3(64), 0, s, (const double *)p.Pfit, p.ngrp_ab, t, tol, absolute_tol, p.small, errors, p.gate);
         }
         CP_HIP(hipGetLastError());
         if (check && ((t + 1) % PA_BLOCK == 0 || t + 1 == n_iter_max)) {  // the verdict, read in blocks: later launches are gated
             int g[2] = {0, 0};
-            CP_HIP(hipMemcpyAsync(g, gate, sizeof(g), hipMemcpyDeviceToHost, s));
+            CP_HIP(hipMemcpyAsync(g, p.gate, sizeof(g), hipMemcpyDeviceToHost, s));
             CP_HIP(hipStreamSynchronize(s));
             used = g[1];
             if (g[0]) break;
         }
     }
     const long big = std::max<long>((long)N, std::max<long>((long)I, (long)K)) * r;
-    hipLaunchKernelGGL(k_pf2als_out, dim3((unsigned)((big + 255) / 256), 4), dim3(256), 0, s, (const float *)W, (const double *)Tm,
-                       (const double *)A64, (const double *)B64, (const double *)C64, (const int *)ext, (int)I, N, (int)K, r, P, A, B, C);
+    hipLaunchKernelGGL(k_pf2als_out, dim3((unsigned)((big + 255) / 256), 4), dim3(256), 0, s, (const float *)p.W, (const double *)p.T,
+                       (const double *)p.A, (const double *)p.B, (const double *)p.C, (const int *)p.ext, (int)I, N, (int)K, r, P, A, B, C);
     CP_HIP(hipGetLastError());
     CP_HIP(hipMemcpyAsync(info, &used, sizeof(int32_t), hipMemcpyHostToDevice, s));
     CP_HIP(hipStreamSynchronize(s));  // (`used` is a local)
@@ -757,15 +731,10 @@ int pf2als_run(const typename XL::T *X, int32_t x_type, const int64_t *row_ptr, 
 }
 
 std::string check_args(const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank) {
-    if (!row_ptr || I < 1 || K < 1) return "need row_ptr, I >= 1, K >= 1";
-    if (rank < 1 || rank > PA_MAX_RANK) return "need 1 <= rank <= 32";
-    if (row_ptr[0] != 0) return "row_ptr[0] must be 0";
-    for (int64_t i = 0; i < I; ++i)
-        if (row_ptr[i + 1] - row_ptr[i] < rank) return "every matrix needs at least rank rows";
-    if (rank > K) return "rank exceeds K";
-    if (row_ptr[I] >= (int64_t(1) << 31) / PA_MAX_RANK) return "more than 2^26 packed rows are not supported";
-    if (I >= (int64_t(1) << 31) / 64) return "more than 2^25 matrices are not supported";
-    return "";
+    std::string bad = packed_args_error(row_ptr, I, K, rank, PA_MAX_RANK);
+    if (bad.empty()) bad = packed_rows_error(row_ptr, I, K, rank, 26);  // rows x PA_MAX_RANK in 32 bits
+    if (bad.empty() && I >= (int64_t(1) << 31) / 64) bad = "more than 2^25 matrices are not supported";
+    return bad;
 }
 
 }  // namespace
@@ -776,50 +745,32 @@ const char *mcl_parafac2_als_last_error(void) { return g_pf2als_error.c_str(); }
 
 int64_t mcl_parafac2_als_workspace_bytes(const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank) {
     if (!check_args(row_ptr, I, K, rank).empty()) return -1;
-    return pa_plan(row_ptr, I, K, rank).total;
+    return pa_plan(nullptr, row_ptr, I, K, rank).total;
 }
 
 int mcl_parafac2_als_typed(const void *X, int32_t x_type, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank, const double *A0,
                            const double *B0, const double *C0, int32_t n_iter_max, int32_t n_iter_parafac, double tol,
                            double absolute_tol, int32_t nn_modes, float *A, float *B, float *C, float *P, double *errors,
                            int32_t *info, void *workspace, int64_t workspace_bytes, void *hip_stream) {
+    ErrorSlot &fail = g_pf2als_error;
     const std::string bad = check_args(row_ptr, I, K, rank);
-    if (!bad.empty()) {
-        g_pf2als_error = "mcl_parafac2_als: " + bad;
-        return 1;
-    }
-    if (!X || !A || !B || !C || !P || !info || !workspace || (tol > 0.0 && !errors)) {
-        g_pf2als_error = "mcl_parafac2_als: NULL argument";
-        return 1;
-    }
-    if ((A0 || B0 || C0) && !(A0 && B0 && C0)) {
-        g_pf2als_error = "mcl_parafac2_als: give all of A0, B0, C0 or none";
-        return 1;
-    }
-    if (!A0 && K > 2048) {
-        g_pf2als_error = "mcl_parafac2_als: the svd start needs K <= 2048";
-        return 1;
-    }
-    if (!x_type_error(x_type).empty()) {
-        g_pf2als_error = "mcl_parafac2_als: " + x_type_error(x_type);
-        return 1;
-    }
-    if (nn_modes & ~5) {
-        g_pf2als_error = "mcl_parafac2_als: nn_modes may hold modes 0 and 2 only (bits 1 and 4)";
-        return 1;
-    }
-    if (n_iter_max < 1 || n_iter_parafac < 1 || !(tol >= 0.0) || !(absolute_tol >= 0.0)) {
-        g_pf2als_error = "mcl_parafac2_als: need n_iter_max >= 1, n_iter_parafac >= 1, tol >= 0 and absolute_tol >= 0";
-        return 1;
-    }
+    if (!bad.empty()) return fail(bad);
+    if (!X || !A || !B || !C || !P || !info || !workspace || (tol > 0.0 && !errors)) return fail("NULL argument");
+    if ((A0 || B0 || C0) && !(A0 && B0 && C0)) return fail("give all of A0, B0, C0 or none");
+    if (!A0 && K > 2048) return fail("the svd start needs K <= 2048");
+    if (!x_type_error(x_type).empty()) return fail(x_type_error(x_type));
+    if (nn_modes & ~5) return fail("nn_modes may hold modes 0 and 2 only (bits 1 and 4)");
+    if (n_iter_max < 1 || n_iter_parafac < 1 || !(tol >= 0.0) || !(absolute_tol >= 0.0))
+        return fail("need n_iter_max >= 1, n_iter_parafac >= 1, tol >= 0 and absolute_tol >= 0");
+    const PaPlan p = pa_plan(workspace, row_ptr, I, K, rank);
+    if (workspace_refused(fail, workspace, workspace_bytes, p.total, "mcl_parafac2_als_workspace_bytes")) return 1;
+    hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
     return mcl_x_dispatch(x_type, [&](auto xl) {
         using XL = decltype(xl);
-        const auto *Xt = static_cast<const typename XL::T *>(X);
-        if (rank <= 16)
-            return pf2als_run<XL, 16>(Xt, x_type, row_ptr, I, K, rank, A0, B0, C0, n_iter_max, n_iter_parafac, tol, absolute_tol, nn_modes, A,
-                                      B, C, P, errors, info, workspace, workspace_bytes, hip_stream);
-        return pf2als_run<XL, 32>(Xt, x_type, row_ptr, I, K, rank, A0, B0, C0, n_iter_max, n_iter_parafac, tol, absolute_tol, nn_modes, A, B,
-                                  C, P, errors, info, workspace, workspace_bytes, hip_stream);
+        return rank_bucket(rank, [&](auto rmax) {
+            return pf2als_run<XL, decltype(rmax)::value>(static_cast<const typename XL::T *>(X), x_type, row_ptr, I, K, rank, A0, B0, C0,
+                                                         n_iter_max, n_iter_parafac, tol, absolute_tol, nn_modes, A, B, C, P, errors, info, p, s);
+        });
     });
 }
 

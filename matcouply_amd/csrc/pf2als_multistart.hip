@@ -28,13 +28,14 @@
 #include <string>
 #include <vector>
 
+#include "entry_host.h"
 #include "mcl_internal.h"
 #include "wg_fp64.h"
 #include "xload.h"
 
 namespace {
 
-static std::string g_pm_error;
+static ErrorSlot g_pm_error;
 constexpr int PM_MAX_RANK = 16;
 constexpr int PM_SYS_BYTES = 40960;  // LDS for a batch of per-slab r x r polar steps (two r x r matrices per thread)
 constexpr double PM_DROP = 1e-12;    // eigenvalues at or below PM_DROP lam_max are dropped (polar factor, pseudo-inverse)
@@ -421,46 +422,15 @@ __global__ __launch_bounds__(MS_THREADS) void k_ms_pf2als_weighted(PmArgs a, con
 }
 #undef PM_START_LDS
 
-struct PmPlan {
-    int64_t N, scratch_len, off_rowptr, off_slab, off_scratch, total;
-};
-
 std::string pm_check(const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank, int32_t n_starts) {
-    if (!row_ptr || I < 1 || K < 1) return "need row_ptr, I >= 1, K >= 1";
-    if (rank < 1 || rank > PM_MAX_RANK) return "need 1 <= rank <= 16";
+    const std::string bad = packed_args_error(row_ptr, I, K, rank, PM_MAX_RANK);
+    if (!bad.empty()) return bad;
     if (n_starts < 1) return "need n_starts >= 1";
-    if (row_ptr[0] != 0) return "row_ptr[0] must be 0";
-    for (int64_t i = 0; i < I; ++i)
-        if (row_ptr[i + 1] - row_ptr[i] < rank) return "every matrix needs at least rank rows";
-    if (rank > K) return "rank exceeds K";
-    if (row_ptr[I] >= (int64_t(1) << 31)) return "more than 2^31 packed rows are not supported";
-    return "";
+    return packed_rows_error(row_ptr, I, K, rank, 31);
 }
 
-PmPlan pm_plan(const int64_t *row_ptr, int64_t I, int64_t K, int rank, int32_t n_starts) {
-    PmPlan p{};
-    p.N = row_ptr[I];
-    p.scratch_len = pm_scratch(I, p.N, K, rank).total;
-    auto al = [](int64_t b) { return (b + 255) & ~int64_t(255); };
-    p.off_rowptr = 0;
-    p.off_slab = al((I + 1) * 8);
-    p.off_scratch = p.off_slab + al(p.N * 4);
-    p.total = p.off_scratch + al(p.scratch_len * 8 * int64_t(n_starts));
-    return p;
-}
-
-template <class XL>
-void pm_launch(int rank, const PmArgs &a, const double *slab_scale, int n_starts, hipStream_t s) {
-    switch (rank) {
-#define PM_CASE(R)                                                                                                          \
-    case R:                                                                                                                 \
-        if (slab_scale) hipLaunchKernelGGL((k_ms_pf2als_weighted<R, XL>), dim3(n_starts), dim3(MS_THREADS), 0, s, a, slab_scale); \
-        else hipLaunchKernelGGL((k_ms_pf2als<R, XL>), dim3(n_starts), dim3(MS_THREADS), 0, s, a);                           \
-        break;
-        PM_CASE(1) PM_CASE(2) PM_CASE(3) PM_CASE(4) PM_CASE(5) PM_CASE(6) PM_CASE(7) PM_CASE(8)
-        PM_CASE(9) PM_CASE(10) PM_CASE(11) PM_CASE(12) PM_CASE(13) PM_CASE(14) PM_CASE(15) PM_CASE(16)
-#undef PM_CASE
-    }
+StartsPlan pm_plan(void *workspace, const int64_t *row_ptr, int64_t I, int64_t K, int rank, int32_t n_starts) {
+    return starts_plan(workspace, row_ptr, I, pm_scratch(I, row_ptr[I], K, rank).total, n_starts);
 }
 
 // mcl_pf2als_multistart_run (weighted false, slab_scale unused) and mcl_pf2als_multistart_run_weighted
@@ -468,45 +438,38 @@ int pm_run(const char *who, bool weighted, const double *slab_scale, const void 
            int64_t K, int32_t rank, int32_t n_starts, int32_t n_iter_max, int32_t n_iter_parafac, double tol, double absolute_tol,
            int32_t nn_modes, double *factors, double *P, double *errors, int32_t *n_iter, void *workspace, int64_t workspace_bytes,
            void *hip_stream) {
-    auto fail = [who](const std::string &m) {
-        g_pm_error = std::string(who) + ": " + m;
-        return 1;
-    };
+    ErrorSlot &fail = g_pm_error.named(who);
     const std::string bad = pm_check(row_ptr, I, K, rank, n_starts);
     if (!bad.empty()) return fail(bad);
     if (weighted && !slab_scale) return fail("slab_scale is NULL (a device array [n_starts, I] of the square roots of the weights)");
     if (!X || !factors || !P || !n_iter || !workspace || (tol > 0.0 && !errors)) return fail("NULL argument");
-    if (x_type != MCL_X_F32 && x_type != MCL_X_BF16 && x_type != MCL_X_F16)
-        return fail("unknown x_type " + std::to_string(x_type) + " (MCL_X_F32 = 0, MCL_X_BF16 = 1, MCL_X_F16 = 2)");
+    if (!x_type_error(x_type).empty()) return fail(x_type_error(x_type));
     if (nn_modes & ~5) return fail("nn_modes may hold modes 0 and 2 only (bits 1 and 4)");
     if (n_iter_max < 1 || n_iter_parafac < 1 || !(tol >= 0.0) || !(absolute_tol >= 0.0))
         return fail("need n_iter_max >= 1, n_iter_parafac >= 1, tol >= 0 and absolute_tol >= 0");
-    const PmPlan p = pm_plan(row_ptr, I, K, rank, n_starts);
-    if (workspace_bytes < p.total) return fail("workspace too small (mcl_pf2als_multistart_workspace_bytes)");
-    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail("workspace must be 256-byte aligned");
+    const StartsPlan p = pm_plan(workspace, row_ptr, I, K, rank, n_starts);
+    if (workspace_refused(fail, workspace, workspace_bytes, p.total, "mcl_pf2als_multistart_workspace_bytes")) return 1;
     hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
-    char *ws = static_cast<char *>(workspace);
-    std::vector<int32_t> slab(p.N);
-    for (int64_t i = 0; i < I; ++i)
-        for (int64_t j = row_ptr[i]; j < row_ptr[i + 1]; ++j) slab[j] = (int32_t)i;
-    if (hipMemcpyAsync(ws + p.off_rowptr, row_ptr, (I + 1) * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipMemcpyAsync(ws + p.off_slab, slab.data(), p.N * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess)
-        return fail("upload of row_ptr failed");
+    std::vector<int32_t> slab;
+    if (upload_starts(p, row_ptr, I, slab, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return fail("upload of row_ptr failed");
     PmArgs a{};
     a.X = X;
-    a.row_ptr = reinterpret_cast<const int64_t *>(ws + p.off_rowptr);
-    a.slab_of_row = reinterpret_cast<const int32_t *>(ws + p.off_slab);
+    a.row_ptr = p.row_ptr;
+    a.slab_of_row = p.slab_of_row;
     a.I = I, a.N = p.N, a.K = K;
-    a.scratch_len = p.scratch_len;
+    a.scratch_len = pm_scratch(I, p.N, K, rank).total;
     a.factors = factors, a.P = P, a.errors = tol > 0.0 ? errors : nullptr;
-    a.scratch = reinterpret_cast<double *>(ws + p.off_scratch);
+    a.scratch = p.scratch;
     a.n_iter = n_iter;
     a.n_iter_max = n_iter_max, a.n_iter_parafac = n_iter_parafac, a.nn_modes = nn_modes;
     a.tol = tol, a.absolute_tol = absolute_tol;
     mcl_x_dispatch(x_type, [&](auto xl) {
         using XL = decltype(xl);
-        pm_launch<XL>(rank, a, weighted ? slab_scale : nullptr, n_starts, s);
+        rank_exact<PM_MAX_RANK>(rank, [&](auto rc) {
+            constexpr int R = decltype(rc)::value;
+            if (weighted) hipLaunchKernelGGL((k_ms_pf2als_weighted<R, XL>), dim3(n_starts), dim3(MS_THREADS), 0, s, a, slab_scale);
+            else hipLaunchKernelGGL((k_ms_pf2als<R, XL>), dim3(n_starts), dim3(MS_THREADS), 0, s, a);
+        });
         return 0;
     });
     const hipError_t e = hipGetLastError();
@@ -522,14 +485,14 @@ const char *mcl_pf2als_multistart_last_error(void) { return g_pm_error.c_str(); 
 
 int64_t mcl_pf2als_multistart_workspace_bytes(const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank, int32_t n_starts) {
     if (!pm_check(row_ptr, I, K, rank, n_starts).empty()) return -1;
-    return pm_plan(row_ptr, I, K, rank, n_starts).total;
+    return pm_plan(nullptr, row_ptr, I, K, rank, n_starts).total;
 }
 
 int mcl_pf2als_multistart_run(const void *X, int32_t x_type, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank, int32_t n_starts,
                               int32_t n_iter_max, int32_t n_iter_parafac, double tol, double absolute_tol, int32_t nn_modes,
                               double *factors, double *P, double *errors, int32_t *n_iter, void *workspace, int64_t workspace_bytes,
                               void *hip_stream) {
-    return pm_run("mcl_pf2als_multistart_run", false, nullptr, X, x_type, row_ptr, I, K, rank, n_starts, n_iter_max, n_iter_parafac, tol,
+    return pm_run("mcl_pf2als_multistart_run: ", false, nullptr, X, x_type, row_ptr, I, K, rank, n_starts, n_iter_max, n_iter_parafac, tol,
                   absolute_tol, nn_modes, factors, P, errors, n_iter, workspace, workspace_bytes, hip_stream);
 }
 
@@ -537,7 +500,7 @@ int mcl_pf2als_multistart_run_weighted(const void *X, int32_t x_type, const int6
                                        int32_t n_starts, const double *slab_scale, int32_t n_iter_max, int32_t n_iter_parafac, double tol,
                                        double absolute_tol, int32_t nn_modes, double *factors, double *P, double *errors, int32_t *n_iter,
                                        void *workspace, int64_t workspace_bytes, void *hip_stream) {
-    return pm_run("mcl_pf2als_multistart_run_weighted", true, slab_scale, X, x_type, row_ptr, I, K, rank, n_starts, n_iter_max,
+    return pm_run("mcl_pf2als_multistart_run_weighted: ", true, slab_scale, X, x_type, row_ptr, I, K, rank, n_starts, n_iter_max,
                   n_iter_parafac, tol, absolute_tol, nn_modes, factors, P, errors, n_iter, workspace, workspace_bytes, hip_stream);
 }
 

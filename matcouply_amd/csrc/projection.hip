@@ -19,7 +19,7 @@
 
 namespace {
 
-static std::string g_project_error;
+static ErrorSlot g_project_error{"mcl_pf2_project: "};
 constexpr int PJ_MAX_RANK = 32;
 
 // ---- set-up (one workgroup): Cfrag (zeroed by the caller) from C, H = C^T C -----------------------------------------------------
@@ -296,26 +296,30 @@ __global__ __launch_bounds__(256) void k_proj_out(const float *__restrict__ W, c
 }
 
 struct PjPlan {
-    int64_t N;
+    int64_t N, total;
     int nseg, NB, KH;
-    int64_t off_segs, off_ext, off_Cfrag, off_H, off_Delta, off_W, off_T, total;
+    int4 *segs;
+    int *ext;
+    float *Cfrag, *W;
+    double *H, *Delta, *T;
 };
 
-PjPlan pj_plan(const int64_t *row_ptr, int64_t I, int64_t K, int rank) {
+// workspace NULL: the parts are null and `total` is the size (mcl_pf2_project_workspace_bytes)
+PjPlan pj_plan(void *workspace, const int64_t *row_ptr, int64_t I, int64_t K, int rank) {
     PjPlan p{};
     p.N = row_ptr[I];
     const int64_t nseg = seg_count(row_ptr, I), r = rank;
     p.nseg = (int)nseg;
     p.NB = rank <= 16 ? 1 : 2;
     p.KH = 4 * (int)((K + 63) / 64);
-    WsCursor ws;
-    p.off_segs = ws.take(std::max<int64_t>(nseg, 1) * 16);
-    p.off_ext = ws.take((I + 1) * 4);
-    p.off_Cfrag = ws.take((int64_t)p.KH * p.NB * 64 * 4 * 4);
-    p.off_H = ws.take(r * r * 8);
-    p.off_Delta = ws.take(r * r * 8);
-    p.off_W = ws.take(p.N * r * 4);
-    p.off_T = ws.take(I * 2 * r * r * 8);
+    WsCursor ws(workspace);
+    p.segs = ws.take<int4>(std::max<int64_t>(nseg, 1) * 16);
+    p.ext = ws.take<int>((I + 1) * 4);
+    p.Cfrag = ws.take<float>((int64_t)p.KH * p.NB * 64 * 4 * 4);
+    p.H = ws.take<double>(r * r * 8);
+    p.Delta = ws.take<double>(r * r * 8);
+    p.W = ws.take<float>(p.N * r * 4);
+    p.T = ws.take<double>(I * 2 * r * r * 8);
     p.total = ws.off;
     return p;
 }
@@ -332,27 +336,12 @@ std::string pj_check_shape(const int64_t *row_ptr, int64_t I, int64_t K, int32_t
     return "";
 }
 
-template <class XL, int NB, bool VEC>
-void pj_launch_xc(const typename XL::T *X, const PjPlan &p, const int4 *segs, int K, int r, const float *Cfrag, float *W, hipStream_t s) {
-    hipLaunchKernelGGL((k_proj_xc<XL, NB, VEC>), dim3((unsigned)((p.nseg + 3) / 4)), dim3(256), 0, s, X, segs, p.nseg, K, r, Cfrag, W);
-}
-
 template <class XL, int RMAX>
 int pj_run(const typename XL::T *X, int32_t x_type, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank, const double *Delta,
            const double *C, const double *a_init, int32_t n_iter_max, double tol, double absolute_tol, double *A, float *B, float *P,
-           double *stats, int32_t *n_iter, double *errors, void *workspace, hipStream_t s) {
+           double *stats, int32_t *n_iter, double *errors, const PjPlan &p, hipStream_t s) {
     constexpr int NB = RMAX / 16;
-    auto fail = [](const std::string &msg) {
-        g_project_error = "mcl_pf2_project: " + msg;
-        return 1;
-    };
-    const PjPlan p = pj_plan(row_ptr, I, K, rank);
-    char *ws = static_cast<char *>(workspace);
-    int4 *segs = reinterpret_cast<int4 *>(ws + p.off_segs);
-    int *ext = reinterpret_cast<int *>(ws + p.off_ext);
-    float *Cfrag = reinterpret_cast<float *>(ws + p.off_Cfrag), *W = reinterpret_cast<float *>(ws + p.off_W);
-    double *H = reinterpret_cast<double *>(ws + p.off_H), *Dl = reinterpret_cast<double *>(ws + p.off_Delta);
-    double *Tm = reinterpret_cast<double *>(ws + p.off_T);
+    ErrorSlot &fail = g_project_error;
     const int r = rank;
 
     // the model and the start are read back and checked before anything is launched
@@ -369,20 +358,21 @@ int pj_run(const typename XL::T *X, int32_t x_type, const int64_t *row_ptr, int6
                                (int)pj_lds_bytes(RMAX)));
 
     const SegTables tb = seg_tables(row_ptr, I);
-    CP_HIP(hipMemcpyAsync(segs, tb.segs.data(), sizeof(int4) * tb.segs.size(), hipMemcpyHostToDevice, s));
-    CP_HIP(hipMemcpyAsync(ext, tb.ext.data(), sizeof(int) * tb.ext.size(), hipMemcpyHostToDevice, s));
-    CP_HIP(hipMemsetAsync(Cfrag, 0, (size_t)p.KH * p.NB * 64 * 4 * 4, s));
-    CP_HIP(hipMemcpyAsync(Dl, Delta, sizeof(double) * r * r, hipMemcpyDeviceToDevice, s));
+    CP_HIP(upload_tables(tb, p.segs, nullptr, p.ext, s));
+    CP_HIP(hipMemsetAsync(p.Cfrag, 0, (size_t)p.KH * p.NB * 64 * 4 * 4, s));
+    CP_HIP(hipMemcpyAsync(p.Delta, Delta, sizeof(double) * r * r, hipMemcpyDeviceToDevice, s));
     CP_HIP(hipStreamSynchronize(s));  // (the tables are locals)
 
-    hipLaunchKernelGGL(k_proj_setup, dim3(1), dim3(256), 0, s, C, (int)K, r, NB, Cfrag, H);
-    hipLaunchKernelGGL(k_proj_norm<XL>, dim3((unsigned)I), dim3(256), 0, s, X, (const int *)ext, (int)K, stats);
-    if (K % 4 == 0 && mcl_x_vec_aligned(X, x_type)) pj_launch_xc<XL, NB, true>(X, p, segs, (int)K, r, Cfrag, W, s);
-    else pj_launch_xc<XL, NB, false>(X, p, segs, (int)K, r, Cfrag, W, s);
-    hipLaunchKernelGGL((k_proj_iterate<XL, RMAX>), dim3((unsigned)I), dim3(256), lds, s, X, C, (int)K, (const float *)W, (const int *)ext, r, (const double *)Dl,
-                       (const double *)H, a_init, (int)n_iter_max, tol, absolute_tol, A, Tm, stats, n_iter, errors);
-    hipLaunchKernelGGL(k_proj_out, dim3((unsigned)((p.N * r + 255) / 256)), dim3(256), 0, s, (const float *)W, (const double *)Tm,
-                       (const int *)ext, (int)I, (long)p.N, r, P, B);
+    hipLaunchKernelGGL(k_proj_setup, dim3(1), dim3(256), 0, s, C, (int)K, r, NB, p.Cfrag, p.H);
+    hipLaunchKernelGGL(k_proj_norm<XL>, dim3((unsigned)I), dim3(256), 0, s, X, (const int *)p.ext, (int)K, stats);
+    vec_dispatch(K % 4 == 0 && mcl_x_vec_aligned(X, x_type), [&](auto vec) {
+        hipLaunchKernelGGL((k_proj_xc<XL, NB, decltype(vec)::value>), dim3((unsigned)((p.nseg + 3) / 4)), dim3(256), 0, s, X, (const int4 *)p.segs,
+                           p.nseg, (int)K, r, (const float *)p.Cfrag, p.W);
+    });
+    hipLaunchKernelGGL((k_proj_iterate<XL, RMAX>), dim3((unsigned)I), dim3(256), lds, s, X, C, (int)K, (const float *)p.W, (const int *)p.ext, r,
+                       (const double *)p.Delta, (const double *)p.H, a_init, (int)n_iter_max, tol, absolute_tol, A, p.T, stats, n_iter, errors);
+    hipLaunchKernelGGL(k_proj_out, dim3((unsigned)((p.N * r + 255) / 256)), dim3(256), 0, s, (const float *)p.W, (const double *)p.T,
+                       (const int *)p.ext, (int)I, (long)p.N, r, P, B);
     CP_HIP(hipGetLastError());
     return 0;
 }
@@ -395,33 +385,28 @@ const char *mcl_pf2_project_last_error(void) { return g_project_error.c_str(); }
 
 int64_t mcl_pf2_project_workspace_bytes(const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank) {
     if (!pj_check_shape(row_ptr, I, K, rank).empty()) return -1;
-    return pj_plan(row_ptr, I, K, rank).total;
+    return pj_plan(nullptr, row_ptr, I, K, rank).total;
 }
 
 int mcl_pf2_project_typed(const void *X, int32_t x_type, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank, const double *Delta,
                           const double *C, const double *a_init, int32_t n_iter_max, double tol, double absolute_tol, double *A, float *B,
                           float *P, double *stats, int32_t *n_iter, double *errors, void *workspace, int64_t workspace_bytes,
                           void *hip_stream) {
-    auto fail = [](const std::string &msg) {
-        g_project_error = "mcl_pf2_project: " + msg;
-        return 1;
-    };
+    ErrorSlot &fail = g_project_error;
     const std::string bad = pj_check_shape(row_ptr, I, K, rank);
     if (!bad.empty()) return fail(bad);
     if (!X || !Delta || !C || !a_init || !A || !B || !P || !stats || !n_iter || !workspace) return fail("NULL argument");
     if (!x_type_error(x_type).empty()) return fail(x_type_error(x_type));
     if (n_iter_max < 1 || !(tol >= 0.0) || !(absolute_tol >= 0.0)) return fail("need n_iter_max >= 1, tol >= 0 and absolute_tol >= 0");
-    if (workspace_bytes < pj_plan(row_ptr, I, K, rank).total) return fail("workspace too small (mcl_pf2_project_workspace_bytes)");
-    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail("workspace must be 256-byte aligned");
+    const PjPlan p = pj_plan(workspace, row_ptr, I, K, rank);
+    if (workspace_refused(fail, workspace, workspace_bytes, p.total, "mcl_pf2_project_workspace_bytes")) return 1;
     hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
     return mcl_x_dispatch(x_type, [&](auto xl) {
         using XL = decltype(xl);
-        const auto *Xt = static_cast<const typename XL::T *>(X);
-        if (rank <= 16)
-            return pj_run<XL, 16>(Xt, x_type, row_ptr, I, K, rank, Delta, C, a_init, n_iter_max, tol, absolute_tol, A, B, P, stats, n_iter,
-                                  errors, workspace, s);
-        return pj_run<XL, 32>(Xt, x_type, row_ptr, I, K, rank, Delta, C, a_init, n_iter_max, tol, absolute_tol, A, B, P, stats, n_iter,
-                              errors, workspace, s);
+        return rank_bucket(rank, [&](auto rmax) {
+            return pj_run<XL, decltype(rmax)::value>(static_cast<const typename XL::T *>(X), x_type, row_ptr, I, K, rank, Delta, C, a_init,
+                                                     n_iter_max, tol, absolute_tol, A, B, P, stats, n_iter, errors, p, s);
+        });
     });
 }
 

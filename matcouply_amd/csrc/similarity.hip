@@ -20,11 +20,12 @@
 #include <cmath>
 #include <string>
 
+#include "entry_host.h"
 #include "mcl_internal.h"
 
 namespace {
 
-static std::string g_fms_error;
+static ErrorSlot g_fms_error{"mcl_fms_scores: "};
 constexpr int FMS_MAX_RANK = 16;
 constexpr int FMS_WS_DOUBLES = 64;  // per model: inv_norm[3][16], w[16]
 constexpr int FMS_WAVES = 4;        // pairs per workgroup
@@ -208,10 +209,7 @@ int64_t mcl_fms_workspace_bytes(int64_t n_models, int32_t rank) {
 int mcl_fms_scores(const double *models, int64_t n_models, int64_t I, int64_t N, int64_t K, int32_t rank, const double *weights,
                    const int32_t *pairs, int64_t n_pairs, int32_t flags, int32_t skip_mode, double *score, int32_t *perm,
                    void *workspace, void *hip_stream) {
-    auto fail = [](const std::string &m) {
-        g_fms_error = "mcl_fms_scores: " + m;
-        return 1;
-    };
+    ErrorSlot &fail = g_fms_error;
     const std::string bad = fms_check(n_models, rank);
     if (!bad.empty()) return fail(bad);
     if (I < 1 || N < 1 || K < 1) return fail("need I >= 1, N >= 1 and K >= 1");
@@ -220,7 +218,7 @@ int mcl_fms_scores(const double *models, int64_t n_models, int64_t I, int64_t N,
     if (flags & ~3) return fail("flags may hold bit 0 (consider_weights) and bit 1 (absolute_value) only");
     if (skip_mode < -1 || skip_mode > 2) return fail("skip_mode must be -1 (none), 0, 1 or 2");
     if (!models || !workspace || (n_pairs > 0 && (!pairs || !score))) return fail("NULL argument");
-    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail("workspace must be 256-byte aligned");
+    if (workspace_refused(fail, workspace, 0, 0, nullptr)) return 1;  // (no size argument: mcl_fms_workspace_bytes(n_models, rank))
     for (int64_t i = 0; i < 2 * n_pairs; ++i)
         if (pairs[i] < 0 || pairs[i] >= n_models)
             return fail("pair " + std::to_string(i / 2) + " names model " + std::to_string(pairs[i]) + " of " + std::to_string(n_models));

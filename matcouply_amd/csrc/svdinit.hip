@@ -18,6 +18,7 @@
 #include <string>
 #include <vector>
 
+#include "entry_host.h"
 #include "mcl_internal.h"
 #include "symeig_lds.h"
 #include "xload.h"
@@ -26,7 +27,7 @@ namespace {
 
 constexpr int SVD_OVERSAMPLE = 8;
 constexpr int SVD_MAX_IT = 400;
-static std::string g_svd_error;
+static ErrorSlot g_svd_error;
 
 inline int svd_m(int64_t K, int rank) { return (int)std::min<int64_t>(K, rank + SVD_OVERSAMPLE); }
 
@@ -285,35 +286,29 @@ __global__ __launch_bounds__(256) void k_svd_right(const double *__restrict__ Q,
 
 struct SvdPlan {
     int m, BS;
-    int64_t off_ext, off_G, off_Gstack, off_Q, off_Y, off_theta, off_U, total;
+    int *ext;
+    double *G, *Gstack, *Q, *Y, *theta, *U;
+    int64_t total;
 };
 
-SvdPlan svd_plan(int64_t I, int64_t K, int rank, int64_t max_batch_rows) {
+// workspace NULL: the parts are null and `total` is the size (mcl_svd_init_workspace_bytes)
+SvdPlan svd_plan(void *workspace, const int64_t *row_ptr, int64_t I, int64_t K, int rank) {
     SvdPlan p{};
     p.m = svd_m(K, rank);
     p.BS = (int)std::min<int64_t>(std::max<int64_t>(I, 1), 256);
     while (p.BS > 1 && (int64_t)p.BS * K * K * 8 > (int64_t(2) << 30)) p.BS /= 2;  // <= 2 GiB of Gram matrices at a time
-    int64_t off = 0;
-    auto take = [&](int64_t bytes) {
-        const int64_t o = off;
-        off = (off + bytes + 255) & ~int64_t(255);
-        return o;
-    };
-    p.off_ext = take((I + 1) * 4);
-    p.off_G = take((int64_t)p.BS * K * K * 8);
-    p.off_Gstack = take(K * K * 8);
-    p.off_Q = take((int64_t)p.BS * K * p.m * 8);
-    p.off_Y = take((int64_t)p.BS * K * p.m * 8);
-    p.off_theta = take((int64_t)p.BS * p.m * 8);
-    p.off_U = take(std::max<int64_t>(max_batch_rows, 1) * rank * 8);
-    p.total = off;
+    int64_t max_batch_rows = 1;
+    for (int64_t b0 = 0; b0 < I; b0 += p.BS) max_batch_rows = std::max(max_batch_rows, row_ptr[std::min<int64_t>(I, b0 + p.BS)] - row_ptr[b0]);
+    WsCursor ws(workspace);
+    p.ext = ws.take<int>((I + 1) * 4);
+    p.G = ws.take<double>((int64_t)p.BS * K * K * 8);
+    p.Gstack = ws.take<double>(K * K * 8);
+    p.Q = ws.take<double>((int64_t)p.BS * K * p.m * 8);
+    p.Y = ws.take<double>((int64_t)p.BS * K * p.m * 8);
+    p.theta = ws.take<double>((int64_t)p.BS * p.m * 8);
+    p.U = ws.take<double>(max_batch_rows * rank * 8);
+    p.total = ws.off;
     return p;
-}
-
-int64_t max_batch_rows_of(const int64_t *row_ptr, int64_t I, int BS) {
-    int64_t mx = 0;
-    for (int64_t b0 = 0; b0 < I; b0 += BS) mx = std::max(mx, row_ptr[std::min<int64_t>(I, b0 + BS)] - row_ptr[b0]);
-    return mx;
 }
 
 }  // namespace
@@ -324,8 +319,7 @@ const char *mcl_svd_init_last_error(void) { return g_svd_error.c_str(); }
 
 int64_t mcl_svd_init_workspace_bytes(const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank) {
     if (!row_ptr || I < 1 || K < 1 || rank < 1) return -1;
-    const SvdPlan p0 = svd_plan(I, K, rank, 1);
-    return svd_plan(I, K, rank, max_batch_rows_of(row_ptr, I, p0.BS)).total;
+    return svd_plan(nullptr, row_ptr, I, K, rank).total;
 }
 
 }  // extern "C"
@@ -335,55 +329,40 @@ int64_t mcl_svd_init_workspace_bytes(const int64_t *row_ptr, int64_t I, int64_t 
 template <class XL>
 static int svd_init(const typename XL::T *X, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank, int32_t threshold, float *B,
                     float *C, void *workspace, int64_t workspace_bytes, int32_t *info, void *hip_stream, bool slabs = true) {
-    auto fail = [](const std::string &msg) {
-        g_svd_error = msg;
-        return 1;
-    };
-    if (!X || !row_ptr || (slabs && !B) || !C || !workspace || !info) return fail("mcl_svd_init: NULL argument");
-    if (I < 1 || K < 1 || rank < 1 || rank > MCL_MAX_RANK) return fail("mcl_svd_init: need I >= 1, K >= 1, 1 <= rank <= 64");
-    if (rank > K) return fail("mcl_svd_init: rank exceeds the number of columns");
+    ErrorSlot &refuse = g_svd_error.named("mcl_svd_init: ");
+    auto fail = [](const std::string &msg) { return g_svd_error.as_is(msg); };  // (a HIP call's message names the call)
+    if (!X || !row_ptr || (slabs && !B) || !C || !workspace || !info) return refuse("NULL argument");
+    if (I < 1 || K < 1 || rank < 1 || rank > MCL_MAX_RANK) return refuse("need I >= 1, K >= 1, 1 <= rank <= 64");
+    if (rank > K) return refuse("rank exceeds the number of columns");
     for (int64_t i = 0; i < I && slabs; ++i)
-        if (row_ptr[i + 1] - row_ptr[i] < rank) return fail("mcl_svd_init: a matrix has fewer rows than the rank");
-    if (row_ptr[I] >= (int64_t(1) << 31)) return fail("mcl_svd_init: more than 2^31 packed rows are not supported");
-    const SvdPlan p0 = svd_plan(I, K, rank, 1);
-    const SvdPlan p = svd_plan(I, K, rank, max_batch_rows_of(row_ptr, I, p0.BS));
-    if (workspace_bytes < p.total) return fail("mcl_svd_init: workspace too small (mcl_svd_init_workspace_bytes)");
-    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail("mcl_svd_init: workspace must be 256-byte aligned");
+        if (row_ptr[i + 1] - row_ptr[i] < rank) return refuse("a matrix has fewer rows than the rank");
+    if (row_ptr[I] >= (int64_t(1) << 31)) return refuse("more than 2^31 packed rows are not supported");
+    const SvdPlan p = svd_plan(workspace, row_ptr, I, K, rank);
+    if (workspace_refused(refuse, workspace, workspace_bytes, p.total, "mcl_svd_init_workspace_bytes")) return 1;
     hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
-    char *ws = static_cast<char *>(workspace);
-    int *ext = reinterpret_cast<int *>(ws + p.off_ext);
-    double *G = reinterpret_cast<double *>(ws + p.off_G), *Gstack = reinterpret_cast<double *>(ws + p.off_Gstack);
-    double *Q = reinterpret_cast<double *>(ws + p.off_Q), *Y = reinterpret_cast<double *>(ws + p.off_Y);
-    double *theta = reinterpret_cast<double *>(ws + p.off_theta), *U = reinterpret_cast<double *>(ws + p.off_U);
     std::vector<int> h_ext((size_t)I + 1);
     for (int64_t i = 0; i <= I; ++i) h_ext[(size_t)i] = (int)row_ptr[i];
-#define SVD_HIP(expr)                                                                  \
-    do {                                                                               \
-        const hipError_t e_ = (expr);                                                  \
-        if (e_ != hipSuccess) return fail(std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-    SVD_HIP(hipMemcpyAsync(ext, h_ext.data(), sizeof(int) * ((size_t)I + 1), hipMemcpyHostToDevice, s));
-    SVD_HIP(hipStreamSynchronize(s));  // (h_ext is a local)
+    CP_HIP(upload(p.ext, h_ext, s));
+    CP_HIP(hipStreamSynchronize(s));  // (h_ext is a local)
     const int m = p.m;
     const size_t sm = sizeof(double) * (size_t)(2 * m * m + m + 2 * ((m + 1) / 2 + 1) + m) + sizeof(int) * (size_t)m + 64;
-    SVD_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_svd_subspace), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm));
+    CP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_svd_subspace), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm));
     const int tiles = (int)((K + 31) / 32);
     const long KK = (long)K * K;
     for (int64_t b0 = 0; b0 < I; b0 += p.BS) {
         const int nb = (int)std::min<int64_t>(p.BS, I - b0);
-        hipLaunchKernelGGL((MCL_XKERNEL0(k_svd_gram)), dim3((unsigned)tiles, (unsigned)tiles, (unsigned)nb), dim3(256), 0, s, X, (const int *)ext, (int)b0,
-                           (int)K, G);
-        hipLaunchKernelGGL(k_svd_add, dim3((unsigned)((KK + 255) / 256)), dim3(256), 0, s, (const double *)G, nb, KK, Gstack, b0 == 0 ? 1 : 0);
+        hipLaunchKernelGGL((MCL_XKERNEL0(k_svd_gram)), dim3((unsigned)tiles, (unsigned)tiles, (unsigned)nb), dim3(256), 0, s, X, (const int *)p.ext, (int)b0,
+                           (int)K, p.G);
+        hipLaunchKernelGGL(k_svd_add, dim3((unsigned)((KK + 255) / 256)), dim3(256), 0, s, (const double *)p.G, nb, KK, p.Gstack, b0 == 0 ? 1 : 0);
         if (!slabs) continue;
-        hipLaunchKernelGGL(k_svd_subspace, dim3((unsigned)nb), dim3(256), sm, s, (const double *)G, (int)K, m, (int)rank, Q, Y, theta, info,
+        hipLaunchKernelGGL(k_svd_subspace, dim3((unsigned)nb), dim3(256), sm, s, (const double *)p.G, (int)K, m, (int)rank, p.Q, p.Y, p.theta, info,
                            (int)b0);
-        hipLaunchKernelGGL((MCL_XKERNEL0(k_svd_left)), dim3((unsigned)nb), dim3(256), 0, s, X, (const int *)ext, (int)b0, (int)K, m, (int)rank,
-                           (const double *)Q, U, (long)row_ptr[b0], (int)threshold, B);
+        hipLaunchKernelGGL((MCL_XKERNEL0(k_svd_left)), dim3((unsigned)nb), dim3(256), 0, s, X, (const int *)p.ext, (int)b0, (int)K, m, (int)rank,
+                           (const double *)p.Q, p.U, (long)row_ptr[b0], (int)threshold, B);
     }
-    hipLaunchKernelGGL(k_svd_subspace, dim3(1), dim3(256), sm, s, (const double *)Gstack, (int)K, m, (int)rank, Q, Y, theta, info, (int)I);
-    hipLaunchKernelGGL(k_svd_right, dim3(1), dim3(256), 0, s, (const double *)Q, (int)K, m, (int)rank, (int)threshold, C);
-    SVD_HIP(hipGetLastError());
-#undef SVD_HIP
+    hipLaunchKernelGGL(k_svd_subspace, dim3(1), dim3(256), sm, s, (const double *)p.Gstack, (int)K, m, (int)rank, p.Q, p.Y, p.theta, info, (int)I);
+    hipLaunchKernelGGL(k_svd_right, dim3(1), dim3(256), 0, s, (const double *)p.Q, (int)K, m, (int)rank, (int)threshold, C);
+    CP_HIP(hipGetLastError());
     return 0;
 }
 
@@ -396,10 +375,7 @@ int mcl_svd_init(const float *X, const int64_t *row_ptr, int64_t I, int64_t K, i
 
 int mcl_svd_init_typed(const void *X, int32_t x_type, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank, int32_t threshold,
                        float *B, float *C, void *workspace, int64_t workspace_bytes, int32_t *info, void *hip_stream) {
-    if (x_type != MCL_X_F32 && x_type != MCL_X_BF16 && x_type != MCL_X_F16) {
-        g_svd_error = "mcl_svd_init_typed: unknown x_type " + std::to_string(x_type) + " (MCL_X_F32 = 0, MCL_X_BF16 = 1, MCL_X_F16 = 2)";
-        return 1;
-    }
+    if (!x_type_error(x_type).empty()) return g_svd_error.named("mcl_svd_init_typed: ").fail(x_type_error(x_type));
     return mcl_x_dispatch(x_type, [&](auto xl) {
         using XL = decltype(xl);
         return svd_init<XL>(static_cast<const typename XL::T *>(X), row_ptr, I, K, rank, threshold, B, C, workspace, workspace_bytes,
@@ -421,7 +397,7 @@ int mcl_svd_stack_right(const void *X, int32_t x_type, const int64_t *row_ptr, i
         return svd_init<XL>(static_cast<const typename XL::T *>(X), row_ptr, I, K, rank, threshold, nullptr, C, workspace,
                             workspace_bytes, info, stream, false);
     });
-    if (rc) err = g_svd_error;
+    if (rc) err = g_svd_error.text;
     return rc;
 }
 
