@@ -822,7 +822,7 @@ int mcl_launch_rows_fused(mcl_context *c, int mode) {
         rc = mcl_rows_fused_dispatch(c, mode, diag);
     }
     if (rc < 0) return rc;
-    c->diag_rows[mode] = (((mode == 1) ? c->tilesB.n_tiles : c->tilesC.n_tiles) + 3) / 4;  // one row per block
+    c->bp.diag_rows[mode] = (((mode == 1) ? c->tilesB.n_tiles : c->tilesC.n_tiles) + 3) / 4;  // one row per block
     MCL_CHECK_HIP(c, hipGetLastError());
     return 0;
 }
@@ -852,7 +852,7 @@ static int launch_C_fused_t(mcl_context *c) {
 #undef MCL_CF
     MCL_CHECK_HIP(c, hipGetLastError());
     c->variant[MCL_PROF_C_FINISH] = "k_C_finish_fused<NBR=" + std::to_string(NBR) + ",NREG=" + std::to_string(NREG) + ">";
-    c->diag_rows[2] = 1;
+    c->bp.diag_rows[2] = 1;
     return 0;
 }
 
@@ -947,9 +947,9 @@ __global__ __launch_bounds__(256) void k_ctc_fold(const double *__restrict__ CtC
 
 int mcl_launch_ctc_fold(mcl_context *c) {
     ProfScope prof_(c, MCL_PROF_OTHER);
-    hipLaunchKernelGGL(k_ctc_fold, dim3(1), dim3(256), 0, c->stream, c->CtCpart, c->ctc_parts, c->r, c->CtC, c->CtC64);
+    hipLaunchKernelGGL(k_ctc_fold, dim3(1), dim3(256), 0, c->stream, c->CtCpart, c->bp.ctc_parts, c->r, c->CtC, c->CtC64);
     MCL_CHECK_HIP(c, hipGetLastError());
-    c->ctc_parts = 0;
+    c->bp.ctc_parts = 0;
     return 0;
 }
 
@@ -967,8 +967,8 @@ static int launch_C_multi_t(mcl_context *c) {
 #undef MCL_CM
     MCL_CHECK_HIP(c, hipGetLastError());
     c->variant[MCL_PROF_C_FINISH] = "k_C_finish_multi<NREG=" + std::to_string(NREG) + ">";
-    c->diag_rows[2] = nblk;
-    c->ctc_parts = nblk;
+    c->bp.diag_rows[2] = nblk;
+    c->bp.ctc_parts = nblk;
     return 0;
 }
 
@@ -977,7 +977,7 @@ int mcl_launch_C_finish_fused(mcl_context *c) {
     if (c->K > 1024 || c->sw.no_fused_c) return -1;
     if ((size_t)(c->r * c->r + c->K * c->r) * sizeof(float) > 150 * 1024) return -1;
     const int n = c->regs[2].n;
-    c->ctc_parts = 0;
+    c->bp.ctc_parts = 0;
     // rank <= 16 and at least two 64-row chunks: one workgroup per chunk (k_C_finish_multi); the
     // fragment image is then the one of the sweep / X C kernels with NB = 1
     if (c->r <= 16 && n <= 2 && c->K >= 128 && c->NB == 1 && !c->sw.no_multi_c &&

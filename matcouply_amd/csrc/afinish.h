@@ -795,12 +795,13 @@ int mcl_launch_A_finish(mcl_context *c, bool fuse_inner) {
     const bool rows_kernel = mcl_a_finish_rows(c);
     // (a B-phase with fp64 row passes also needs the fp64 inverses: only the row-split kernels write them)
     const bool b_needs_64 = mcl_rows64(c) || c->exact;  // the B-phase reads the fp64 inverses (fp64 row passes / wide.hip)
-    const bool seg = c->use_seg_gram;
+    const APlan &plan = c->a_plan;
+    const bool seg = plan.use_seg_gram;
     // the kernels' arguments under the kernels' names (AF_PARAMS), handed over with AF_ARGS
     float *BtB = c->BtB, *rhoA = c->rhoA, *LinvA = c->LinvA, *A = c->A, *rhoB = c->rhoB, *LinvB = c->LinvB, *rhsA_out = c->rhsA;
-    const double *CtC = c->CtC64, *seg_rhs = c->seg_rhs, *seg_btb = (seg && c->seg_from_sweep) ? c->part_btb : c->seg_btb;
+    const double *CtC = c->CtC64, *seg_rhs = c->seg_rhs, *seg_btb = (seg && plan.seg_from_sweep) ? c->part_btb : c->seg_btb;
     const float *rho_max = c->rho_max;
-    const int *slab_seg_ptr = seg ? (c->seg_from_sweep ? c->slab_part_ptr : c->slab_seg_ptr) : nullptr;
+    const int *slab_seg_ptr = seg ? (plan.seg_from_sweep ? c->slab_part_ptr : c->slab_seg_ptr) : nullptr;
     const int I = (int)c->I, r = c->r, constant = c->opt.constant_A, inner = c->opt.inner_n_iter_max, n_regs_B = c->regs[1].n;
     const int fused_inner = fuse_inner ? 1 : 0;
     const float scale = (float)c->opt.feasibility_penalty_scale, l2 = (float)c->opt.l2_penalty[0], l2_B = (float)c->opt.l2_penalty[1];
@@ -811,15 +812,15 @@ int mcl_launch_A_finish(mcl_context *c, bool fuse_inner) {
                         (rows_kernel || !b_needs_64)) ? 1 : 0;
     // what the row-split kernel absorbs: rhs_i from the sweep's M_bseg
     AFuse F{};
-    F.ctc_parts = c->ctc_parts, F.CtCpart = c->CtCpart, F.CtC64_out = c->CtC64, F.CtC_out = c->CtC;
-    if (c->a_rhs_from_M) {
+    F.ctc_parts = c->bp.ctc_parts, F.CtCpart = c->CtCpart, F.CtC64_out = c->CtC64, F.CtC_out = c->CtC;
+    if (plan.rhs_from_M) {
         F.Mpart = c->Mpart, F.Cfrag = c->CfragS, F.NBm = c->NB;
         F.MS = mcl_sweep_KC(c) * 64 * 16 * c->NB;
     }
     F.LinvB64 = b_needs_64 ? c->LinvB64 : nullptr;
     F.LinvA64 = c->LinvA64, F.rhsA64 = c->rhsA64, F.Q64 = c->Q64;  // (allocated in the exact-products mode only)
     F.wide_inner = (c->exact && !c->sw.no_wide) ? 1 : 0;
-    if (!rows_kernel && c->ctc_parts > 0)
+    if (!rows_kernel && c->bp.ctc_parts > 0)
         if (int rc = mcl_launch_ctc_fold(c)) return rc;
     const dim3 block(256), per_wave((unsigned)((c->I + 3) / 4)), per_pair((unsigned)((c->I + 1) / 2)), per_slab((unsigned)c->I);
     bool launched;
@@ -831,9 +832,9 @@ int mcl_launch_A_finish(mcl_context *c, bool fuse_inner) {
     } else {
         launched = dispatch_rp<8, 16, 32>(c->RP, [&](auto rp) {
             constexpr int RP = decltype(rp)::value;
-            if (c->a_rhs_wide && c->a_rhs_pairs)  // two slabs per workgroup (one partial per slab, many slabs)
+            if (plan.rhs_wide && plan.rhs_pairs)  // two slabs per workgroup (one partial per slab, many slabs)
                 hipLaunchKernelGGL((k_A_finish_rows_wide<RP, 2>), per_pair, block, 0, c->stream, AF_ARGS);
-            else if (c->a_rhs_wide)
+            else if (plan.rhs_wide)
                 hipLaunchKernelGGL((k_A_finish_rows_wide<RP, 1>), per_slab, block, 0, c->stream, AF_ARGS);
             else
                 hipLaunchKernelGGL((k_A_finish_rows<RP>), per_wave, block, 0, c->stream, AF_ARGS);
@@ -844,10 +845,10 @@ int mcl_launch_A_finish(mcl_context *c, bool fuse_inner) {
         return 1;
     }
     MCL_CHECK_HIP(c, hipGetLastError());
-    c->a64_valid = !fuse_inner && c->Q64 != nullptr;  // rhsA64 / Q64 / LinvA64 hold this phase's systems
-    c->variant[MCL_PROF_A_FINISH] = !rows_kernel ? "k_A_finish" : (c->a_rhs_wide ? (c->a_rhs_pairs ? "k_A_finish_rows_wide<SPB=2>" : "k_A_finish_rows_wide<SPB=1>") : "k_A_finish_rows");
-    c->ctc_parts = 0;  // the rows kernels wrote the totals
-    c->b_systems_valid = (next_B != 0);
+    if (!fuse_inner && c->Q64 != nullptr) c->bp.made(BP_A64);  // rhsA64 / Q64 / LinvA64 hold this phase's systems
+    c->variant[MCL_PROF_A_FINISH] = !rows_kernel ? "k_A_finish" : (plan.rhs_wide ? (plan.rhs_pairs ? "k_A_finish_rows_wide<SPB=2>" : "k_A_finish_rows_wide<SPB=1>") : "k_A_finish_rows");
+    c->bp.ctc_parts = 0;  // the rows kernels wrote the totals
+    if (next_B != 0) c->bp.made(BP_B_SYSTEMS);
     return 0;
 }
 
@@ -855,7 +856,7 @@ int mcl_launch_A_e1(mcl_context *c, bool btb_is_q) {
     ProfScope prof_(c, MCL_PROF_OTHER);
     if (c->I == 0) return 0;
     // (the fp64 copies exist in the exact-products mode and are current when the systems were just built from them)
-    const bool wide = btb_is_q && c->exact && c->a64_valid;
+    const bool wide = btb_is_q && c->exact && c->bp.has(BP_A64);
     hipLaunchKernelGGL(k_A_e1, dim3((unsigned)c->I), dim3(64), 0, c->stream, c->rhsA, c->BtB, c->CtC, btb_is_q ? 1 : 0,
                        c->A, c->regs[0], c->r, c->e1, c->diagA_row, wide ? (const double *)c->rhsA64 : nullptr,
                        wide ? (const double *)c->Q64 : nullptr);

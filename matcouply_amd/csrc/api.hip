@@ -260,10 +260,10 @@ int ready_noflush(mcl_context *c) {
 // The step API defers the prox + dual row pass of a fused stack (see mcl_B_prox_finish): every entry point but
 // mcl_B_solve - which merges it with its own pass - issues it first, so callers never observe the deferral.
 int flush_B_finish(mcl_context *c) {
-    if (!c->b_finish_pending) return 0;
-    c->b_finish_pending = false;
+    if (!c->step.finish_pending) return 0;
+    c->step.finish_pending = false;
     if (int rc = mcl_launch_rows_finish_fused(c, 1, true)) return rc;  // also leaves the mode's diagnostics table
-    c->diag_valid[1] = true;
+    c->bp.made(BP_DIAG(1));
     return 0;
 }
 
@@ -297,18 +297,17 @@ int ready(mcl_context *c) {
 // next solve / the end of the phase - the single prox + dual row pass is only issued once the stack is complete.  A host
 // that skipped an index would otherwise leave stale aux / dual rows without any error.
 int round_complete(mcl_context *c, const char *who) {
-    if (!c->step_fuse) return 0;
-    c->step_fuse = c->step_stats = false;  // report once; the host may restart the phase with mcl_B_begin
+    if (!c->step.fuse) return 0;
+    c->step = StepRound{};  // report once; the host may restart the phase with mcl_B_begin
     return fail(c, std::string(who) + ": the previous inner iteration did not step every penalty of mode 1 "
                    "(mcl_B_prox_local / mcl_B_prox_finish for k = 0 .. n-1): its aux / dual rows were not updated");
 }
 
 int ensure_ctc(mcl_context *c) {
-    if (!c->ctc_valid) {
+    if (!c->bp.has(BP_CTC)) {
         if (int rc = mcl_launch_ctc(c)) return rc;
-        c->ctc_valid = true;
-        c->ctc_parts = 0;
-    } else if (c->ctc_parts > 0) {  // current, but still in the partial blocks of k_C_finish_multi
+        c->bp.made(BP_CTC);
+    } else if (c->bp.ctc_parts > 0) {  // current, but still in the partial blocks of k_C_finish_multi
         if (int rc = mcl_launch_ctc_fold(c)) return rc;
     }
     return 0;
@@ -322,29 +321,29 @@ int monitor_condition(mcl_context *c, int mode) {
     return mcl_launch_cond_probe(c, 1 << mode, c->cond_monitor, true);
 }
 
-int ensure_xc(mcl_context *c) {
-    if (!c->xc_valid && c->exact) {  // exact-products mode: fp64 sums of exact products, rounded once for the fp32 image
-        if (int rc = mcl_launch_exact_xc(c)) return rc;
-        c->xc_did_gram = false;
-        c->xc_valid = true;
-    }
-    if (!c->xc_valid) {
-        if (!c->cfrag_valid) {
-            if (int rc = mcl_launch_build_cfrag(c)) return rc;
-            c->cfrag_valid = true;
-        }
-        if (int rc = mcl_launch_contract_xc(c)) return rc;
-        c->xc_valid = true;
+// fragment image of the current C: CfragS aliases Cfrag, one image serves the X C kernels and the sweep
+int ensure_cfrag_sweep(mcl_context *c) {
+    if (!c->bp.has(BP_CFRAG)) {
+        if (int rc = mcl_launch_build_cfrag(c)) return rc;
+        c->bp.made(BP_CFRAG);
     }
     return 0;
 }
 
-// fragment image of the current C for the sweep kernels
-int ensure_cfrag_sweep(mcl_context *c) {  // CfragS aliases Cfrag: one image serves the X C kernels and the sweep
-    if (!c->cfrag_valid) {
-        if (int rc = mcl_launch_build_cfrag(c)) return rc;
-        c->cfrag_valid = true;
+// with_gram: an X C launch made here may also leave the per-segment rhs / Gram of the A-phase (seg_rhs / seg_btb);
+// *did_gram says whether one did
+int ensure_xc(mcl_context *c, bool with_gram = false, bool *did_gram = nullptr) {
+    bool did = false;
+    if (!c->bp.has(BP_XC) && c->exact) {  // exact-products mode: fp64 sums of exact products, rounded once for the fp32 image
+        if (int rc = mcl_launch_exact_xc(c)) return rc;
+        c->bp.made(BP_XC);
     }
+    if (!c->bp.has(BP_XC)) {
+        if (int rc = ensure_cfrag_sweep(c)) return rc;
+        if (int rc = mcl_launch_contract_xc(c, with_gram, &did)) return rc;
+        c->bp.made(BP_XC);
+    }
+    if (did_gram) *did_gram = did;
     return 0;
 }
 
@@ -361,18 +360,16 @@ int checked_inner_loop(mcl_context *c, int mode) {
     int rc = 0;
     for (int it = 0; it < n_it && rc == 0; ++it) {
         rc = (mode == 0) ? mcl_launch_A_rows_solve(c, c->inner_part) : mcl_launch_rows_solve(c, mode, c->inner_part);
-        c->stack_fused = c->stats_in_solve = false;
-        c->pf2_delta_fused = !c->sw.no_pf2_delta_fusion;
+        const ProxForm form{false, false, !c->sw.no_pf2_delta_fusion};
         for (int k = 0; k < c->regs[mode].n && rc == 0; ++k) {
-            rc = mcl_launch_generic_prox_local(c, mode, k);
-            if (rc == 0) rc = mcl_launch_generic_prox_finish(c, mode, k);
+            rc = mcl_launch_generic_prox_local(c, mode, k, form);
+            if (rc == 0) rc = mcl_launch_generic_prox_finish(c, mode, k, form);
         }
-        c->pf2_delta_fused = false;
         if (rc == 0) rc = mcl_launch_rows_diag(c, mode);
         if (rc == 0) rc = mcl_launch_inner_check(c, mode, false);
     }
     c->gate_active = run_gate, c->regs[mode].gate = reg_gate;
-    c->diag_valid[mode] = rc == 0 && n_it > 0 && mode != 0;  // (mode 0: mcl_launch_A_e1 follows and owns its tables)
+    if (rc == 0 && n_it > 0 && mode != 0) c->bp.made(BP_DIAG(mode));  // (mode 0: mcl_launch_A_e1 follows and owns its tables)
     return rc;
 }
 
@@ -396,19 +393,16 @@ int generic_inner_loop(mcl_context *c, int mode) {
         } else {
             if (int rc = mcl_launch_rows_solve(c, mode)) return rc;
         }
-        c->stack_fused = fuse;
-        c->stats_in_solve = stats;
-        c->pf2_delta_fused = !c->sw.no_pf2_delta_fusion;
+        const ProxForm form{fuse, stats, !c->sw.no_pf2_delta_fusion};
         int rc = 0;
         // (Round 6, measured and dropped: the PARAFAC2 algebra of an inner iteration does not depend on the unimodal regressions of
         // the same iteration, and a launch of the regressions leaves 13-16 % of the device's wave slots idle - two rounds of long
         // waves, tools/uni_stamps.py.  Run on a low-priority stream of the library's own beside the regressions, the algebra's
         // waves do not wait for those gaps: the regressions take 10.3 instead of 7.6 ms, config 5 106 instead of 96 ms per iteration.)
         for (int k = 0; k < c->regs[mode].n && rc == 0; ++k) {
-            rc = mcl_launch_generic_prox_local(c, mode, k);
-            if (rc == 0) rc = mcl_launch_generic_prox_finish(c, mode, k);
+            rc = mcl_launch_generic_prox_local(c, mode, k, form);
+            if (rc == 0) rc = mcl_launch_generic_prox_finish(c, mode, k, form);
         }
-        c->stack_fused = c->stats_in_solve = c->pf2_delta_fused = false;
         if (rc) return rc;
         if (fuse) {
             if (chain && it + 1 < n_it) {
@@ -418,7 +412,7 @@ int generic_inner_loop(mcl_context *c, int mode) {
             }
         }
     }
-    c->diag_valid[mode] = fuse && n_it > 0;  // the fused finish pass leaves the mode's diagnostics table current
+    if (fuse && n_it > 0) c->bp.made(BP_DIAG(mode));  // the fused finish pass leaves the mode's diagnostics table current
     return 0;
 }
 
@@ -490,7 +484,7 @@ int mcl_set_problem_typed(mcl_context *c, const void *X, int32_t x_type, const i
     if (I < 0 || K < 1) return fail(c, "mcl_set_problem: need I >= 0 and K >= 1");
     if (rank < 1 || rank > MCL_MAX_RANK) return fail(c, "mcl_set_problem: rank must be in [1, 64]");
     if (int rc = settle_deferred(c)) return rc;
-    c->b_finish_pending = false;  // a deferred row pass of the step API refers to the buffers being replaced
+    c->step.finish_pending = false;  // a deferred row pass of the step API refers to the buffers being replaced
     if (!row_ptr || row_ptr[0] != 0) return fail(c, "mcl_set_problem: row_ptr[0] must be 0");
     for (int64_t i = 0; i < I; ++i)
         if (row_ptr[i + 1] < row_ptr[i]) return fail(c, "mcl_set_problem: row_ptr must be non-decreasing");
@@ -644,9 +638,7 @@ int mcl_set_problem_typed(mcl_context *c, const void *X, int32_t x_type, const i
     single(I, c->h_atile_slab, c->h_atile_row0, c->h_atile_nrows);
     c->has_problem = true;
     c->has_workspace = false;
-    c->xc_valid = c->ctc_valid = c->e1_valid = c->xsq_valid = false;
-    c->mseg_valid = c->grpart_valid = false;
-    c->diag_valid[0] = c->diag_valid[1] = c->diag_valid[2] = false;
+    c->bp.changed(IN_X | IN_WORKSPACE);  // (the shapes went with X: no installation fits them)
     return 0;
 }
 
@@ -658,7 +650,7 @@ int mcl_set_options(mcl_context *c, const mcl_options *opt) {
     if (c->has_workspace && opt->exact_products != c->opt.exact_products)
         c->has_workspace = false;  // the carve-up depends on the mode: the workspace has to be installed again
     c->opt = *opt;
-    c->b_systems_valid = false;
+    c->bp.changed(IN_OPTIONS);
     return 0;
 }
 
@@ -667,14 +659,10 @@ int mcl_set_factors(mcl_context *c, float *A, float *B, float *C) {
     if (!c->has_problem) return fail(c, "mcl_set_factors: call mcl_set_problem first");
     if ((c->I > 0 && !A) || (c->N > 0 && !B) || !C) return fail(c, "mcl_set_factors: NULL factor pointer");
     if (int rc = settle_deferred(c)) return rc;
-    c->b_finish_pending = false;  // a deferred row pass of the step API refers to the buffers being replaced
+    c->step.finish_pending = false;  // a deferred row pass of the step API refers to the buffers being replaced
     c->A = A, c->B = B, c->C = C;
     c->has_factors = true;
-    c->b_systems_valid = false;
-    c->cfrag_valid = false;
-    c->xc_valid = c->ctc_valid = c->e1_valid = false;
-    c->mseg_valid = c->grpart_valid = false;
-    c->diag_valid[0] = c->diag_valid[1] = c->diag_valid[2] = false;
+    c->bp.changed(IN_ALL_STATE);  // (the same pointers again: the caller has written the tensors, ADMM variables included)
     return 0;
 }
 
@@ -683,7 +671,7 @@ int mcl_set_penalties(mcl_context *c, int32_t mode, int32_t n, const mcl_penalty
     if (mode < 0 || mode > 2) return fail(c, "mcl_set_penalties: mode must be 0, 1 or 2");
     if (n < 0 || n > MCL_MAX_REGS) return fail(c, "mcl_set_penalties: at most 4 penalties per mode");
     if (int rc = settle_deferred(c)) return rc;
-    c->b_finish_pending = false;  // a deferred row pass of the step API refers to the buffers being replaced
+    c->step.finish_pending = false;  // a deferred row pass of the step API refers to the buffers being replaced
     RegSet rs{};
     rs.n = n;
     for (int k = 0; k < n; ++k) {
@@ -717,10 +705,8 @@ int mcl_set_penalties(mcl_context *c, int32_t mode, int32_t n, const mcl_penalty
         rs.aux2[k] = d.aux2;
     }
     c->regs[mode] = rs;
-    c->b_systems_valid = false;
     c->has_workspace = false;  // scratch requirements may have changed
-    c->diag_valid[mode] = false;
-    c->e1_valid = false;
+    c->bp.changed(IN_PEN(mode) | IN_ADMM(mode) | IN_WORKSPACE);
     return 0;
 }
 
@@ -743,7 +729,7 @@ int mcl_set_workspace(mcl_context *c, void *workspace, int64_t bytes) {
         if (c->has_workspace) plan(c, c->ws);  // a refused call leaves the installed workspace as it was
         return fail(c, "mcl_set_workspace: workspace too small");
     }
-    c->b_finish_pending = false;  // a deferred row pass of the step API refers to the buffers being replaced
+    c->step.finish_pending = false;  // a deferred row pass of the step API refers to the buffers being replaced
     if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(c, "mcl_set_workspace: workspace must be 256-byte aligned");
     c->ws = static_cast<char *>(workspace);
     c->ws_bytes = bytes;
@@ -787,10 +773,7 @@ int mcl_set_workspace(mcl_context *c, void *workspace, int64_t bytes) {
     MCL_CHECK_HIP(c, hipMemcpyAsync(c->ext_C, c->h_ext.data() + 2, 2 * sizeof(int), hipMemcpyHostToDevice, s));
     // the host vectors must outlive the async copies: they are members of the context
     c->has_workspace = true;
-    c->cfrag_valid = false;
-    c->mseg_valid = c->grpart_valid = false;
-    c->xc_valid = c->ctc_valid = c->e1_valid = c->xsq_valid = false;
-    c->diag_valid[0] = c->diag_valid[1] = c->diag_valid[2] = false;
+    c->bp.changed(IN_WORKSPACE);  // zeroed: it holds nothing
     return 0;
 }
 
@@ -810,8 +793,8 @@ int mcl_B_begin(mcl_context *c) {
 float *mcl_B_rho_max(mcl_context *c) { return c ? c->rho_max : nullptr; }
 
 static int B_factor_impl(mcl_context *c) {
-    if (c->b_systems_valid) {  // built by the preceding A-finish from the same a_i and CtC
-        c->b_systems_valid = false;
+    if (c->bp.has(BP_B_SYSTEMS)) {  // built by the preceding A-finish from the same a_i and CtC
+        c->bp.dropped(BP_B_SYSTEMS);  // ... for ONE B-phase: the next one builds its own (mcl_launch_B_systems, equal to rounding)
         return 0;
     }
     return mcl_launch_B_systems(c);
@@ -824,7 +807,7 @@ int mcl_B_factor(mcl_context *c) {
 
 // the finish pass of inner iteration t can be merged with the solve of t + 1 (k_rows_finish_solve_stats)
 static bool step_can_chain(const mcl_context *c) {
-    if (!c->step_fuse || !c->step_stats || c->sw.no_pass_chain) return false;
+    if (!c->step.fuse || !c->step.stats || c->sw.no_pass_chain) return false;
     int n_l2 = 0;
     for (int k = 0; k < c->regs[1].n; ++k) n_l2 += c->regs[1].kind[k] == MCL_PEN_L2BALL;
     return n_l2 <= 1;
@@ -833,20 +816,18 @@ static bool step_can_chain(const mcl_context *c) {
 int mcl_B_solve(mcl_context *c) {
     if (int rc = ready_noflush(c)) return rc;
     if (int rc = round_complete(c, "mcl_B_solve")) return rc;
-    c->e1_valid = false;
-    c->mseg_valid = c->grpart_valid = false;
-    c->diag_valid[1] = false;
+    c->bp.changed(IN_B);
     // fusable stacks (see generic_inner_loop): statistics out of the solve pass, ONE prox + dual row pass once the
     // last penalty of the stack has been finished - the per-penalty calls below then only run the per-slab algebra
-    c->step_fuse = mcl_stack_can_fuse(c, 1);
-    c->step_stats = c->step_fuse && mcl_stats_can_ride_in_solve(c, 1);
-    c->step_done_mask = 0;
-    if (c->b_finish_pending) {  // previous inner iteration's prox + dual pass and this solve in one kernel
-        c->b_finish_pending = false;
+    const bool finish_first = c->step.finish_pending;
+    c->step = StepRound{};
+    c->step.fuse = mcl_stack_can_fuse(c, 1);
+    c->step.stats = c->step.fuse && mcl_stats_can_ride_in_solve(c, 1);
+    if (finish_first) {  // previous inner iteration's prox + dual pass and this solve in one kernel
         if (step_can_chain(c)) return mcl_launch_rows_finish_solve_stats(c);
         if (int rc = mcl_launch_rows_finish_fused(c, 1, false)) return rc;
     }
-    if (c->step_stats) return mcl_launch_rows_solve_stats(c);
+    if (c->step.stats) return mcl_launch_rows_solve_stats(c);
     if (c->regs[1].n == 0) return mcl_launch_B_solve_f64(c);
     return mcl_launch_rows_solve(c, 1);
 }
@@ -859,10 +840,7 @@ int mcl_B_end(mcl_context *c) {
 int mcl_B_prox_local(mcl_context *c, int32_t k) {
     if (int rc = ready(c)) return rc;
     if (k < 0 || k >= c->regs[1].n) return fail(c, "mcl_B_prox_local: penalty index out of range");
-    c->stack_fused = c->step_fuse, c->stats_in_solve = c->step_stats;
-    const int rc = mcl_launch_generic_prox_local(c, 1, k);
-    c->stack_fused = c->stats_in_solve = false;
-    return rc;
+    return mcl_launch_generic_prox_local(c, 1, k, ProxForm{c->step.fuse, c->step.stats, false});
 }
 
 float *mcl_B_prox_reduce_buffer(mcl_context *c, int32_t k, int64_t *count) {
@@ -877,22 +855,21 @@ float *mcl_B_prox_reduce_buffer(mcl_context *c, int32_t k, int64_t *count) {
 int mcl_B_prox_finish(mcl_context *c, int32_t k) {
     if (int rc = ready(c)) return rc;
     if (k < 0 || k >= c->regs[1].n) return fail(c, "mcl_B_prox_finish: penalty index out of range");
-    c->stack_fused = c->step_fuse, c->stats_in_solve = c->step_stats;
-    int rc = mcl_launch_generic_prox_finish(c, 1, k);
-    c->stack_fused = c->stats_in_solve = false;
-    if (rc == 0 && c->step_fuse) {
-        c->step_done_mask |= 1u << k;
-        if (c->step_done_mask == (1u << c->regs[1].n) - 1u) {  // whole stack stepped: the fused row pass
-            if (step_can_chain(c)) c->b_finish_pending = true;  // issued by the next entry point (merged into mcl_B_solve)
-            else rc = mcl_launch_rows_finish_fused(c, 1, false);
-            c->step_fuse = c->step_stats = false;
+    int rc = mcl_launch_generic_prox_finish(c, 1, k, ProxForm{c->step.fuse, c->step.stats, false});
+    if (rc == 0 && c->step.fuse) {
+        c->step.done_mask |= 1u << k;
+        if (c->step.done_mask == (1u << c->regs[1].n) - 1u) {  // whole stack stepped: the fused row pass
+            const bool chain = step_can_chain(c);  // then issued by the next entry point (merged into mcl_B_solve)
+            if (!chain) rc = mcl_launch_rows_finish_fused(c, 1, false);
+            c->step = StepRound{};
+            c->step.finish_pending = chain;
         }
     }
     return rc;
 }
 
 int mcl_update_B(mcl_context *c) {
-    if (c && c->diag_pending && !c->diag_crossed_sweep && ready_noflush(c) == 0 && !c->b_finish_pending &&
+    if (c && c->diag_pending && !c->diag_crossed_sweep && ready_noflush(c) == 0 && !c->step.finish_pending &&
         mcl_sweep_eligible(c)) {
         // a deferred diagnostics reduction survives ONE sweep (which writes the OTHER mode-1 table) and rides on the
         // C-phase reduction that follows it; a second sweep would flip the table parity back and overwrite the table the
@@ -910,13 +887,11 @@ int mcl_update_B(mcl_context *c) {
         if (c->opt.constant_B)
             if (int rc = mcl_launch_B_rho(c)) return rc;
         if (int rc = B_factor_impl(c)) return rc;
-        c->e1_valid = false;
+        c->bp.changed(IN_B | IN_ADMM(1));
         const int rc = mcl_launch_sweep(c);
         if (rc > 0) return rc;
         if (rc == 0) {
-            c->mseg_valid = true;
-            c->grpart_valid = true;
-            c->diag_valid[1] = true;
+            c->bp.made(BP_MPART), c->bp.made(BP_GRPART), c->bp.made(BP_DIAG(1));
             return 0;
         }
         c->sweep_planned = false;  // the device refused the kernel's LDS size: two-pass path from now on
@@ -928,25 +903,19 @@ int mcl_update_B(mcl_context *c) {
         if (c->opt.constant_B)
             if (int rc = mcl_launch_B_rho(c)) return rc;
         if (int rc = B_factor_impl(c)) return rc;
-        c->e1_valid = false;
+        c->bp.changed(IN_B);
         if (c->opt.inner_n_iter_max <= 0) return 0;
-        c->mseg_valid = c->grpart_valid = false;
-        c->diag_valid[1] = false;
         return mcl_launch_B_solve_f64(c);
     }
     if (int rc = mcl_B_begin(c)) return rc;
     if (int rc = mcl_B_factor(c)) return rc;
-    c->e1_valid = false;
+    c->bp.changed(IN_B | IN_ADMM(1));
     if (c->opt.inner_n_iter_max <= 0) return 0;
-    c->mseg_valid = c->grpart_valid = false;
-    if (mcl_wide_applies(c, 1)) {  // small problem: the whole inner loop in fp64 (wide.hip)
-        c->diag_valid[1] = false;  // (set again by the row-separable form, which leaves the table itself)
-        return mcl_wide_phase(c, 1);
-    }
+    if (mcl_wide_applies(c, 1)) return mcl_wide_phase(c, 1);  // small problem: the whole inner loop in fp64 (wide.hip)
     if (mcl_mode_is_row_separable(c, 1) && !(c->opt.inner_tol > 0.0)) {
         const int rc = mcl_launch_rows_fused(c, 1);
         if (rc == 0) {
-            c->diag_valid[1] = true;
+            c->bp.made(BP_DIAG(1));
             return 0;
         }
         if (rc > 0) return rc;
@@ -956,13 +925,14 @@ int mcl_update_B(mcl_context *c) {
 
 // ---- C-phase -------------------------------------------------------------------------------------------
 int mcl_update_C_local(mcl_context *c) {
-    if (c && c->cond_monitor && ready_noflush(c) == 0 && !c->b_finish_pending)
+    if (c && c->cond_monitor && ready_noflush(c) == 0 && !c->step.finish_pending)
         if (int rc = monitor_condition(c, 2)) return rc;
-    if (c && c->diag_pending && ready_noflush(c) == 0 && !c->b_finish_pending && c->mseg_valid && c->grpart_valid)
+    const bool from_sweep = c && c->bp.has(BP_MPART) && c->bp.has(BP_GRPART);
+    if (c && c->diag_pending && ready_noflush(c) == 0 && !c->step.finish_pending && from_sweep)
         return mcl_launch_reduce_weighted(c);  // ... with the deferred diagnostics reduction on its spare workgroup
     if (int rc = ready(c)) return rc;
     if (c->exact) return mcl_launch_exact_gr(c);
-    if (c->mseg_valid && c->grpart_valid) return mcl_launch_reduce_weighted(c);
+    if (from_sweep) return mcl_launch_reduce_weighted(c);
     if (int rc = mcl_launch_contract_xt(c)) return rc;
     return mcl_launch_reduce_partials(c);
 }
@@ -981,41 +951,29 @@ int mcl_update_C_finish(mcl_context *c) {
     ProfScope prof_(c, MCL_PROF_C_FINISH);
     if (mcl_wide_applies(c, 2)) {  // small problem: the whole inner loop in fp64 (wide.hip)
         if (int rc = mcl_launch_C_prepare(c)) return rc;
-        c->xc_valid = c->ctc_valid = c->e1_valid = false;
-        c->ctc_parts = 0;
-        c->cfrag_valid = false;
-        c->b_systems_valid = false;
-        c->diag_valid[2] = false;
+        c->bp.changed(IN_C | IN_ADMM(2));
         c->variant[MCL_PROF_C_FINISH] = "k_C_prepare + fp64 inner loop (wide.hip)";
         return mcl_wide_phase(c, 2);
     }
     const bool checked_C = c->opt.inner_tol > 0.0 && c->regs[2].n > 0;  // inner stopping test: one launch per step
     if (c->opt.inner_n_iter_max > 0 && mcl_mode_is_row_separable(c, 2) && !checked_C) {
         // everything from the system solve to CtC / C fragments in one single-workgroup launch
+        c->bp.changed(IN_C | IN_ADMM(2));  // (a shape without such a kernel, rc < 0, says the same again below)
         const int rc = mcl_launch_C_finish_fused(c);
         if (rc == 0) {
-            c->xc_valid = c->e1_valid = false;
-            c->b_systems_valid = false;
-            c->ctc_valid = true;
-            c->cfrag_valid = true;
-            c->diag_valid[2] = true;
+            c->bp.made(BP_CTC), c->bp.made(BP_CFRAG), c->bp.made(BP_DIAG(2));
             return 0;
         }
         if (rc > 0) return rc;
     }
     if (int rc = mcl_launch_C_prepare(c)) return rc;
     if (c->opt.inner_n_iter_max <= 0) return 0;
-    c->xc_valid = c->ctc_valid = c->e1_valid = false;
-    c->cfrag_valid = false;
-    c->b_systems_valid = false;
-    if (c->regs[2].n == 0) {  // un-shifted normal equations: the solve runs in fp64
-        c->diag_valid[2] = false;
-        return mcl_launch_C_solve_f64(c);
-    }
+    c->bp.changed(IN_C | IN_ADMM(2));
+    if (c->regs[2].n == 0) return mcl_launch_C_solve_f64(c);  // un-shifted normal equations: the solve runs in fp64
     if (mcl_mode_is_row_separable(c, 2) && !checked_C) {
         const int rc = mcl_launch_rows_fused(c, 2);
         if (rc == 0) {
-            c->diag_valid[2] = true;
+            c->bp.made(BP_DIAG(2));
             return 0;
         }
         if (rc > 0) return rc;
@@ -1031,16 +989,13 @@ int mcl_A_begin(mcl_context *c) {
     // C^T C still in the partial blocks of k_C_finish_multi: the rows kernels of the A-phase finish sum them themselves (and
     // write the totals); anything else - the constant-rho pre-pass, the column-layout finish - gets them folded first
     const bool rows_finish = mcl_a_finish_rows(c) && !c->opt.constant_A;
-    if (!(c->ctc_valid && c->ctc_parts > 0 && rows_finish))
+    if (!(c->bp.has(BP_CTC) && c->bp.ctc_parts > 0 && rows_finish))
         if (int rc = ensure_ctc(c)) return rc;
     // When X C has to be recomputed anyway (C changed), the per-slab reductions ride in its epilogue; the
     // constant-rho pre-pass (k_A_rho) needs the assembled per-slab Gram, so it keeps the separate kernel.
-    c->use_seg_gram = false;
-    c->seg_from_sweep = false;
-    c->a_rhs_from_M = false;
-    c->a_rhs_wide = false;
-    c->a_rhs_pairs = false;
-    if (c->mseg_valid && !c->opt.constant_A && mcl_mode_is_row_separable(c, 0)) {
+    APlan plan{};  // what mcl_A_finish will launch
+    c->a_plan = plan;
+    if (c->bp.has(BP_MPART) && !c->opt.constant_A && mcl_mode_is_row_separable(c, 0)) {
         // the sweep left M_i = X_i^T B_i per bseg: rhs_i = coldot(M_i, C), no pass over X
         if (int rc = ensure_cfrag_sweep(c)) return rc;
         // rank 5..32: the finish kernel forms rhs_i from the sweep's M partials itself (one launch less); otherwise a
@@ -1051,30 +1006,24 @@ int mcl_A_begin(mcl_context *c) {
         const bool fusable = mcl_a_finish_rows(c) && !c->sw.no_a_fusion;
         // (with one partial per slab only while all the workgroups are resident at once - two per CU: beyond 512 slabs a
         // second round of workgroups would cost more than the overlap returns, config 3: +4 us)
-        c->a_rhs_wide = fusable && c->n_parts <= 8 * c->I && (c->n_parts > c->I || c->I <= 512) && !c->sw.no_a_wide;
+        plan.rhs_wide = fusable && c->n_parts <= 8 * c->I && (c->n_parts > c->I || c->I <= 512) && !c->sw.no_a_wide;
         // ... up to 1024 slabs two slabs share a workgroup: one system wave and one streaming wave each
-        c->a_rhs_pairs = fusable && !c->a_rhs_wide && c->n_parts <= c->I && c->I <= 1024 && !c->sw.no_a_wide;
-        if (c->a_rhs_pairs) c->a_rhs_wide = true;
-        c->a_rhs_from_M = fusable && (c->n_parts <= c->I || c->a_rhs_wide);
-        if (!c->a_rhs_from_M)
+        plan.rhs_pairs = fusable && !plan.rhs_wide && c->n_parts <= c->I && c->I <= 1024 && !c->sw.no_a_wide;
+        if (plan.rhs_pairs) plan.rhs_wide = true;
+        plan.rhs_from_M = fusable && (c->n_parts <= c->I || plan.rhs_wide);
+        if (!plan.rhs_from_M)
             if (int rc = mcl_launch_A_rhs_from_M(c)) return rc;
-        c->use_seg_gram = true;
-        c->seg_from_sweep = true;
-        c->e1_valid = false;
+        plan.use_seg_gram = plan.seg_from_sweep = true;
+        c->a_plan = plan;
+        c->bp.dropped(BP_E1);  // (the phase's right-hand sides and cross products take the buffers e1 was computed from)
         return 0;
     }
-    if (!c->xc_valid && !c->opt.constant_A && mcl_mode_is_row_separable(c, 0) && !c->sw.no_fused_gram) {
-        c->xc_with_gram = true;
-        const int rc = ensure_xc(c);
-        c->xc_with_gram = false;
-        if (rc) return rc;
-        c->use_seg_gram = c->xc_did_gram;
-    } else {
-        if (int rc = ensure_xc(c)) return rc;
-    }
-    if (!c->use_seg_gram)
+    const bool with_gram = !c->bp.has(BP_XC) && !c->opt.constant_A && mcl_mode_is_row_separable(c, 0) && !c->sw.no_fused_gram;
+    if (int rc = ensure_xc(c, with_gram, &plan.use_seg_gram)) return rc;
+    if (!plan.use_seg_gram)
         if (int rc = mcl_launch_slab_gram(c)) return rc;
-    c->e1_valid = false;
+    c->a_plan = plan;
+    c->bp.dropped(BP_E1);
     if (c->opt.constant_A)
         if (int rc = mcl_launch_A_rho(c)) return rc;
     return 0;
@@ -1086,7 +1035,7 @@ int mcl_A_finish(mcl_context *c) {
     if (int rc = ready(c)) return rc;
     if (c->opt.inner_n_iter_max <= 0) return 0;
     ProfScope prof_(c, MCL_PROF_A_FINISH);
-    c->grpart_valid = false;  // the sweep's [G | R] partials were weighted with the previous a_i
+    c->bp.changed(IN_A | IN_ADMM(0));  // (e.g. the sweep's [G | R] partials were weighted with the previous a_i)
     if (mcl_mode_is_row_separable(c, 0) && c->opt.inner_tol > 0.0 && c->regs[0].n > 0) {
         // inner stopping test: the systems, then one launch per step (k_A_rows_solve, per-row prox, table, test)
         if (int rc = mcl_launch_A_finish(c, false)) return rc;
@@ -1109,9 +1058,8 @@ int mcl_A_finish(mcl_context *c) {
         }
         if (int rc = mcl_launch_A_e1(c, true)) return rc;
     }
-    c->e1_valid = true;
-    c->e1_from_raw_gram = false;  // the BtB buffer now holds Q_i (cross_products)
-    c->diag_valid[0] = true;
+    c->bp.made(BP_E1), c->bp.made(BP_DIAG(0));
+    c->bp.e1_from_raw_gram = false;  // the BtB buffer now holds Q_i (cross_products)
     return 0;
 }
 
@@ -1122,26 +1070,22 @@ int mcl_update_A(mcl_context *c) {
 
 int mcl_A_factor(mcl_context *c) {
     if (int rc = ready(c)) return rc;
-    if (c->use_seg_gram) return fail(c, "internal: mcl_A_factor needs the assembled per-slab Gram");
-    c->b_systems_valid = false;
+    if (c->a_plan.use_seg_gram) return fail(c, "internal: mcl_A_factor needs the assembled per-slab Gram");
+    c->bp.dropped(BP_B_SYSTEMS);  // (a phase driven in steps leaves none; the solves that follow move A anyway)
     return mcl_launch_A_finish(c, false);
 }
 
 int mcl_A_solve(mcl_context *c) {
     if (int rc = ready(c)) return rc;
-    c->grpart_valid = false;
-    c->e1_valid = false;
-    c->diag_valid[0] = false;
-    c->b_systems_valid = false;
+    c->bp.changed(IN_A);
     return mcl_launch_A_rows_solve(c);
 }
 
 int mcl_A_end(mcl_context *c) {
     if (int rc = ready(c)) return rc;
     if (int rc = mcl_launch_A_e1(c, true)) return rc;
-    c->e1_valid = true;
-    c->e1_from_raw_gram = false;
-    c->diag_valid[0] = true;
+    c->bp.made(BP_E1), c->bp.made(BP_DIAG(0));
+    c->bp.e1_from_raw_gram = false;
     return 0;
 }
 
@@ -1152,46 +1096,40 @@ int mcl_C_begin(mcl_context *c) {
 
 int mcl_C_solve(mcl_context *c) {
     if (int rc = ready(c)) return rc;
-    c->xc_valid = c->ctc_valid = c->e1_valid = false;
-    c->cfrag_valid = false;
-    c->b_systems_valid = false;
-    c->diag_valid[2] = false;
+    c->bp.changed(IN_C | IN_ADMM(2));  // (the host runs the proxes of the step on the tensors themselves)
     return mcl_launch_rows_solve(c, 2);
 }
 
 int mcl_C_end(mcl_context *c) {
     if (int rc = ready(c)) return rc;
-    c->xc_valid = c->ctc_valid = c->e1_valid = false;
-    c->cfrag_valid = false;
-    c->b_systems_valid = false;
-    c->diag_valid[2] = false;
+    c->bp.changed(IN_C | IN_ADMM(2));
     return 0;
 }
 
 // ---- diagnostics ---------------------------------------------------------------------------------------
 // every table the diagnostics vector is reduced from is made current (what mcl_diagnostics does before its reduction)
 static int mcl_prepare_diag_tables(mcl_context *c) {
-    if (!c->xsq_valid) {
+    if (!c->bp.has(BP_XSQ)) {
         if (int rc = mcl_launch_x_sq(c)) return rc;
-        c->xsq_valid = true;
+        c->bp.made(BP_XSQ);
     }
-    if (!c->diag_valid[1])
-        if (int rc = mcl_launch_rows_diag(c, 1)) return rc;
-    if (!c->diag_valid[2])
-        if (int rc = mcl_launch_rows_diag(c, 2)) return rc;
-    c->diag_valid[1] = c->diag_valid[2] = true;
-    if (!c->e1_valid) {
+    for (int mode = 1; mode <= 2; ++mode)
+        if (!c->bp.has(BP_DIAG(mode))) {
+            if (int rc = mcl_launch_rows_diag(c, mode)) return rc;
+            c->bp.made(BP_DIAG(mode));
+        }
+    if (!c->bp.has(BP_E1)) {
         // no current A-phase by-products: full formula with a pass over X (decomposition.py:430-444)
         if (int rc = ensure_ctc(c)) return rc;
         if (int rc = ensure_xc(c)) return rc;
         if (int rc = mcl_launch_slab_gram(c)) return rc;
         if (int rc = mcl_launch_A_e1(c, false)) return rc;
-        c->e1_valid = true;
-        c->e1_from_raw_gram = true;
-    } else if (!c->diag_valid[0]) {
-        if (int rc = mcl_launch_A_e1(c, !c->e1_from_raw_gram)) return rc;
+        c->bp.made(BP_E1);
+        c->bp.e1_from_raw_gram = true;
+    } else if (!c->bp.has(BP_DIAG(0))) {
+        if (int rc = mcl_launch_A_e1(c, !c->bp.e1_from_raw_gram)) return rc;
     }
-    c->diag_valid[0] = true;
+    c->bp.made(BP_DIAG(0));
     return 0;
 }
 
@@ -1207,7 +1145,8 @@ int mcl_diagnostics_deferred(mcl_context *c, double *out, int32_t include_replic
     if (!out) return fail(c, "mcl_diagnostics_deferred: out is NULL");
     if (int rc = ready(c)) return rc;  // also issues an older deferred reduction
     // deferrable: every table is current and ||X||^2 is known, i.e. mcl_diagnostics() would only launch its reduction
-    if (!(c->xsq_valid && c->e1_valid && c->diag_valid[0] && c->diag_valid[1] && c->diag_valid[2]) || c->sw.no_diag_defer)
+    const Byproducts &bp = c->bp;
+    if (!(bp.has(BP_XSQ) && bp.has(BP_E1) && bp.has(BP_DIAG(0)) && bp.has(BP_DIAG(1)) && bp.has(BP_DIAG(2))) || c->sw.no_diag_defer)
         return mcl_diagnostics(c, out, include_replicated);
     c->diag_pending_T = mcl_diag_tables(c, true);
     c->diag_pending_out = out, c->diag_pending_incl = include_replicated ? 1 : 0;
@@ -1274,15 +1213,9 @@ int mcl_iterate(mcl_context *c, int32_t n_iter, int32_t update_A, int32_t update
 // gated run that stopped early the scratch buffers hold a mixture of the stopping iteration's by-products and recomputed
 // ones, the host-side flags describe iterations that did not happen - the factors and ADMM variables are exact.
 static void forget_byproducts(mcl_context *c) {
-    c->b_finish_pending = false;
+    c->step = StepRound{};
     c->diag_pending = c->diag_crossed_sweep = false;
-    c->step_fuse = c->step_stats = false;
-    c->b_systems_valid = false;
-    c->cfrag_valid = false;
-    c->xc_valid = c->ctc_valid = c->e1_valid = false;
-    c->ctc_parts = 0;
-    c->mseg_valid = c->grpart_valid = false;
-    c->diag_valid[0] = c->diag_valid[1] = c->diag_valid[2] = false;
+    c->bp.changed(IN_ALL_STATE);  // (||X||^2 stands: X and the workspace are what they were)
 }
 
 int mcl_run(mcl_context *c, int32_t n_iter_max, int32_t update_A, int32_t update_B, int32_t update_C,
@@ -1450,7 +1383,7 @@ float *mcl_internal_buffer(mcl_context *c, int32_t which, int64_t *count) {
         case MCL_BUF_RHO_A: p = c->rhoA, n = c->I; break;
         case MCL_BUF_RHO_C: p = c->rhoC, n = 1; break;
         case MCL_BUF_CTC:
-            if (c->ctc_valid && c->ctc_parts > 0) (void)mcl_launch_ctc_fold(c);
+            if (c->bp.has(BP_CTC) && c->bp.ctc_parts > 0) (void)mcl_launch_ctc_fold(c);
             p = c->CtC, n = (int64_t)c->r * c->r;
             break;
         case MCL_BUF_LINV_B: p = c->LinvB, n = c->I * c->r * c->r; break;

@@ -980,7 +980,8 @@ int mcl_launch_build_cfrag(mcl_context *c) {
 }
 
 template <class XL, int NB>
-static int launch_xc(mcl_context *c) {
+static int launch_xc(mcl_context *c, bool with_gram, bool *did_gram) {
+    *did_gram = false;
     const int KC = xc_KC(c);
     const long nblk = (c->N + 15) / 16;
     long target_waves = 1024;  // measured best: one 256-thread block per CU
@@ -1002,7 +1003,7 @@ static int launch_xc(mcl_context *c) {
         const int n_segs = c->segs.n_tiles;
         const unsigned g = (unsigned)((c->n_seg_waves + 3) / 4);
         // 0: X C only; 1: + per-segment rhs / Gram in fp32 chains (penalised A); 2: in fp64 (penalty-free A)
-        int gram = !c->xc_with_gram ? 0 : (c->regs[0].n == 0 ? 2 : 1);
+        int gram = !with_gram ? 0 : (c->regs[0].n == 0 ? 2 : 1);
         if (NB == 4 && gram == 2) gram = 0;  // rank > 32 has no registers for the fp64 Gram tiles: k_slab_gram follows
 #define MCL_XCR_(CREG_, GRAM_, NT_)                                                                                  \
     hipLaunchKernelGGL((MCL_XKERNEL(k_contract_xc_row, NB, CREG_, GRAM_, NT_)), dim3(g), dim3(256), sm, c->stream, mcl_x<XL>(c), c->Cfrag, \
@@ -1018,7 +1019,7 @@ static int launch_xc(mcl_context *c) {
         };
         if (n_segs > 0 && !creg && mcl_try_contract_xc_lds(c, gram)) {
             // K % 512 == 0 with the fragment image of C resident in LDS and four X tiles in flight per wave (xclds.hip)
-            c->xc_did_gram = gram != 0;
+            *did_gram = gram != 0;
             char bufl[96];
             snprintf(bufl, sizeof bufl, "k_contract_xc_lds%s<%sNB=%d,GRAM=%d>", mcl_x_kname<XL>(), mcl_x_targ<XL>(), NB, gram);
             c->variant[MCL_PROF_XC] = bufl;
@@ -1043,7 +1044,7 @@ static int launch_xc(mcl_context *c) {
             if (!creg) launch_row(std::false_type{});
         }
 #undef MCL_XCR_
-        c->xc_did_gram = gram != 0;
+        *did_gram = gram != 0;
         char buf[96];
         if (creg && !c->sw.xc_depth1)
             snprintf(buf, sizeof buf, "k_contract_xc_256%s<%sDEPTH=2,GRAM=%d>", mcl_x_kname<XL>(), mcl_x_targ<XL>(), gram);
@@ -1053,7 +1054,6 @@ static int launch_xc(mcl_context *c) {
         MCL_CHECK_HIP(c, hipGetLastError());
         return 0;
     }
-    c->xc_did_gram = false;
 #define MCL_XC(NB_, VEC_, KCT_)                                                                                     \
     hipLaunchKernelGGL((MCL_XKERNEL(k_contract_xc, NB_, VEC_, KCT_)), dim3(grid), dim3(256), 0, c->stream, mcl_x<XL>(c), c->Cfrag, c->XC, \
                        (long)c->N, (int)c->K, c->r, KC, bpw, nblk, dbg)
@@ -1074,12 +1074,12 @@ static int launch_xc(mcl_context *c) {
     return 0;
 }
 
-int mcl_launch_contract_xc(mcl_context *c) {
+int mcl_launch_contract_xc(mcl_context *c, bool with_gram, bool *did_gram) {
     return mcl_x_dispatch(c->x_type, [&](auto xl) {
         using XL = decltype(xl);
-        if (c->NB == 1) return launch_xc<XL, 1>(c);
-        if (c->NB == 2) return launch_xc<XL, 2>(c);
-        return launch_xc<XL, 4>(c);
+        if (c->NB == 1) return launch_xc<XL, 1>(c, with_gram, did_gram);
+        if (c->NB == 2) return launch_xc<XL, 2>(c, with_gram, did_gram);
+        return launch_xc<XL, 4>(c, with_gram, did_gram);
     });
 }
 

@@ -311,7 +311,7 @@ int mcl_launch_rows_diag(mcl_context *c, int mode) {
         else MCL_RD(4, false);
     }
 #undef MCL_RD
-    c->diag_rows[mode] = tm.n_tiles;  // one row per tile
+    c->bp.diag_rows[mode] = tm.n_tiles;  // one row per tile
     MCL_CHECK_HIP(c, hipGetLastError());
     return 0;
 }
@@ -334,8 +334,8 @@ DiagTables mcl_diag_tables(const mcl_context *c, bool a_from_rows) {
     DiagTables T;
     T.tab[0] = a_from_rows ? c->diagA_row : c->diagA_tile;
     T.rows[0] = a_from_rows ? (int)c->I : c->tilesA.n_tiles;
-    T.tab[1] = c->diagB_tile, T.rows[1] = c->diag_rows[1];
-    T.tab[2] = c->diagC_tile, T.rows[2] = c->diag_rows[2];
+    T.tab[1] = c->diagB_tile, T.rows[1] = c->bp.diag_rows[1];
+    T.tab[2] = c->diagC_tile, T.rows[2] = c->bp.diag_rows[2];
     for (int m = 0; m < 3; ++m) T.nreg[m] = c->regs[m].n;
     T.e1 = c->e1, T.I = (int)c->I, T.xsq = c->x_sq;
     return T;

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/matcouply_hip.h"
+#include "byproducts.h"
 
 #define DIAG_COLS (2 + MCL_MAX_REGS)
 #define MCL_SEG_ROWS 256
@@ -76,6 +77,30 @@ struct ModeView {
     const int *gate;       // stop flag of a gated run (mcl_run with a stopping rule), else NULL: see MCL_GATE
 };
 
+// How the prox of one penalty is to be launched (mcl_launch_generic_prox_local / _finish; passed by value)
+struct ProxForm {
+    bool stack_fused = false;      // statistics kernels only: one fused prox + dual row pass follows for the whole stack
+    bool stats_in_solve = false;   // ... and the B-mode statistics (PARAFAC2 Gram, L2-ball column norms) already came out of the
+                                   // solve pass (k_rows_solve_stats + k_stats_reduce)
+    bool pf2_delta_fused = false;  // single-process inner loop: k_pf2_sum_delta instead of k_pf2_sum / (all-reduce) / k_pf2_delta
+};
+
+// Step API: one mcl_B_solve .. mcl_B_prox_* round (round_complete and mcl_B_solve start a new one)
+struct StepRound {
+    bool fuse = false, stats = false;  // ProxForm::stack_fused / stats_in_solve of the round
+    unsigned done_mask = 0;            // penalties finished in this round
+    bool finish_pending = false;       // the fused prox + dual pass of the round has not been issued yet (flush_B_finish)
+};
+
+// What mcl_A_begin decides and mcl_A_finish launches (afinish.h: AFuse)
+struct APlan {
+    bool use_seg_gram = false;    // k_A_finish sums seg_rhs / seg_btb instead of reading rhsA / BtB
+    bool seg_from_sweep = false;  // ... over the sweep's bsegs (seg_rhs / part_btb) instead of segments
+    bool rhs_from_M = false;      // k_A_finish_rows forms rhs_i from the sweep's M_bseg itself
+    bool rhs_wide = false;        // ... with one workgroup (four waves) per slab: k_A_finish_rows_wide
+    bool rhs_pairs = false;       // ... or two slabs per workgroup (one system + one streaming wave each)
+};
+
 // MCL_* environment switches (A/B experiments, debug paths): read ONCE per context in mcl_create(), never on a launch
 // path - a getenv() is a linear scan of the environment and is not safe against a concurrent setenv().
 struct mcl_switches {
@@ -137,7 +162,6 @@ struct mcl_context {
     float *GRpart = nullptr;       // [n_bsegs, (16 NB)^2 + 16 NB]  per-bseg a-weighted Gram and the a_i it was weighted with
     int n_grpart = 0;
     long long *sweep_cycles = nullptr;  // [n_blocks, 4 waves, 6] per-section cycle counts (MCL_SWEEP_DBG & 32)
-    bool grpart_valid = false;     // GRpart was weighted with the current A (and mseg_valid)
     bool sweep_planned = false;    // the workspace holds the sweep buffers
     // exact-products mode: fp64 shadow state of the inner loops of modes 1 / 2 (wide.hip): factor, auxiliary and dual
     // variables for the length of a phase, the PARAFAC2 coordinate matrix
@@ -145,11 +169,8 @@ struct mcl_context {
     double *wZ[3][MCL_MAX_REGS] = {}, *wU[3][MCL_MAX_REGS] = {};
     double *wD = nullptr;
     double *LinvA64 = nullptr, *rhsA64 = nullptr, *Q64 = nullptr;  // fp64 copies of the A-phase systems / right-hand sides / cross products (mode 0 of wide.hip, k_A_e1)
-    bool a64_valid = false;  // ... and they belong to the systems mcl_launch_A_finish(fused_inner = false) built last
     double *exact_part = nullptr;  // exact-products mode: [G | R] per 256-row chunk (fp64), summed in a fixed order
     bool exact = false;            // exact-products mode (small problems): X C, [G | R] and the A-phase tables from fp64 sums of exact products
-    bool mseg_valid = false;       // Mpart / part_btb correspond to the current B
-    bool seg_from_sweep = false;   // k_A_finish sums seg_rhs / part_btb over bsegs instead of segments
     float *XC = nullptr;        // [N, r]   X C  (cached between the A-phase and the next B-phase)
     float *Cfrag = nullptr;     // C in MFMA-fragment order for the X C kernel
     float *CtC = nullptr;       // [r, r]
@@ -183,9 +204,6 @@ struct mcl_context {
     std::vector<int> h_wave_seg_ptr;
     int n_seg_waves = 0;
     std::vector<int> h_slab_seg_ptr;
-    bool xc_with_gram = false;  // request: the next X C launch also produces seg_rhs / seg_btb
-    bool xc_did_gram = false;   // the last X C launch produced them
-    bool use_seg_gram = false;  // k_A_finish sums seg_rhs / seg_btb instead of reading rhsA / BtB
     float *rhsA = nullptr;      // [I, r]
     float *BtB = nullptr;       // [I, r, r]  -> overwritten by Q_i = BtB_i o CtC (cross_products)
     float *rhoA = nullptr;      // [I]
@@ -224,10 +242,8 @@ struct mcl_context {
     DiagTables diag_pending_T{};
     double *diag_pending_out = nullptr;
     int diag_pending_incl = 1;
-    // launch fusion of the A-phase finish (afinish.h: AFuse)
-    bool a_rhs_from_M = false;       // k_A_finish_rows forms rhs_i from the sweep's M_bseg itself
-    bool a_rhs_wide = false;         // ... with one workgroup (four waves) per slab: k_A_finish_rows_wide
-    bool a_rhs_pairs = false;        // ... or two slabs per workgroup (one system + one streaming wave each)
+    APlan a_plan;  // what mcl_A_begin decided for mcl_A_finish / mcl_A_factor
+    StepRound step;
 
     double *gl2_T = nullptr;    // [max rows, r] fp64: U^T Y of the GeneralizedL2 prox / U^T F of its value
     double *colsq = nullptr;    // [max(I,1), r]   per-slab column sums of squares (L2Ball)
@@ -244,29 +260,14 @@ struct mcl_context {
     double *pf2_qr = nullptr;   // [N * r] fp64: Y_i Delta^T of the slabs k_pf2_polar_qr takes
     float *pf2_red = nullptr;   // [r*r + 1]  sum over this context's slabs (all-reduced by a multi-GPU host)
     std::vector<int> h_row_ptr32, h_ext;
-    bool e1_from_raw_gram = false;  // BtB buffer holds B_i^T B_i (true) or Q_i = B_i^T B_i o CtC (false)
     int n_part = 0;
 
-    // validity of cached by-products
-    bool xc_valid = false;      // XC == X @ C for the current C
-    bool ctc_valid = false;     // CtC == C^T C for the current C
-    int ctc_parts = 0;          // > 0: ... as that many partial blocks in CtCpart, not yet folded (k_C_finish_multi)
-    double *CtCpart = nullptr;  // [16, 16, 16] fp64
-    bool cfrag_valid = false;   // Cfrag is the fragment image of the current C
-    bool e1_valid = false;      // e1/rhsA/BtB consistent with the current factors (A-phase just ran)
-    bool diag_valid[3] = {false, false, false};  // per-mode diag tables consistent with factors/aux
-    bool diagA_from_rows = false;
-    bool xsq_valid = false;
-    bool b_systems_valid = false;  // rhoB/LinvB already hold the systems of the coming B-phase (built by A-finish)
-    int diag_rows[3] = {0, 0, 0};  // rows currently valid in diagA_row / diagB_tile / diagC_tile
-    bool b_begun = false;
-    bool stack_fused = false;  // generic inner loop: statistics kernels only, then one fused prox + dual row pass
-    bool step_fuse = false, step_stats = false;  // the same two decisions for the current mcl_B_solve .. mcl_B_prox_* round
-    unsigned step_done_mask = 0;                 // penalties finished in this round
-    bool b_finish_pending = false;  // step API: the fused prox + dual pass of the last inner iteration has not been issued yet
-    bool pf2_delta_fused = false;  // single-process inner loop: k_pf2_sum_delta instead of k_pf2_sum / (all-reduce) / k_pf2_delta
-    bool stats_in_solve = false;   // ... and the B-mode statistics (PARAFAC2 Gram, L2-ball column norms) already came out of
-                                   // the solve pass (k_rows_solve_stats + k_stats_reduce)
+    // The cached by-products of the factors: which of XC, CtC, Cfrag, Mpart / part_btb, GRpart, e1 / rhsA / BtB, rhoB / LinvB,
+    // the fp64 A systems, x_sq and the three diagnostics tables are current.  What each is computed from stands in ONE
+    // table, BP_DEPENDS_ON of byproducts.h; an entry point names what it changes (bp.changed(IN_C | IN_ADMM(2))), a launch
+    // site what it produced (bp.made(BP_XC)), and nothing else decides what falls.
+    Byproducts bp;
+    double *CtCpart = nullptr;  // [16, 16, 16] fp64 partial blocks of C^T C (bp.ctc_parts of them)
     std::vector<int> h_slab_tile_ptr;  // first B tile of every slab
     int *slab_tile_ptr = nullptr;      // int32[I+1]
     double *stat_gram = nullptr;       // [tilesB, (16 NB)^2]  per-tile Y^T Y, Y = B + U_pf2 (fp64 MFMA result order)
@@ -339,7 +340,8 @@ static inline bool mcl_rows_vec_ok(int r, const RegSet &rs, const void *F, const
 
 // ---- launchers implemented in contract.hip ---------------------------------------------------------
 int mcl_launch_build_cfrag(mcl_context *c);
-int mcl_launch_contract_xc(mcl_context *c);                      // XC = X @ C
+// XC = X @ C; with_gram: the kernels that can also leave the per-segment rhs / Gram of the A-phase (*did_gram: this one did)
+int mcl_launch_contract_xc(mcl_context *c, bool with_gram, bool *did_gram);
 int mcl_launch_contract_xt(mcl_context *c);                      // partials of [G | R]
 int mcl_launch_reduce_partials(mcl_context *c);                  // GR = sum of partials
 int mcl_launch_slab_gram(mcl_context *c);                        // rhsA, BtB from B and XC
@@ -415,11 +417,11 @@ int mcl_launch_A_rows_solve(mcl_context *c, double *change_part = nullptr);
 int mcl_launch_rows_solve_stats(mcl_context *c);         // B solve + per-tile statistics + reduce
 int mcl_launch_rows_finish_solve_stats(mcl_context *c);  // finish of iteration t + solve / stats of t + 1
 int mcl_launch_rows_finish_fused(mcl_context *c, int mode, bool want_diag);
-int mcl_launch_generic_prox_local(mcl_context *c, int mode, int k);   // prox of penalty k: dispatches on its kind into the files below
-int mcl_launch_generic_prox_finish(mcl_context *c, int mode, int k);  // ... and what has to wait for a multi-GPU host's all-reduce
+int mcl_launch_generic_prox_local(mcl_context *c, int mode, int k, ProxForm form);   // prox of penalty k: dispatches on its kind into the files below
+int mcl_launch_generic_prox_finish(mcl_context *c, int mode, int k, ProxForm form);  // ... and what has to wait for a multi-GPU host's all-reduce
 
 // ---- slabprox.hip: the slab-coupled proxes of the rarer penalties (enqueue only: the caller checks the launch error) --------
-void mcl_launch_prox_l2ball(mcl_context *c, const ModeView &mv, const RegSet &rs, int k, bool vec);  // column norms (+ scale and dual step when the stack is not fused)
+void mcl_launch_prox_l2ball(mcl_context *c, const ModeView &mv, const RegSet &rs, int k, bool vec, ProxForm form);  // column norms (+ scale and dual step when the stack is not fused)
 void mcl_launch_prox_tv(mcl_context *c, const ModeView &mv, const RegSet &rs, int k);       // aux only: k_rows_dual follows
 void mcl_launch_prox_gl2(mcl_context *c, const ModeView &mv, const RegSet &rs, int k);      // aux and dual
 void mcl_launch_prox_simplex(mcl_context *c, const ModeView &mv, const RegSet &rs, int k);  // aux only: k_rows_dual follows
@@ -429,8 +431,8 @@ int mcl_launch_simplex_wide(mcl_context *c, int mode, int k, const double *F64, 
 
 // ---- pf2polar.hip: the PARAFAC2 prox of mode 1 around its row passes ------------------------------------------------------
 bool mcl_stats_reduce_in_algebra(const mcl_context *c);
-int mcl_launch_pf2_polar(mcl_context *c, int k);  // S_i (unless the solve pass left it), then T_i and rho_i T_i^T S_i of every slab
-void mcl_launch_pf2_sum(mcl_context *c, int k);   // ... summed over the slabs (single process: and the new Delta); enqueue only
+int mcl_launch_pf2_polar(mcl_context *c, int k, ProxForm form);  // S_i (unless the solve pass left it), then T_i and rho_i T_i^T S_i of every slab
+void mcl_launch_pf2_sum(mcl_context *c, int k, ProxForm form);   // ... summed over the slabs (single process: and the new Delta); enqueue only
 void mcl_launch_pf2_delta(mcl_context *c, int k);  // Delta from the (all-reduced) sums; enqueue only
 int mcl_launch_pf2_jacobi_wide(mcl_context *c, int k, const double *F64, const double *U64, const double *D64);  // T_i from the fp64 state of wide.hip
 

@@ -910,10 +910,10 @@ static int pf2_jacobi_qr(mcl_context *c, int k, bool jacobi, int use_status, boo
 }
 
 // S_i = Y_i^T Y_i (unless the solve pass produced it), then T_i and rho_i T_i^T S_i of every slab
-int mcl_launch_pf2_polar(mcl_context *c, int k) {
+int mcl_launch_pf2_polar(mcl_context *c, int k, ProxForm form) {
     const RegSet &rs = c->regs[1];
     const int r = c->r;
-    if (c->stats_in_solve) {
+    if (form.stats_in_solve) {
         // S_i already produced by k_rows_solve_stats + k_stats_reduce
     } else if (c->NB == 1)
         hipLaunchKernelGGL(k_pf2_gram<1>, dim3((unsigned)c->I), dim3(256), 0, c->stream, c->row_ptr_dev, c->B, rs.dual[k], r, c->pf2_S);
@@ -924,7 +924,7 @@ int mcl_launch_pf2_polar(mcl_context *c, int k) {
     const bool ns = c->NB <= 2 && !c->sw.pf2_jacobi;  // Newton-Schulz first
     if (ns) {
         TileStats ts{c->slab_tile_ptr, c->stat_gram, c->stat_colsq, c->colsq, 16 * c->NB, (int)c->I};
-        const bool tiles = c->stats_in_solve && mcl_stats_reduce_in_algebra(c);
+        const bool tiles = form.stats_in_solve && mcl_stats_reduce_in_algebra(c);
 #define MCL_NS(NB_, TILES_)                                                                                          \
     hipLaunchKernelGGL((k_pf2_algebra_ns<NB_, TILES_>), dim3((unsigned)((c->I + NsShape<NB_>::SPW - 1) / NsShape<NB_>::SPW)),                   \
                        dim3(64 * NsShape<NB_>::SPW + (((TILES_) && (NB_) == 1) ? 64 : 0)), 0, c->stream, c->pf2_S,                  \
@@ -954,9 +954,9 @@ int mcl_launch_pf2_polar(mcl_context *c, int k) {
 }
 
 // sum over the slabs of rho_i T_i^T S_i | rho_i (behind the row pass that applies T_i: rows.hip)
-void mcl_launch_pf2_sum(mcl_context *c, int k) {
+void mcl_launch_pf2_sum(mcl_context *c, int k, ProxForm form) {
     const int n2 = c->r * c->r;
-    if (c->pf2_delta_fused)  // single-process inner loop: Delta follows at once, no all-reduce in between
+    if (form.pf2_delta_fused)  // single-process inner loop: Delta follows at once, no all-reduce in between
         hipLaunchKernelGGL(k_pf2_sum_delta, dim3((unsigned)n2), dim3(256), 0, c->stream, c->pf2_acc, (int)c->I, n2,
                            c->pf2_red, c->regs[1].aux2[k], c->gate_active);
     else

@@ -519,7 +519,7 @@ int mcl_launch_inner_check_raw(mcl_context *c, bool begin, const double *change_
 
 int mcl_launch_inner_check(mcl_context *c, int mode, bool begin) {
     const int n_change = (mode == 0) ? (int)c->I : mcl_tiles(c, mode).n_tiles;
-    return mcl_launch_inner_check_raw(c, begin, c->inner_part, n_change, mcl_diag_tile(c, mode), c->diag_rows[mode], c->regs[mode].n);
+    return mcl_launch_inner_check_raw(c, begin, c->inner_part, n_change, mcl_diag_tile(c, mode), c->bp.diag_rows[mode], c->regs[mode].n);
 }
 
 int mcl_launch_rows_solve(mcl_context *c, int mode, double *change_part) {
@@ -547,7 +547,7 @@ int mcl_launch_A_rows_solve(mcl_context *c, double *change_part) {
 
 // The local part of the prox of penalty k.  A kind that needs more than a row pass calls into the file that owns it; what is
 // enqueued here keeps the order of the steps on the stream.
-int mcl_launch_generic_prox_local(mcl_context *c, int mode, int k) {
+int mcl_launch_generic_prox_local(mcl_context *c, int mode, int k, ProxForm form) {
     ModeView mv = view_of(c, mode);
     if (mv.n_tiles == 0) return 0;
     const RegSet &rs = c->regs[mode];
@@ -559,7 +559,7 @@ int mcl_launch_generic_prox_local(mcl_context *c, int mode, int k) {
         case MCL_PEN_NN:
         case MCL_PEN_BOX:
         case MCL_PEN_L1:
-            if (c->stack_fused) break;  // no statistics; the fused finish pass does the prox
+            if (form.stack_fused) break;  // no statistics; the fused finish pass does the prox
             if (mode == 0 && !c->opt.constant_A) {  // per-row feasibility penalties (the un-fused A loop of the inner stopping test)
                 hipLaunchKernelGGL(k_A_rows_prox, dim3((unsigned)((c->I * c->r + 255) / 256)), dim3(256), 0, c->stream,
                                    (const float *)c->rhoA, c->A, rs, k, (int)c->I, c->r);
@@ -568,11 +568,11 @@ int mcl_launch_generic_prox_local(mcl_context *c, int mode, int k) {
             DISPATCH_ROWS(c, vec, k_rows_prox_rowsep, grid, block, mv, rs, k, c->r);
             break;
         case MCL_PEN_L2BALL:
-            mcl_launch_prox_l2ball(c, mv, rs, k, vec);
+            mcl_launch_prox_l2ball(c, mv, rs, k, vec, form);
             break;
         case MCL_PEN_UNIMODAL:
             if (int rc = mcl_launch_unimodal(c, mv.ext, mv.n_slabs, mv.F, rs, mode, k)) return rc;  // unimodal.hip
-            if (!c->stack_fused)  // the fused finish pass updates the dual
+            if (!form.stack_fused)  // the fused finish pass updates the dual
                 DISPATCH_ROWS(c, vec, k_rows_dual, grid, block, mv, rs, k, c->r);
             break;
         case MCL_PEN_TV:
@@ -584,10 +584,10 @@ int mcl_launch_generic_prox_local(mcl_context *c, int mode, int k) {
                 c->err = "PARAFAC2 constraint can only be imposed with mode=1";
                 return 1;
             }
-            if (int rc = mcl_launch_pf2_polar(c, k)) return rc;
-            if (!c->stack_fused)  // the fused finish pass applies T_i itself
+            if (int rc = mcl_launch_pf2_polar(c, k, form)) return rc;
+            if (!form.stack_fused)  // the fused finish pass applies T_i itself
                 DISPATCH_ROWS(c, vec, k_pf2_apply, grid, block, mv, (const float *)rs.dual[k], (const float *)c->pf2_T, rs.aux[k], c->r);
-            mcl_launch_pf2_sum(c, k);
+            mcl_launch_pf2_sum(c, k, form);
             break;
         case MCL_PEN_GL2:
             mcl_launch_prox_gl2(c, mv, rs, k);
@@ -604,13 +604,13 @@ int mcl_launch_generic_prox_local(mcl_context *c, int mode, int k) {
     return 0;
 }
 
-int mcl_launch_generic_prox_finish(mcl_context *c, int mode, int k) {
+int mcl_launch_generic_prox_finish(mcl_context *c, int mode, int k, ProxForm form) {
     const RegSet &rs = c->regs[mode];
     if (rs.kind[k] != MCL_PEN_PARAFAC2) return 0;  // dual update already fused into the local step
     ModeView mv = view_of(c, mode);
     if (mv.n_tiles == 0) return 0;
-    if (!c->pf2_delta_fused) mcl_launch_pf2_delta(c, k);
-    if (!c->stack_fused) {  // (the dual update of a fused stack rides in its finish pass)
+    if (!form.pf2_delta_fused) mcl_launch_pf2_delta(c, k);
+    if (!form.stack_fused) {  // (the dual update of a fused stack rides in its finish pass)
         dim3 grid((unsigned)((mv.n_tiles + 3) / 4)), block(256);
         const bool vec = mcl_rows_vec_ok(c->r, rs, mv.F);
         DISPATCH_ROWS(c, vec, k_rows_pf2_dual, grid, block, mv, rs, k, c->r);
@@ -655,7 +655,7 @@ int mcl_launch_rows_finish_fused(mcl_context *c, int mode, bool want_diag) {
                       diag, want_diag ? 1 : 0, (const double *)nullptr);
     }
     MCL_CHECK_HIP(c, hipGetLastError());
-    if (want_diag) c->diag_rows[mode] = mv.n_tiles;  // one row per tile, as k_rows_diag writes them
+    if (want_diag) c->bp.diag_rows[mode] = mv.n_tiles;  // one row per tile, as k_rows_diag writes them
     return 0;
 }
 

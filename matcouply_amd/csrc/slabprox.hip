@@ -294,9 +294,9 @@ __global__ __launch_bounds__(256) void k_slab_simplex(const int *__restrict__ ex
 // =========================================================================================================
 // host launchers
 // =========================================================================================================
-void mcl_launch_prox_l2ball(mcl_context *c, const ModeView &mv, const RegSet &rs, int k, bool vec) {
-    if (c->stack_fused) {  // statistics only; slot k of the colsq table
-        if (c->stats_in_solve) return;  // already produced by k_rows_solve_stats + k_stats_reduce
+void mcl_launch_prox_l2ball(mcl_context *c, const ModeView &mv, const RegSet &rs, int k, bool vec, ProxForm form) {
+    if (form.stack_fused) {  // statistics only; slot k of the colsq table
+        if (form.stats_in_solve) return;  // already produced by k_rows_solve_stats + k_stats_reduce
         hipLaunchKernelGGL(k_slab_colsq, dim3((unsigned)mv.n_slabs), dim3(256), 0, c->stream, mv.ext, mv.F,
                            rs.dual[k], rs.nonneg[k], c->r, c->RP, c->colsq + (long)k * mv.n_slabs * c->r);
         return;

@@ -962,7 +962,7 @@ static int launch_sweep_v(mcl_context *c) {
     }
 #undef MCL_SWEEP_LAUNCH
     MCL_CHECK_HIP(c, hipGetLastError());
-    c->diag_rows[1] = grid;
+    c->bp.diag_rows[1] = grid;
     c->n_grpart = c->n_parts;  // one partial per bseg, or per group of four bsegs of a slab
     char buf[96];
     snprintf(buf, sizeof buf, "k_sweep%s<%sKS=%d,NB=%d,NREG=%d,DEPTH=%d,NW=%d,VEC=%d>", mcl_x_kname<XL>(), mcl_x_targ<XL>(), KS, NB,

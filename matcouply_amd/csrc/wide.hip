@@ -782,8 +782,8 @@ int mcl_wide_phase(mcl_context *c, int mode) {
         hipLaunchKernelGGL(k_wide_rowsep, dim3((unsigned)W.n_tiles), dim3(64 * subs), sm_rs, c->stream, W, rhs64, Arows, Linv64, F32, rs, r,
                            n_it, diag);
         MCL_CHECK_HIP(c, hipGetLastError());
-        c->diag_rows[mode] = W.n_tiles;
-        c->diag_valid[mode] = true;  // the kernel left the mode's diagnostics table
+        c->bp.diag_rows[mode] = W.n_tiles;
+        c->bp.made(BP_DIAG(mode));  // the kernel left the mode's diagnostics table
         return 0;
     }
     c->variant[MCL_PROF_ROWS_FUSED] = "k_wide_* (fp64 state, one kernel per step)";

@@ -134,7 +134,7 @@ def options(n=1, **fields):
 def weights(rows):
     a = np.ascontiguousarray(rows, dtype=np.float64)
     _keep.append(a)
-    return a.ctypes.data
+    return ctypes.c_void_p(a.ctypes.data)  # (not the bare address: an int would go into the case's id, another in every process)
 
 
 PEN = _engine
