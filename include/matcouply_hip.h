@@ -378,6 +378,22 @@ int mcl_multistart_run_weighted(const void *X, int32_t x_type, const int64_t *ro
                                 const mcl_multistart_options *opt, int32_t n_jobs, const double *slab_weights, double *state,
                                 double *diag, int32_t *n_iter, int32_t *stop, void *workspace, int64_t workspace_bytes,
                                 void *hip_stream);
+/* Jobs on data with missing entries in the same launch (cmf_aoadmm_missing: EM imputation, element-wise cross-validation).
+ * observed: DEVICE uint8 [n_masks, N, K], 1 = observed; n_masks is 1 (one mask for all jobs) or n_jobs, job s reads mask
+ * s % n_masks.  Every job keeps an fp64 copy X~ of X in the workspace: X at its observed entries; at the others its mask's row
+ * of fill_values (DEVICE fp64 [n_masks, K], a constant per column) or, with fill_values NULL, the model B_i D_i C^T of its
+ * start.  An outer iteration is the B, C and A phases of mcl_multistart_run on X~, then one pass with M = B_i D_i C^T that sums
+ * (X - M)^2 over the observed entries and stores M into the others; rec_error = sqrt(that sum) / sqrt(sum of X^2 over the
+ * observed entries), loss = 0.5 rec_error^2 + regularisation, gaps and the stopping rule as for mcl_multistart_run.  Row 0 of
+ * diag is the same pass on the start (it stores M only with fill_values NULL).  The value of X at a missing entry is never
+ * used: it may be NaN.  Errors, before any launch: what mcl_multistart_run refuses, n_masks not 1 or n_jobs, a NULL mask.
+ * A job's result does not depend on n_jobs or on its neighbours. */
+int64_t mcl_multistart_missing_workspace_bytes(const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank,
+                                               const mcl_multistart_options *opt, int32_t n_jobs);
+int mcl_multistart_run_missing(const void *X, int32_t x_type, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank,
+                               const mcl_multistart_options *opt, int32_t n_jobs, const uint8_t *observed, int32_t n_masks,
+                               const double *fill_values, double *state, double *diag, int32_t *n_iter, int32_t *stop,
+                               void *workspace, int64_t workspace_bytes, void *hip_stream);
 
 /* ---- many random starts of parafac2_als at once (parafac2_als_multistart, csrc/pf2als_multistart.hip) ---------------------- */
 /* One workgroup per start runs the whole unconstrained PARAFAC2-ALS fit of mcl_parafac2_als_typed (projections from the polar

@@ -63,6 +63,7 @@ EXPORTED_SYMBOLS = [
     "mcl_multistart_workspace_bytes", "mcl_multistart_run", "mcl_multistart_last_error",
     "mcl_multistart_grid_workspace_bytes", "mcl_multistart_run_grid",
     "mcl_multistart_weighted_workspace_bytes", "mcl_multistart_run_weighted",
+    "mcl_multistart_missing_workspace_bytes", "mcl_multistart_run_missing",
     "mcl_parafac2_als_workspace_bytes", "mcl_parafac2_als_typed", "mcl_parafac2_als_last_error",
     "mcl_pf2als_multistart_workspace_bytes", "mcl_pf2als_multistart_run", "mcl_pf2als_multistart_last_error",
     "mcl_pf2als_multistart_run_weighted",
@@ -203,6 +204,9 @@ def load_library():
         "mcl_multistart_weighted_workspace_bytes": (I64, [ctypes.POINTER(I64), I64, I64, I32, ctypes.POINTER(MultistartOptions), I32]),
         "mcl_multistart_run_weighted": (ctypes.c_int, [P, I32, ctypes.POINTER(I64), I64, I64, I32, ctypes.POINTER(MultistartOptions),
                                                        I32, P, P, P, P, P, P, I64, P]),
+        "mcl_multistart_missing_workspace_bytes": (I64, [ctypes.POINTER(I64), I64, I64, I32, ctypes.POINTER(MultistartOptions), I32]),
+        "mcl_multistart_run_missing": (ctypes.c_int, [P, I32, ctypes.POINTER(I64), I64, I64, I32, ctypes.POINTER(MultistartOptions),
+                                                      I32, P, I32, P, P, P, P, P, P, I64, P]),
         "mcl_parafac2_als_workspace_bytes": (I64, [ctypes.POINTER(I64), I64, I64, I32]),
         "mcl_parafac2_als_typed": (ctypes.c_int, [P, I32, ctypes.POINTER(I64), I64, I64, I32, P, P, P, I32, I32, ctypes.c_double,
                                                   ctypes.c_double, I32, P, P, P, P, P, P, P, I64, P]),
@@ -662,6 +666,39 @@ def multistart_run_weighted(X, row_ptr, rank, options, slab_weights, state):
         return lib.mcl_multistart_run_weighted(X_, xt, rp, I, K, r, opt, S, wp, *tail)
 
     return _multistart_launch(X, row_ptr, rank, options, None, state, lib.mcl_multistart_weighted_workspace_bytes, run)
+
+
+def multistart_missing_workspace_bytes(I, N, K, rank, n_jobs):
+    """mcl_multistart_missing_workspace_bytes restated: the plan of mcl_multistart_run (row_ptr, the row -> slab map, n_jobs
+    scratch slices) and behind it the jobs' fp64 copies of X, [n_jobs, N, K]; every part on a 256-byte boundary"""
+    al = lambda n: (max(n, 1) + 255) & ~255
+    plan = al((I + 1) * 8) + (al(N * 4) if N else 0) + al(multistart_scratch_len(I, N, K, rank) * 8 * n_jobs)
+    return plan + ((n_jobs * N * K * 8 + 255) & ~255)
+
+
+def multistart_run_missing(X, row_ptr, rank, options, observed, fill_values, state):
+    """multistart_run on data with missing entries (mcl_multistart_run_missing): `observed` a uint8 CUDA tensor [n_masks, N, K]
+    (1 = observed) with n_masks 1 or state.shape[0]; `fill_values` a float64 CUDA tensor [n_masks, K] (the start of the missing
+    entries, a constant per column) or None (they start as the start's model) -> (diag, n_iter, stop) as multistart_run, with
+    rec_error and loss over the observed entries.  The values of X at missing entries are never used."""
+    import torch
+
+    lib = load_library()
+    S, N, K = int(state.shape[0]), int(X.shape[0]), int(X.shape[1])
+    if not (torch.is_tensor(observed) and observed.is_cuda and observed.dtype == torch.uint8 and observed.is_contiguous()
+            and observed.dim() == 3 and tuple(observed.shape[1:]) == (N, K)):
+        raise EngineError(f"observed must be a contiguous uint8 CUDA tensor [n_masks, {N}, {K}]")
+    n_masks = int(observed.shape[0])
+    if fill_values is not None and not (torch.is_tensor(fill_values) and fill_values.is_cuda and fill_values.dtype == torch.float64
+                                        and fill_values.is_contiguous() and tuple(fill_values.shape) == (n_masks, K)):
+        raise EngineError(f"fill_values must be a contiguous float64 CUDA tensor [{n_masks}, {K}] or None")
+    fp = fill_values.data_ptr() if fill_values is not None else None
+
+    def run(X_, xt, rp, I, K_, r, opt, S_, *tail):
+        # (the refusal path of _multistart_launch passes no X: the mask goes along, so that the library's own sentence comes back)
+        return lib.mcl_multistart_run_missing(X_, xt, rp, I, K_, r, opt, S_, observed.data_ptr(), n_masks, fp, *tail)
+
+    return _multistart_launch(X, row_ptr, rank, options, None, state, lib.mcl_multistart_missing_workspace_bytes, run)
 
 
 class NativeReg:

@@ -28,6 +28,12 @@
 // cmf_aoadmm_grid: the same launch with options of its own for every workgroup (mcl_multistart_run_grid).  The workgroup copies
 // jobs[blockIdx.x] over the options of its LDS copy of the arguments, which is where every helper reads them; the jobs share X
 // and one state layout (ms_check_grid), everything else - strengths, tolerances, iteration limits - is per job.
+//
+// cmf_aoadmm_missing (missing.py): k_multistart_missing is the same fit on data with missing entries, by
+// expectation-maximisation.  Every job owns an fp64 copy X~ of X in the workspace (k_missing_copy_in: X where the job's mask
+// says observed, the fill elsewhere), the phases read X~ through the fp64 loader of xload.h, and the diagnostics of every outer
+// iteration are ONE pass over the job's entries that sums (X - M)^2 over the observed ones and stores the model M = B_i D_i C^T
+// into the others (mcl_multistart_run_missing).
 #include <algorithm>
 #include <cmath>
 #include <string>
@@ -101,7 +107,12 @@ static __device__ inline double prox_value(const mcl_multistart_penalty &p, doub
 // not in the job (its rows of A, B and of every aux and dual are zeros on entry and stay exact zeros).  A weight multiplies ONE
 // factor of a product and never a product that feeds an add, so that the contraction into fused multiply-adds is the
 // unweighted kernel's and a weight of 1.0 changes no bit.  Without WEIGHTED `w` is never read.
-template <int R, class XL, bool WEIGHTED>
+//
+// MISSING: X is the job's own fp64 copy X~ (XL = XF64), `obs` the job's mask [N, K] (1 = observed).  The phases are the
+// complete-data ones on X~; impute_pass replaces model_terms.  Nothing computed from X~ lives from one outer iteration to the
+// next: every phase rebuilds its right-hand side and X C from X~, and rhs_A / Q of the A phase feed nothing here.  Without
+// MISSING `obs` and `fill_model` are never read.
+template <int R, class XL, bool WEIGHTED, bool MISSING = false>
 struct Start {
     const MsArgs &a;
     const typename XL::T *X;
@@ -113,6 +124,8 @@ struct Start {
     MsScratch sc;
     double *red, *sys, *sh;  // LDS: reduction scratch, system batch, small shared values
     int nb;                  // systems per batch
+    const uint8_t *obs;      // MISSING: the job's mask [N, K], 1 = observed
+    bool fill_model;         // MISSING: the missing entries of X~ start as the start's model (row 0 of the diagnostics stores it)
 
     __device__ int64_t rows_of(int m) const { return m == 0 ? I : (m == 1 ? N : K); }
     __device__ __forceinline__ double *F(int m) const { return m == 0 ? A : (m == 1 ? B : C); }
@@ -616,10 +629,36 @@ struct Start {
         *model = wg_sum(m, red);
     }
 
-    // one diagnostics row: rec_error, loss, flags, regularisation, gaps; returns the flags
-    __device__ __forceinline__ int diagnostics(bool from_A, double x_sq, double *row) {
-        double inner, model;
-        model_terms(from_A, &inner, &model);
+    // MISSING: one pass over the job's entries with M = B_i D_i C^T at (j, c): the sum of (X - M)^2 over the observed ones is
+    // returned, and with `store` the others get X~(j, c) = M.  Thread t takes the entries t, t + 256, ... (row-major), wg_sum adds
+    // the 256 partials: a fixed order.  The mask selects; the value of X~ at a missing entry is never used in arithmetic.
+    __device__ __forceinline__ double impute_pass(bool store) {
+        double *Xt = const_cast<double *>(reinterpret_cast<const double *>(X));
+        const int64_t n = N * K, dj = MS_THREADS / K, dc = MS_THREADS % K;
+        int64_t j = threadIdx.x / K, c = threadIdx.x % K;
+        double ss = 0.0;
+        for (int64_t e = threadIdx.x; e < n; e += MS_THREADS) {
+            const double *bj = B + j * R, *ai = A + (int64_t)slab[j] * R, *cc = C + c * R;
+            double m = 0.0;
+            #pragma unroll
+            for (int l = 0; l < R; ++l) m += (bj[l] * ai[l]) * cc[l];
+            if (obs[e]) {
+                const double d = Xt[e] - m;
+                ss += d * d;
+            } else if (store) {
+                Xt[e] = m;
+            }
+            j += dj, c += dc;
+            if (c >= K) c -= K, ++j;
+        }
+        return wg_sum(ss, red);  // (its barriers: the stores are visible to the workgroup's next pass over X~)
+    }
+
+    // one diagnostics row: rec_error, loss, flags, regularisation, gaps; returns the flags.  MISSING: `store` as in impute_pass
+    __device__ __forceinline__ int diagnostics(bool from_A, double x_sq, double *row, bool store = false) {
+        double inner = 0.0, model = 0.0, resid = 0.0;
+        if constexpr (MISSING) resid = impute_pass(store);
+        else model_terms(from_A, &inner, &model);
         double reg = 0.0, worst = -INFINITY, gaps[3][MCL_MAX_REGS];
 #pragma unroll
         for (int m = 0; m < 3; ++m) {
@@ -635,7 +674,9 @@ struct Start {
             }
             if (a.o.l2_penalty[m] != 0.0) reg += 0.5 * a.o.l2_penalty[m] * nf;
         }
-        const double rec = sqrt(fmax(0.0, x_sq - 2.0 * inner + model)) / sqrt(x_sq);
+        double rec;
+        if constexpr (MISSING) rec = sqrt(resid) / sqrt(x_sq);
+        else rec = sqrt(fmax(0.0, x_sq - 2.0 * inner + model)) / sqrt(x_sq);
         const double loss = 0.5 * rec * rec + reg;
         const bool feasible = a.o.feasibility_tol > 0.0 && worst < a.o.feasibility_tol;
         if (threadIdx.x == 0) {
@@ -656,7 +697,12 @@ struct Start {
         // ||X||^2 (every start: the same order, the same bits); WEIGHTED: sum_i w_i ||X_i||^2, in that order too
         double xs = 0.0;
         for (int64_t e = t; e < a.N * a.K; e += MS_THREADS) {
-            if constexpr (WEIGHTED) {
+            if constexpr (MISSING) {  // the observed entries alone
+                if (obs[e]) {
+                    const double v = (double)XL::ld1(X + e);
+                    xs += v * v;
+                }
+            } else if constexpr (WEIGHTED) {
                 const double wi = w[slab[e / a.K]];
                 if (wi != 0.0) {
                     const double v = (double)XL::ld1(X + e);
@@ -669,7 +715,7 @@ struct Start {
         }
         const double x_sq = wg_sum(xs, red);
 
-        int f0 = diagnostics(false, x_sq, diag);
+        int f0 = diagnostics(false, x_sq, diag, fill_model);
         if (t == 0) diag[2] = (double)(f0 | 2);
         __syncthreads();
         const mcl_multistart_options &o = a.o;
@@ -681,7 +727,7 @@ struct Start {
             if (o.update_C) phase_C();
             if (o.update_A) phase_A();
             double *row = diag + (int64_t)(it + 1) * MCL_MS_DIAG;
-            const int feasible = diagnostics(o.update_A != 0, x_sq, row);
+            const int feasible = diagnostics(o.update_A != 0, x_sq, row, true);
             __syncthreads();
             const double loss = row[1];
             const bool evaluated = !active || feasible || o.evaluate_loss_always;
@@ -699,7 +745,8 @@ struct Start {
 
 // The LDS, the arguments' LDS copy and the start object are declared in the kernels themselves, not in a function the two share:
 // where they are declared moves the register allocation of the unweighted instantiations (DESIGN.md sections 17 and 18).
-#define MS_START(WEIGHTED, WPTR)                                                                                              \
+// MORE: statements on the start object `st` of job `s` before the fit (k_multistart_missing: its slice of X~ and its mask).
+#define MS_START(WEIGHTED, MISSING, WPTR, MORE)                                                                               \
     __shared__ double red[MS_THREADS];                                                                                        \
     __shared__ double sys[MS_SYS_BYTES / 8];                                                                                  \
     __shared__ double sh[4 * R * R + 16 + MCL_MAX_REGS * R * R];                                                              \
@@ -714,7 +761,7 @@ struct Start {
         __syncthreads();                                                                                                      \
     }                                                                                                                         \
     const MsArgs &a = sa;                                                                                                     \
-    Start<R, XL, WEIGHTED> st{a, static_cast<const typename XL::T *>(a.X), a.row_ptr, a.slab_of_row, a.I, a.N, a.K, WPTR};    \
+    Start<R, XL, WEIGHTED, MISSING> st{a, static_cast<const typename XL::T *>(a.X), a.row_ptr, a.slab_of_row, a.I, a.N, a.K, WPTR}; \
     st.A = a.state + s * a.state_len;                                                                                         \
     st.B = st.A + a.I * R;                                                                                                    \
     st.C = st.B + a.N * R;                                                                                                    \
@@ -722,19 +769,46 @@ struct Start {
     st.sc = ms_scratch(a.I, a.N, a.K, R);                                                                                     \
     st.red = red, st.sys = sys, st.sh = sh;                                                                                   \
     st.nb = std::min(MS_THREADS, MS_SYS_BYTES / (2 * R * R * 8));                                                             \
+    MORE                                                                                                                      \
     st.fit(s);
 
 template <int R, class XL>
 __global__ __launch_bounds__(MS_THREADS) void k_multistart(MsArgs a0) {
-    MS_START(false, nullptr)
+    MS_START(false, false, nullptr, )
 }
 
 // job blockIdx.x under its own row of slab_weight [n_jobs, I] (fp64, device)
 template <int R, class XL>
 __global__ __launch_bounds__(MS_THREADS) void k_multistart_weighted(MsArgs a0, const double *slab_weight) {
-    MS_START(true, slab_weight + (int64_t)blockIdx.x * a0.I)
+    MS_START(true, false, slab_weight + (int64_t)blockIdx.x * a0.I, )
+}
+
+// job blockIdx.x on its own copy X~ (a0.X: fp64 [n_jobs, N, K], k_missing_copy_in) under mask blockIdx.x % n_masks of
+// observed [n_masks, N, K]
+template <int R>
+__global__ __launch_bounds__(MS_THREADS) void k_multistart_missing(MsArgs a0, const uint8_t *observed, int32_t n_masks, int32_t fill_model) {
+    using XL = XF64;
+    MS_START(false, true, nullptr,
+             st.X += s * (a.N * a.K);
+             st.obs = observed + (s % n_masks) * (a.N * a.K);
+             st.fill_model = fill_model != 0;)
 }
 #undef MS_START
+
+// X~ of every job: block s copies X (stored type, converted exactly) where mask s % n_masks says observed; elsewhere the mask's
+// row of fill_values [n_masks, K], or 0.0 without fill_values (k_multistart_missing stores the start's model there before any
+// phase reads it).  A select, never a product: X may hold NaN or anything else at a missing entry.
+template <class XL>
+__global__ __launch_bounds__(MS_THREADS) void k_missing_copy_in(const typename XL::T *X, const uint8_t *observed, int32_t n_masks,
+                                                                const double *fill_values, int64_t NK, int64_t K, double *Xt) {
+    const int64_t s = blockIdx.x, m = s % n_masks;
+    const uint8_t *ob = observed + m * NK;
+    double *out = Xt + s * NK;
+    for (int64_t e = threadIdx.x; e < NK; e += MS_THREADS) {
+        const double fill = fill_values ? fill_values[m * K + e % K] : 0.0;
+        out[e] = ob[e] ? (double)XL::ld1(X + e) : fill;
+    }
+}
 
 std::string ms_check(const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank, const mcl_multistart_options *o, int32_t n_starts) {
     if (!row_ptr || !o || I < 1 || K < 1) return "need row_ptr, options, I >= 1, K >= 1";
@@ -831,23 +905,33 @@ std::string ms_check_weights(const double *w, int32_t n_jobs, int64_t I) {
     return "";
 }
 
+// the X~ slices of mcl_multistart_run_missing in the workspace, behind the plan of mcl_multistart_run
+int64_t ms_filled_bytes(int32_t n_jobs, int64_t N, int64_t K) { return (int64_t(n_jobs) * N * K * 8 + 255) & ~int64_t(255); }
+
 // mcl_multistart_run (per_job false: *opt for every workgroup, passed in the kernarg), mcl_multistart_run_grid (per_job true:
 // opt[s] for workgroup s, uploaded to the workspace) and mcl_multistart_run_weighted (weighted true: *opt for every workgroup
-// and the host array slab_weights [n_starts, I], uploaded to the workspace)
+// and the host array slab_weights [n_starts, I], uploaded to the workspace) and mcl_multistart_run_missing (observed set: *opt for
+// every workgroup, the device mask observed [n_masks, N, K] and device fill_values [n_masks, K] or NULL)
 int ms_run(const char *who, const char *sizer, const void *X, int32_t x_type, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank,
            const mcl_multistart_options *opt, int32_t n_starts, bool per_job, bool weighted, const double *slab_weights,
-           double *state, double *diag, int32_t *n_iter, int32_t *stop, void *workspace, int64_t workspace_bytes, void *hip_stream) {
+           bool missing, const uint8_t *observed, int32_t n_masks, const double *fill_values, double *state, double *diag,
+           int32_t *n_iter, int32_t *stop, void *workspace, int64_t workspace_bytes, void *hip_stream) {
     ErrorSlot &fail = g_ms_error.named(who);
     std::string bad = per_job ? ms_check_grid(row_ptr, I, K, rank, opt, n_starts) : ms_check(row_ptr, I, K, rank, opt, n_starts);
     if (bad.empty() && weighted) bad = ms_check_weights(slab_weights, n_starts, I);
     if (!bad.empty()) return fail(bad);
+    if (missing && n_masks != 1 && n_masks != n_starts) return fail("need n_masks = 1 or n_masks = n_jobs");
+    if (missing && !observed) return fail("NULL observed mask");
     if (!X || !state || !diag || !n_iter || !stop || !workspace) return fail("NULL argument");
     if (!x_type_error(x_type).empty()) return fail(x_type_error(x_type));
     const StartsPlan p = ms_plan(workspace, row_ptr, I, K, rank, n_starts);
-    const int64_t jobs_bytes = per_job ? ms_jobs_bytes(n_starts) : (weighted ? ms_weights_bytes(n_starts, I) : 0);
+    const int64_t jobs_bytes = per_job    ? ms_jobs_bytes(n_starts)
+                               : weighted ? ms_weights_bytes(n_starts, I)
+                               : missing  ? ms_filled_bytes(n_starts, p.N, K)
+                                          : 0;
     if (workspace_refused(fail, workspace, workspace_bytes, p.total + jobs_bytes, sizer)) return 1;
     hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
-    char *extra = static_cast<char *>(workspace) + p.total;  // the jobs' options or weights, behind the plan
+    char *extra = static_cast<char *>(workspace) + p.total;  // the jobs' options, weights or X~ slices, behind the plan
     std::vector<int32_t> slab;
     if (upload_starts(p, row_ptr, I, slab, s) != hipSuccess ||
         (per_job && hipMemcpyAsync(extra, opt, int64_t(n_starts) * sizeof(mcl_multistart_options), hipMemcpyHostToDevice, s) != hipSuccess) ||
@@ -870,7 +954,21 @@ int ms_run(const char *who, const char *sizer, const void *X, int32_t x_type, co
     a.o = *opt;
     a.jobs = per_job ? reinterpret_cast<const mcl_multistart_options *>(extra) : nullptr;
     const double *slab_weight = weighted ? reinterpret_cast<const double *>(extra) : nullptr;
-    mcl_x_dispatch(x_type, [&](auto xl) {
+    if (missing) {  // the typed copy into the fp64 slices, then the fit on them: 16 instantiations, not 48
+        double *Xt = reinterpret_cast<double *>(extra);
+        mcl_x_dispatch(x_type, [&](auto xl) {
+            using XL = decltype(xl);
+            hipLaunchKernelGGL((k_missing_copy_in<XL>), dim3(n_starts), dim3(MS_THREADS), 0, s, static_cast<const typename XL::T *>(X),
+                               observed, n_masks, fill_values, p.N * K, K, Xt);
+            return 0;
+        });
+        a.X = Xt;
+        rank_exact<MS_MAX_RANK>(rank, [&](auto rc) {
+            constexpr int R = decltype(rc)::value;
+            hipLaunchKernelGGL((k_multistart_missing<R>), dim3(n_starts), dim3(MS_THREADS), 0, s, a, observed, n_masks,
+                               int32_t(fill_values == nullptr));
+        });
+    } else mcl_x_dispatch(x_type, [&](auto xl) {
         using XL = decltype(xl);
         rank_exact<MS_MAX_RANK>(rank, [&](auto rc) {
             constexpr int R = decltype(rc)::value;
@@ -900,7 +998,7 @@ int mcl_multistart_run(const void *X, int32_t x_type, const int64_t *row_ptr, in
                        const mcl_multistart_options *opt, int32_t n_starts, double *state, double *diag, int32_t *n_iter, int32_t *stop,
                        void *workspace, int64_t workspace_bytes, void *hip_stream) {
     return ms_run("mcl_multistart_run: ", "mcl_multistart_workspace_bytes", X, x_type, row_ptr, I, K, rank, opt, n_starts, false, false,
-                  nullptr, state, diag, n_iter, stop, workspace, workspace_bytes, hip_stream);
+                  nullptr, false, nullptr, 0, nullptr, state, diag, n_iter, stop, workspace, workspace_bytes, hip_stream);
 }
 
 int64_t mcl_multistart_grid_workspace_bytes(const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank,
@@ -913,7 +1011,7 @@ int mcl_multistart_run_grid(const void *X, int32_t x_type, const int64_t *row_pt
                             const mcl_multistart_options *options, int32_t n_jobs, double *state, double *diag, int32_t *n_iter,
                             int32_t *stop, void *workspace, int64_t workspace_bytes, void *hip_stream) {
     return ms_run("mcl_multistart_run_grid: ", "mcl_multistart_grid_workspace_bytes", X, x_type, row_ptr, I, K, rank, options, n_jobs, true,
-                  false, nullptr, state, diag, n_iter, stop, workspace, workspace_bytes, hip_stream);
+                  false, nullptr, false, nullptr, 0, nullptr, state, diag, n_iter, stop, workspace, workspace_bytes, hip_stream);
 }
 
 int64_t mcl_multistart_weighted_workspace_bytes(const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank,
@@ -927,7 +1025,22 @@ int mcl_multistart_run_weighted(const void *X, int32_t x_type, const int64_t *ro
                                 double *diag, int32_t *n_iter, int32_t *stop, void *workspace, int64_t workspace_bytes,
                                 void *hip_stream) {
     return ms_run("mcl_multistart_run_weighted: ", "mcl_multistart_weighted_workspace_bytes", X, x_type, row_ptr, I, K, rank, opt, n_jobs,
-                  false, true, slab_weights, state, diag, n_iter, stop, workspace, workspace_bytes, hip_stream);
+                  false, true, slab_weights, false, nullptr, 0, nullptr, state, diag, n_iter, stop, workspace, workspace_bytes, hip_stream);
+}
+
+int64_t mcl_multistart_missing_workspace_bytes(const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank,
+                                               const mcl_multistart_options *opt, int32_t n_jobs) {
+    if (!ms_check(row_ptr, I, K, rank, opt, n_jobs).empty()) return -1;
+    return ms_plan(nullptr, row_ptr, I, K, rank, n_jobs).total + ms_filled_bytes(n_jobs, row_ptr[I], K);
+}
+
+int mcl_multistart_run_missing(const void *X, int32_t x_type, const int64_t *row_ptr, int64_t I, int64_t K, int32_t rank,
+                               const mcl_multistart_options *opt, int32_t n_jobs, const uint8_t *observed, int32_t n_masks,
+                               const double *fill_values, double *state, double *diag, int32_t *n_iter, int32_t *stop,
+                               void *workspace, int64_t workspace_bytes, void *hip_stream) {
+    return ms_run("mcl_multistart_run_missing: ", "mcl_multistart_missing_workspace_bytes", X, x_type, row_ptr, I, K, rank, opt, n_jobs,
+                  false, false, nullptr, true, observed, n_masks, fill_values, state, diag, n_iter, stop, workspace, workspace_bytes,
+                  hip_stream);
 }
 
 }  // extern "C"

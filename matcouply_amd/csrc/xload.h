@@ -55,6 +55,14 @@ struct XF16 {
     static __device__ __forceinline__ float ld1(const uint16_t *p) { return h(*p); }
 };
 
+// fp64 data a kernel keeps for itself (the filled copy X~ of csrc/multistart.hip's missing-entry fit): element loads only, no
+// vector form and no place in mcl_x_dispatch - no caller stores X in fp64
+struct XF64 {
+    using T = double;
+    static constexpr const char *name = "f64";
+    static __device__ __forceinline__ double ld1(const double *p) { return *p; }
+};
+
 // register image of four elements: the raw vector load, or (V = false: the non-vectorised paths, element by element
 // through ld1) four fp32 values
 template <class XL, bool V>

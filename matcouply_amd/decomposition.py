@@ -1938,13 +1938,15 @@ def _zero_weight_mask(row_ptr, K, rank, kinds, w):
     return np.concatenate(parts)
 
 
-def _multistart_fused(matrices, rank, random_states, kws, per_job_options=False, slab_weights=None):
+def _multistart_fused(matrices, rank, random_states, kws, per_job_options=False, slab_weights=None, missing=None):
     """every keyword set of `kws` (complete cmf_aoadmm keywords with one state layout) from every start, in one launch: job
     g * len(random_states) + s is kws[g] from random_states[s].  One set with per_job_options False is cmf_aoadmm_multistart
     (mcl_multistart_run, the options in the kernel's arguments); cmf_aoadmm_grid gives every job options of its own
     (mcl_multistart_run_grid).  `kws` and `random_states` are not empty.  `slab_weights` [len(random_states), I] (one keyword
     set): cmf_aoadmm_resample, job s fits under slab_weights[s] (mcl_multistart_run_weighted); the start is the full problem's
-    draw with the part of every zero-weight matrix set to zero afterwards."""
+    draw with the part of every zero-weight matrix set to zero afterwards.  `missing` = (observed, fill_values) (one keyword
+    set): cmf_aoadmm_missing (missing.py), job s fits the entries its mask marks (mcl_multistart_run_missing); host arrays, uint8
+    [n_masks, N, K] and float64 [n_masks, K] or None."""
     device = _device()
     X, row_ptr = _pack(matrices, device)
     I, N, K = len(row_ptr) - 1, int(row_ptr[-1]), int(X.shape[1])
@@ -1976,7 +1978,11 @@ def _multistart_fused(matrices, rank, random_states, kws, per_job_options=False,
         for v, w in zip(vectors, slab_weights):
             v[_zero_weight_mask(row_ptr, K, rank, kinds, w)] = 0.0
     state = torch.from_numpy(np.stack(vectors)).to(device)
-    if slab_weights is not None:
+    if missing is not None:
+        assert len(kws) == 1 and not per_job_options and slab_weights is None
+        observed, fill_values = (None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(device) for a in missing)
+        diag, n_iter, stop = _engine.multistart_run_missing(X, row_ptr, rank, job_options[0], observed, fill_values, state)
+    elif slab_weights is not None:
         diag, n_iter, stop = _engine.multistart_run_weighted(X, row_ptr, rank, job_options[0], slab_weights, state)
     elif per_job_options:
         diag, n_iter, stop = _engine.multistart_run_grid(X, row_ptr, rank, job_options, state)
