@@ -207,15 +207,30 @@ static __device__ void pf2_jacobi_slab(double *smd, const double *Ssrc, const fl
     if (lane == 0) acc_out[(long)slab * (n2 + 1) + n2] = rh;
 }
 
+// Is a Gram matrix on which Newton-Schulz converged too ill-conditioned for the Gram route?  zn = ||(G / tr)^-1/2||_F^2 =
+// sum_i tr / lambda_i bounds cond(G) from both sides, zn / r^2 <= cond(G) <= zn; the middle, zn / r, is held against the 1e10 of
+// the Jacobi route's test.  A slab flagged here goes to the QR route, which is exact at any conditioning; a well-conditioned
+// one (cond(Y Delta^T) <= 1e5 / sqrt(r) whatever its spectrum) never is.
+static __device__ __forceinline__ bool pf2_ill_conditioned(double zn, int r) { return zn >= 1e10 * r; }
+
 __global__ __launch_bounds__(64) void k_pf2_algebra(const double *__restrict__ S, const float *__restrict__ Delta,
                                                     const float *__restrict__ rho, int r, float *__restrict__ T,
                                                     double *__restrict__ acc_out, int *__restrict__ status, int use_status,
                                                     double *__restrict__ T64, const int *__restrict__ ext,
-                                                    const double *__restrict__ Delta64 = nullptr) {
+                                                    const double *__restrict__ Delta64 = nullptr,
+                                                    const float *__restrict__ xmin_est = nullptr) {
     extern __shared__ double smd[];
-    // use_status: entries <= 0 were done by the Newton-Schulz kernel (-iterations); this kernel leaves 2 (k_pf2_polar_qr
-    // takes the slab) or 0 in the entry of every slab it handles
-    if (use_status && status[blockIdx.x] <= 0) return;
+    // use_status: entries <= 0 were done by the Newton-Schulz kernel (-iterations); this kernel leaves 2 (k_pf2_polar_qr takes
+    // the slab) or 0 in the entry of every slab it handles.  xmin_est (rank 32): a slab on which Newton-Schulz converged although
+    // the estimate 1 / ||Z||_F it left says that the Gram matrix is too ill-conditioned for the Gram route is flagged as well
+    // (its factor stands until the QR kernel has redone it)
+    if (use_status && status[blockIdx.x] <= 0) {
+        if (xmin_est != nullptr && threadIdx.x == 0) {
+            const double est = (double)xmin_est[blockIdx.x];
+            if (est > 0.0 && pf2_ill_conditioned(1.0 / (est * est), r)) status[blockIdx.x] = 2;
+        }
+        return;
+    }
     const int slab = blockIdx.x;
     pf2_jacobi_slab(smd, S + (long)slab * r * r, Delta, (double)rho[slab], r, slab, threadIdx.x, T, acc_out, T64, status,
                     ext[slab + 1] - ext[slab] >= r, Delta64);
@@ -766,17 +781,29 @@ __global__ __launch_bounds__(64 * NsShape<NB>::SPW + ((TILES && NB == 1) ? 64 : 
 #ifdef MCL_NS_STAMPS
     if (lane == 0) stamps[(long)slab * 8 + 5] = it_used;
 #endif
-    if (lane == 0) status[slab] = -it_used;  // <= 0: converged (number of Newton-Schulz iterations, for diagnostics)
-    if (scaled) {  // 1 / ||Z||_F <= 1 / ||Z||_2 = sqrt(eig_min(G / tr)): the next call's starting estimate for this slab
-        double zn = 0.0;
+    // ||Z||_F^2 = sum_i tr / lambda_i(G): between cond(G) and r^2 cond(G)
+    double zn = 0.0;
 #pragma unroll
-        for (int a = 0; a < NB; ++a)
+    for (int a = 0; a < NB; ++a)
 #pragma unroll
-            for (int b = 0; b < NB; ++b)
+        for (int b = 0; b < NB; ++b)
 #pragma unroll
-                for (int v = 0; v < 4; ++v) zn += Z.t[a][b][v] * Z.t[a][b][v];
-        zn = wave_sum_d(zn);
-        if (lane == 0) xmin_est[slab] = (float)(1.0 / sqrt(zn));
+            for (int v = 0; v < 4; ++v) zn += Z.t[a][b][v] * Z.t[a][b][v];
+    zn = wave_sum_d(zn);
+    // 1 / ||Z||_F <= 1 / ||Z||_2 = sqrt(eig_min(G / tr)): the next call's starting estimate for this slab (read only by the scaled
+    // iteration) - and what pf2_ill_conditioned goes by
+    if (lane == 0) xmin_est[slab] = (float)(1.0 / sqrt(zn));
+    // The iteration also "converges" (by stagnation at its round-off floor) on a Gram matrix far too ill-conditioned for the Gram
+    // route: cond(Y Delta^T) = 1e6 and 1e7 in 28 - 33 steps, with eps cond^2 in W - Delta off by 7 - 30 times its fp32 bar
+    // (tests/test_gpu_pf2_polar.py) where the QR route that ranks > 32 take for the same slab meets it.  Such a slab is flagged
+    // (2) like the ones the Jacobi route flags: k_pf2_polar_qr redoes it where it is launched, and what the epilogue below
+    // writes stands where it is not.  Rank <= 16: here; rank 32 (any more code behind the iteration costs that kernel two more
+    // spilled registers): k_pf2_algebra, launched behind this kernel, flags it by the estimate above.
+    // status <= 0: converged (number of Newton-Schulz iterations, for diagnostics)
+    if constexpr (INK) {
+        if (lane == 0) status[slab] = pf2_ill_conditioned(zn, r) ? 2 : -it_used;
+    } else {
+        if (lane == 0) status[slab] = -it_used;
     }
     // S_i for the epilogue: from memory (this wave wrote it above when it summed the tiles; its LDS copy has been the scratch of
     // the transposes since)
@@ -890,6 +917,10 @@ bool mcl_stats_reduce_in_algebra(const mcl_context *c) {
 // without the attribute.
 static int pf2_jacobi_qr(mcl_context *c, int k, bool jacobi, int use_status, bool qr, const double *F64, const double *U64,
                          const double *D64) {
+    // behind the rank-32 Newton-Schulz kernel: its estimate of this call, by which k_pf2_algebra flags the slabs that converged
+    // on a Gram matrix too ill-conditioned - where the QR kernel's work does not count, as for rank <= 16 (mcl_launch_pf2_polar):
+    // the large problems of the fast kernels (config 5: most slabs of the early iterations) keep the Newton-Schulz factor
+    const float *xmin = (use_status && (c->I <= 64 || c->exact)) ? c->pf2_xmin : nullptr;
     const RegSet &rs = c->regs[1];
     const int r = c->r, n2 = r * r;
     if (jacobi) {
@@ -897,7 +928,7 @@ static int pf2_jacobi_qr(mcl_context *c, int k, bool jacobi, int use_status, boo
         if (sm > 65536)
             MCL_CHECK_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(k_pf2_algebra), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm));
         hipLaunchKernelGGL(k_pf2_algebra, dim3((unsigned)c->I), dim3(64), sm, c->stream, c->pf2_S, rs.aux2[k], c->rhoB, r, c->pf2_T,
-                           c->pf2_acc, c->pf2_status, use_status, c->pf2_T64, c->row_ptr_dev, D64);
+                           c->pf2_acc, c->pf2_status, use_status, c->pf2_T64, c->row_ptr_dev, D64, xmin);
     }
     if (qr) {
         const size_t smq = sizeof(double) * (size_t)(3 * n2 + 4 * 64 + 64);
