@@ -6,7 +6,7 @@ hand-written HIP kernels (libmatcouply_hip.so, C ABI in include/matcouply_hip.h)
 """
 __version__ = "0.1.0"
 
-from . import coupled_matrices, data, decomposition, evaluation, missing, penalties, projection, random, resampling, similarity  # noqa: F401,E402
+from . import coupled_matrices, data, decomposition, evaluation, missing, multistart, penalties, projection, random, resampling, similarity  # noqa: F401,E402
 from .decomposition import PackedMatrices, best_start, cmf_aoadmm_grid, parafac2_aoadmm_grid  # noqa: F401,E402
 from .similarity import factor_match_score, multistart_similarity, permute_cmf  # noqa: F401,E402
 from .evaluation import (ModelEvaluation, core_consistency, fit, multistart_evaluation, relative_sse,  # noqa: F401,E402

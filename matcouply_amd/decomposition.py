@@ -1796,22 +1796,9 @@ def parafac2_aoadmm(
         verbose=verbose, group=group, gather_A=gather_A, arithmetic=arithmetic)
 
 
-# ------------------------------------------------------------------------------------------------------------
-# many random starts of one problem (not in the reference: its examples hand-roll this loop)
-# ------------------------------------------------------------------------------------------------------------
-# fused starts are served up to this many elements of X (sum J_i * K): the largest shape of profiles/multistart_rate.txt, where
-# 16 fused starts take 0.42 x the time of 16 sequential calls.  method="auto" takes the fused kernel from the first start up to
-# _MULTISTART_AUTO_ANY_N elements (examples' size: 1 fused start 0.53 x one call) and from _MULTISTART_AUTO_MIN_N starts above
-# (one fused start is a whole fit on one CU: 1.9 x one call at 2^16 elements, 6.3 x at 2^18; the crossovers lie at 2 and 7 starts)
-_MULTISTART_MAX_ELEMENTS = 1 << 18
-_MULTISTART_AUTO_ANY_N = 1 << 13
-_MULTISTART_AUTO_MIN_N = 8
-_MULTISTART_KINDS = (_engine.PEN_NN, _engine.PEN_BOX, _engine.PEN_L1, _engine.PEN_L2BALL, _engine.PEN_PARAFAC2)
-
-
-def _cmf_kwargs(kwargs):
-    """the keyword arguments of a cmf_aoadmm call as a complete dict of its parameters (TypeError for unknown ones)"""
-    bound = inspect.signature(cmf_aoadmm).bind(None, 1, **kwargs)
+def _cmf_kwargs(kwargs, signature=None):
+    """a cmf_aoadmm call's keyword arguments (`signature`: another fit's) as a complete dict of its parameters (TypeError for unknown ones)"""
+    bound = (signature or inspect.signature(cmf_aoadmm)).bind(None, 1, **kwargs)
     bound.apply_defaults()
     kw = dict(bound.arguments)
     del kw["matrices"], kw["rank"]
@@ -1842,490 +1829,8 @@ def _constant_flags(constant_feasibility_penalty):
     return bool((c and not isinstance(c, str)) or c == "A"), bool((c and not isinstance(c, str)) or c == "B")
 
 
-def _multistart_unfused_reason(matrices, rank, kw):
-    """why the fused kernel cannot run these starts (a sentence), or None.  Looks at the arguments only: no device call."""
-    if _test_engine_factory() is not None:
-        return "a substitute compute engine is installed (the fused kernel runs on the HIP engine only)"
-    if not 1 <= rank <= _engine.MS_MAX_RANK:
-        return f"rank {rank} is above {_engine.MS_MAX_RANK}"
-    if kw["verbose"]:
-        return "verbose output is not produced by the fused kernel"
-    if kw["group"] is not None or kw["gather_A"]:
-        return "group= (sharded runs) is not served"
-    if kw["arithmetic"] != "auto":
-        return f"arithmetic={kw['arithmetic']!r} is not served (the fused kernel is fp64 throughout)"
-    if kw["_byproducts"] is not None:
-        return "_byproducts is not served"
-    if kw["tol"] and kw["absolute_tol"] is None:
-        return "tol with absolute_tol=None (the reference raises TypeError in its comparison)"
-    if kw["inner_n_iter_max"] is None or int(kw["inner_n_iter_max"]) != kw["inner_n_iter_max"] or kw["n_iter_max"] is None \
-            or int(kw["n_iter_max"]) != kw["n_iter_max"] or kw["n_iter_max"] > (1 << 30):
-        return "n_iter_max and inner_n_iter_max must be integers"
-    try:
-        rows = [int(matrices.row_ptr[i + 1] - matrices.row_ptr[i]) for i in range(len(matrices))] \
-            if isinstance(matrices, PackedMatrices) else [int(shape(m)[0]) for m in matrices]
-        K = int(shape(matrices[0])[1])
-    except Exception:
-        return "the matrices are not a list of 2-D arrays"
-    if sum(rows) * K > _MULTISTART_MAX_ELEMENTS:
-        return f"X has {sum(rows) * K} elements, above the fused bound of {_MULTISTART_MAX_ELEMENTS}"
-    try:
-        _, regs, _, _ = _start_penalties(kw, matrices, rank, np.random.RandomState(0))
-    except Exception as e:  # let the sequential path raise the reference's error
-        return f"the penalties could not be set up ({type(e).__name__})"
-    constant_A, _ = _constant_flags(kw["constant_feasibility_penalty"])
-    for mode in range(3):
-        if len(regs[mode]) > _engine.MCL_MAX_REGS:
-            return f"more than {_engine.MCL_MAX_REGS} penalties on mode {mode}"
-        for reg in regs[mode]:
-            desc = penalties.native_descriptor_of(reg)
-            if desc is None or desc[0] not in _MULTISTART_KINDS:
-                return f"{type(reg).__name__} on mode {mode} is not served (NonNegativity, Box, L1Penalty, L2Ball, Parafac2)"
-            if desc[0] == _engine.PEN_PARAFAC2 and (mode != 1 or min(rows) < rank):
-                return "Parafac2 is served on mode 1 with every J_i >= rank"
-            if desc[0] == _engine.PEN_L2BALL and mode == 0 and not constant_A:
-                return "an L2Ball on mode 0 needs constant_feasibility_penalty"
-    if min(rows) == 0:
-        # an empty X_i has B_i^T B_i = 0 and a_i = 0: its A row and B_i systems are l2 + rho n times the identity, where rho is
-        # the slab's own (zero) feasibility penalty unless it is held constant over the slabs.  Singular systems raise in the
-        # reference; the fused kernel would invert them
-        l2 = _listify(kw["l2_penalty"], "l2_penalty")
-        _, constant_B = _constant_flags(kw["constant_feasibility_penalty"])
-        for mode, constant in ((0, constant_A), (1, constant_B)):
-            if not ((l2[mode] or 0) > 0 or (constant and regs[mode])):
-                return (f"an empty matrix leaves its mode-{mode} system singular (needs l2_penalty on mode {mode}, or a "
-                        "penalty there with constant_feasibility_penalty)")
-    return None
-
-
-def _multistart_options(kw, descs):
-    """the mcl_multistart_options of one fit: `kw` the complete cmf_aoadmm keywords, `descs` the native descriptors per mode"""
-    o = _engine.MultistartOptions()
-    for mode in range(3):
-        o.n_regs[mode] = len(descs[mode])
-        for k, (kind, nonneg, p0, p1) in enumerate(descs[mode]):
-            o.regs[mode][k].kind, o.regs[mode][k].non_negativity = int(kind), int(bool(nonneg))
-            o.regs[mode][k].p0, o.regs[mode][k].p1 = float(p0), float(p1)
-    l2 = [0 if v is None else v for v in _listify(kw["l2_penalty"], "l2_penalty")]
-    for mode in range(3):
-        o.l2_penalty[mode] = float(l2[mode])
-    o.feasibility_penalty_scale = float(kw["feasibility_penalty_scale"])
-    o.inner_tol = float(kw["inner_tol"]) if kw["inner_tol"] and kw["inner_tol"] > 0 else 0.0
-    o.inner_n_iter_max = int(kw["inner_n_iter_max"])
-    o.tol, o.absolute_tol = float(kw["tol"] or 0), float(kw["absolute_tol"] or 0)
-    o.feasibility_tol = float(kw["feasibility_tol"] or 0)
-    o.constant_A, o.constant_B = _constant_flags(kw["constant_feasibility_penalty"])
-    o.update_A, o.update_B, o.update_C = bool(kw["update_A"]), bool(kw["update_B_is"]), bool(kw["update_C"])
-    o.evaluate_loss_always = bool(kw["return_errors"])
-    o.n_iter_max = max(int(kw["n_iter_max"]), 0)
-    return o
-
-
-def _zero_weight_mask(row_ptr, K, rank, kinds, w):
-    """which doubles of a job's state slice (the layout of mcl_multistart_run) belong to a matrix of weight 0: its row of A, its
-    B_i and its rows of every aux and dual of modes 0 and 1 (its P_i for PARAFAC2; Delta and mode 2 are the whole job's)"""
-    I, N = len(row_ptr) - 1, int(row_ptr[-1])
-    dead_A = np.repeat(np.asarray(w) == 0, rank)
-    dead_B = np.repeat(np.repeat(np.asarray(w) == 0, np.diff(row_ptr)), rank)
-    dead = {0: dead_A, 1: dead_B, 2: np.zeros(K * rank, dtype=bool)}
-    parts = [dead_A, dead_B, dead[2]]
-    for mode in range(3):
-        for kind in kinds[mode]:
-            parts.append(dead[mode])
-            if kind == _engine.PEN_PARAFAC2:
-                parts.append(np.zeros(rank * rank, dtype=bool))
-            parts.append(dead[mode])
-    return np.concatenate(parts)
-
-
-def _multistart_fused(matrices, rank, random_states, kws, per_job_options=False, slab_weights=None, missing=None):
-    """every keyword set of `kws` (complete cmf_aoadmm keywords with one state layout) from every start, in one launch: job
-    g * len(random_states) + s is kws[g] from random_states[s].  One set with per_job_options False is cmf_aoadmm_multistart
-    (mcl_multistart_run, the options in the kernel's arguments); cmf_aoadmm_grid gives every job options of its own
-    (mcl_multistart_run_grid).  `kws` and `random_states` are not empty.  `slab_weights` [len(random_states), I] (one keyword
-    set): cmf_aoadmm_resample, job s fits under slab_weights[s] (mcl_multistart_run_weighted); the start is the full problem's
-    draw with the part of every zero-weight matrix set to zero afterwards.  `missing` = (observed, fill_values) (one keyword
-    set): cmf_aoadmm_missing (missing.py), job s fits the entries its mask marks (mcl_multistart_run_missing); host arrays, uint8
-    [n_masks, N, K] and float64 [n_masks, K] or None."""
-    device = _device()
-    X, row_ptr = _pack(matrices, device)
-    I, N, K = len(row_ptr) - 1, int(row_ptr[-1]), int(X.shape[1])
-    f32 = lambda a: np.asarray(to_numpy(a), dtype=np.float32).astype(np.float64).ravel()  # cmf_aoadmm keeps its state in fp32
-    vectors, job_kw, job_options, kinds = [], [], [], None
-    for kw in kws:
-        for rs in random_states:
-            cmf, regs, auxes, duals = _start_penalties(kw, matrices, rank, check_random_state(rs))
-            _, (A0, B0_is, C0) = cmf
-            parts = [f32(A0), np.concatenate([f32(b) for b in B0_is]), f32(C0)]
-            for mode in range(3):
-                for aux, dual in zip(auxes[mode], duals[mode]):
-                    if isinstance(aux, tuple):  # PARAFAC2: (P_i list, Delta)
-                        parts += [np.concatenate([f32(p) for p in aux[0]]), f32(aux[1])]
-                    else:
-                        parts.append(np.concatenate([f32(a) for a in aux]) if mode == 1 else f32(aux))
-                    parts.append(np.concatenate([f32(d) for d in dual]) if mode == 1 else f32(dual))
-            vectors.append(np.concatenate(parts))
-            descs = [[penalties.native_descriptor_of(r) for r in regs[m]] for m in range(3)]
-            job_kw.append(kw)
-        job_options += [_multistart_options(kw, descs)] * len(random_states)
-        assert kinds in (None, [[d[0] for d in descs[m]] for m in range(3)]), "multistart: the jobs differ in their state layout"
-        kinds = [[d[0] for d in descs[m]] for m in range(3)]
-    L = _engine.multistart_state_len(I, N, K, rank, kinds)
-    assert all(v.size == L for v in vectors), "multistart: state layout mismatch"
-
-    if slab_weights is not None:
-        assert len(kws) == 1 and not per_job_options and len(slab_weights) == len(vectors)
-        for v, w in zip(vectors, slab_weights):
-            v[_zero_weight_mask(row_ptr, K, rank, kinds, w)] = 0.0
-    state = torch.from_numpy(np.stack(vectors)).to(device)
-    if missing is not None:
-        assert len(kws) == 1 and not per_job_options and slab_weights is None
-        observed, fill_values = (None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(device) for a in missing)
-        diag, n_iter, stop = _engine.multistart_run_missing(X, row_ptr, rank, job_options[0], observed, fill_values, state)
-    elif slab_weights is not None:
-        diag, n_iter, stop = _engine.multistart_run_weighted(X, row_ptr, rank, job_options[0], slab_weights, state)
-    elif per_job_options:
-        diag, n_iter, stop = _engine.multistart_run_grid(X, row_ptr, rank, job_options, state)
-    else:
-        assert len(kws) == 1
-        diag, n_iter, stop = _engine.multistart_run(X, row_ptr, rank, job_options[0], state)
-    diag, n_iter, stop = diag.cpu().numpy(), n_iter.cpu().numpy(), stop.cpu().numpy()
-
-    out = _Out(matrices)
-    rows = (I, N, K)
-    results = []
-    for s in range(len(vectors)):
-        st = state[s]
-        kw = job_kw[s]
-        tol, absolute_tol, feasibility_tol = kw["tol"], kw["absolute_tol"], kw["feasibility_tol"]
-        pos = 0
-
-        def nxt(n_rows, cols=rank):
-            nonlocal pos
-            t = st[pos: pos + n_rows * cols].view(n_rows, cols)
-            pos += n_rows * cols
-            return t
-
-        A, B, C = nxt(I), nxt(N), nxt(K)
-        result = [CoupledMatrixFactorization((None, (out(A), out.split(B, row_ptr), out(C))))]
-        admm = [[(kind, nxt(rows[mode]), nxt(rank) if kind == _engine.PEN_PARAFAC2 else None, nxt(rows[mode]))
-                 for kind in kinds[mode]] for mode in range(3)]  # (aux, the Delta of a PARAFAC2, dual: the order of the state)
-        if kw["return_admm_vars"]:
-            result.append(_admm_vars_out(out, row_ptr, admm))
-        if kw["return_errors"]:
-            n = int(n_iter[s])
-            d = diag[s, : n + 1]
-            flags = d[:, 2].astype(np.int64)
-            kept = [0] + [t for t in range(1, n + 1) if flags[t] & 2]
-            gaps = [tuple([np.float64(d[t, 4 + m * _engine.MCL_MAX_REGS + k]) for k in range(len(kinds[m]))] for m in range(3))
-                    for t in range(n + 1)]
-            code = int(stop[s])
-            satisfied = bool(code) if (tol or absolute_tol) else None
-            message = _StopRule.message_of(code)
-            feasible = _check_feasibility(gaps[-1], feasibility_tol) if feasibility_tol else None
-            result.append(DiagnosticMetrics(
-                rec_errors=[float(d[t, 0]) for t in kept], feasibility_gaps=gaps, regularized_loss=[float(d[t, 1]) for t in kept],
-                satisfied_stopping_condition=satisfied, satisfied_feasibility_condition=feasible, message=message, n_iter=n))
-        results.append(result[0] if len(result) == 1 else tuple(result))
-    return results
-
-
-def cmf_aoadmm_multistart(matrices, rank, random_states, *, method="auto", **cmf_aoadmm_kwargs):
-    """Fit the same problem from several random starts: element ``s`` of the list returned is what
-    ``cmf_aoadmm(matrices, rank, random_state=random_states[s], **cmf_aoadmm_kwargs)`` returns (same tuple structure, array
-    types and dtypes).  Start ``s`` draws its initial factors, auxiliary and dual variables with the initialisers of
-    ``cmf_aoadmm``, in its order.  The usual selection afterwards: the lowest ``regularized_loss[-1]`` among the starts with
-    ``satisfied_stopping_condition``.
-
-    ``method="sequential"`` calls ``cmf_aoadmm`` once per start (every option).  ``method="fused"`` fits all starts in one launch
-    of a HIP kernel, one workgroup per start, in fp64 (csrc/multistart.hip); it serves rank <= 16, the penalties NonNegativity,
-    Box, L1Penalty, L2Ball (mode 0: with ``constant_feasibility_penalty``) and Parafac2 on the B_i (every J_i >= rank), and X of
-    at most ``_MULTISTART_MAX_ELEMENTS`` elements; anything else raises ``NotImplementedError`` before the device is touched
-    (``verbose``, ``group=``, ``arithmetic`` other than ``"auto"``, Unimodality, TV, GeneralizedL2, UnitSimplex, user penalty
-    classes).  ``method="auto"`` takes the fused kernel when it serves the call, else the sequential loop.  Only
-    ``init="random"``: any other start would be the same N times (``ValueError``).
-    """
-    if method not in ("auto", "fused", "sequential"):
-        raise ValueError(f'method must be "auto", "fused" or "sequential", not {method!r}')
-    if "random_state" in cmf_aoadmm_kwargs:
-        raise TypeError("cmf_aoadmm_multistart takes random_states, not random_state")
-    init = cmf_aoadmm_kwargs.get("init", "random")
-    if not (isinstance(init, str) and init == "random"):
-        raise ValueError(f"cmf_aoadmm_multistart needs init=\"random\" (init={init!r} gives the same start every time)")
-    random_states = list(random_states)
-    kw = _cmf_kwargs(cmf_aoadmm_kwargs)
-    if method != "sequential":
-        reason = _multistart_unfused_reason(matrices, rank, kw)
-        if reason is None and method == "auto" and len(random_states) < _MULTISTART_AUTO_MIN_N:
-            n_el = sum(int(shape(matrices[i])[0]) for i in range(len(matrices))) * int(shape(matrices[0])[1])
-            if n_el > _MULTISTART_AUTO_ANY_N:
-                reason = f"{len(random_states)} starts of {n_el} elements run faster one by one"
-        if reason is None:
-            return _multistart_fused(matrices, rank, random_states, [kw]) if random_states else []
-        if method == "fused":
-            raise NotImplementedError(f"cmf_aoadmm_multistart(method=\"fused\"): {reason}")
-    return [cmf_aoadmm(matrices, rank, random_state=rs, **cmf_aoadmm_kwargs) for rs in random_states]
-
-
-def parafac2_aoadmm_multistart(matrices, rank, random_states, *, method="auto", **parafac2_aoadmm_kwargs):
-    """:func:`cmf_aoadmm_multistart` with the PARAFAC2 constraint on mode 1: element ``s`` is what
-    ``parafac2_aoadmm(matrices, rank, random_state=random_states[s], **parafac2_aoadmm_kwargs)`` returns."""
-    if "parafac2" in parafac2_aoadmm_kwargs:
-        raise TypeError("parafac2_aoadmm_multistart() got an unexpected keyword argument 'parafac2'")
-    kwargs = dict(parafac2_aoadmm_kwargs)
-    kwargs.setdefault("l2_penalty", 0)
-    return cmf_aoadmm_multistart(matrices, rank, random_states, method=method, parafac2=True, **kwargs)
-
-
-# ------------------------------------------------------------------------------------------------------------
-# a grid of penalty strengths x random starts (DESIGN.md section 11a): the loop users write around the multi-start one
-# ------------------------------------------------------------------------------------------------------------
-# keywords that decide the shape of the result or are not options of one fit: common to the whole grid only
-_GRID_COMMON_ONLY = ("return_errors", "return_admm_vars", "verbose", "group")
-# device memory a fused grid may ask for (state, scratch, diagnostics and options of all jobs).  A Cartesian product grows
-# quickly, and every job holds its slices for the whole launch although only a few hundred workgroups are resident at a time.
-# 8 GiB is 1 / 36 of the MI355X's 288 GB and leaves the rest to the process's other tensors; it holds ~50 000 jobs of the
-# examples' size with 1000 iterations of diagnostics (~165 kB each) and ~1300 of 64 x 64 x 64 at rank 16 with four penalties
-# per mode (~6.5 MB each).  A larger grid runs as several calls
-_GRID_MAX_BYTES = 1 << 33
-
-
-def _grid_keywords(name, param_grid, common):
-    """the grid's keyword sets: [(point, point merged into the common keywords as complete cmf_aoadmm keywords)], checked"""
-    def check(kwargs, where):
-        if "random_state" in kwargs:
-            raise TypeError(f"{name} takes random_states, not random_state{where}")
-        init = kwargs.get("init", "random")
-        if not (isinstance(init, str) and init == "random"):
-            raise ValueError(f"{name} needs init=\"random\" (init={init!r}{where} gives the same start every time)")
-
-    check(common, "")
-    points = []
-    for g, point in enumerate(param_grid):
-        if not isinstance(point, dict):
-            raise TypeError(f"{name}: param_grid[{g}] is a {type(point).__name__}, not a dict of cmf_aoadmm keywords")
-        check(point, f" in param_grid[{g}]")
-        for key in point:
-            if key in _GRID_COMMON_ONLY:
-                raise ValueError(f"{name}: {key!r} in param_grid[{g}] is not an option of one fit; pass it once for the whole grid")
-            if key in common:
-                raise TypeError(f"{name} got {key!r} both in param_grid[{g}] and as a common keyword")
-        points.append((point, _cmf_kwargs({**common, **point})))
-    return points
-
-
-def _multistart_layout(matrices, rank, kw):
-    """what the state layout and the phases of the fused kernel follow from, per mode: the (kind, non-negativity) of every
-    penalty in order and whether the mode is updated; plus the constant-feasibility-penalty flags"""
-    _, regs, _, _ = _start_penalties(kw, matrices, rank, np.random.RandomState(0))
-    names = {_engine.PEN_NN: "NonNegativity", _engine.PEN_BOX: "Box", _engine.PEN_L1: "L1Penalty", _engine.PEN_L2BALL: "L2Ball",
-             _engine.PEN_PARAFAC2: "Parafac2"}
-    modes = []
-    for mode, updated in enumerate((kw["update_A"], kw["update_B_is"], kw["update_C"])):
-        descs = [penalties.native_descriptor_of(reg) for reg in regs[mode]]
-        modes.append((tuple(names[d[0]] + ("(non_negativity)" if d[1] and d[0] != _engine.PEN_NN else "") for d in descs),
-                      "updated" if updated else "not updated"))
-    return modes, _constant_flags(kw["constant_feasibility_penalty"])
-
-
-def _grid_unfused_reason(matrices, rank, kws, n_starts):
-    """why the fused kernel cannot run this grid in one launch (a sentence), or None.  No device call."""
-    for g, kw in enumerate(kws):
-        reason = _multistart_unfused_reason(matrices, rank, kw)
-        if reason is not None:
-            return f"grid point {g}: {reason}"
-    first = _multistart_layout(matrices, rank, kws[0])
-    for g, kw in enumerate(kws[1:], 1):
-        modes, constant = _multistart_layout(matrices, rank, kw)
-        for mode in range(3):
-            if modes[mode] != first[0][mode]:
-                return (f"grid point {g} has the penalties {list(modes[mode][0])} ({modes[mode][1]}) on mode {mode}, grid point 0 "
-                        f"{list(first[0][mode][0])} ({first[0][mode][1]}): one launch holds one state layout (a strength of 0 or "
-                        "None drops its penalty)")
-        if constant != first[1]:
-            return f"grid point {g} differs from grid point 0 in constant_feasibility_penalty"
-    rows = [int(shape(matrices[i])[0]) for i in range(len(matrices))]
-    I, N, K = len(rows), sum(rows), int(shape(matrices[0])[1])
-    n_pen = [[2 * n + (rank if name == "Parafac2" else 0) for name in first[0][m][0]] for m, n in enumerate((I, N, K))]
-    state_len = (I + N + K + sum(sum(p) for p in n_pen)) * rank
-    diag_len = (max(max(int(kw["n_iter_max"]), 0) for kw in kws) + 1) * _engine.MS_DIAG
-    per_job = 8 * (state_len + _engine.multistart_scratch_len(I, N, K, rank) + diag_len) + _engine.MS_OPTIONS_BYTES
-    n_jobs = len(kws) * n_starts
-    if n_jobs * per_job > _GRID_MAX_BYTES or n_jobs >= 1 << 31:
-        return (f"{n_jobs} jobs of {per_job} bytes each (state, scratch, diagnostics) need more than the {_GRID_MAX_BYTES} bytes "
-                "a fused grid may take; split the grid")
-    return None
-
-
-def cmf_aoadmm_grid(matrices, rank, param_grid, random_states, *, method="auto", **cmf_aoadmm_kwargs):
-    """Fit the same data over a grid of option values, every grid point from several random starts: ``result[g][s]`` is what
-    ``cmf_aoadmm(matrices, rank, random_state=random_states[s], **cmf_aoadmm_kwargs, **param_grid[g])`` returns (same tuple
-    structure, array types and dtypes, as for a start of :func:`cmf_aoadmm_multistart`).  ``param_grid`` is a sequence of dicts
-    of ``cmf_aoadmm`` keywords, one per grid point (``itertools.product`` builds a Cartesian one); a keyword stands either in
-    the grid points or among the common ones (``TypeError`` for both), and ``return_errors``, ``return_admm_vars``,
-    ``verbose`` and ``group`` are common only (``ValueError``).  An empty grid gives ``[]``.  :func:`best_start` picks a grid
-    point's start by the examples' rule.  Random-state objects among ``random_states`` (rather than seeds) are drawn from
-    grid point by grid point, in the order of the sequential method.
-
-    ``method="sequential"`` calls ``cmf_aoadmm`` once per grid point and start (every option).  ``method="fused"`` fits all
-    ``len(param_grid) * len(random_states)`` jobs in one launch of the kernel of :func:`cmf_aoadmm_multistart`, one workgroup
-    per job with options of its own (mcl_multistart_run_grid).  It serves what ``cmf_aoadmm_multistart(method="fused")`` serves
-    for every grid point, and needs all grid points to parse to the same penalty classes, non-negativity flags and order on
-    every mode, the same ``update_*`` and the same ``constant_feasibility_penalty``: the jobs share one state layout.  The
-    strengths, bounds, ``l2_penalty``, ``feasibility_penalty_scale``, tolerances and iteration limits may differ.  A strength of
-    0 or ``None`` drops its penalty when the keywords are parsed, so ``l1_penalty=0`` beside ``0.1`` is two layouts.  A grid
-    whose jobs need more than ``_GRID_MAX_BYTES`` of device memory is not served either.  Each of these raises
-    ``NotImplementedError`` naming the grid point, before the device is touched.  ``method="auto"`` takes the fused kernel when
-    it serves the call and the jobs are many or small enough (the rule of ``cmf_aoadmm_multistart`` on the number of jobs),
-    else the sequential loop.  A job's result does not depend on the grid it is part of.
-    """
-    return _aoadmm_grid("cmf_aoadmm_grid", matrices, rank, param_grid, random_states, method, cmf_aoadmm_kwargs)
-
-
-def _aoadmm_grid(name, matrices, rank, param_grid, random_states, method, common):
-    if method not in ("auto", "fused", "sequential"):
-        raise ValueError(f'method must be "auto", "fused" or "sequential", not {method!r}')
-    points = _grid_keywords(name, list(param_grid), common)
-    random_states = list(random_states)
-    if not points:
-        return []
-    if not random_states:
-        return [[] for _ in points]
-    if method != "sequential":
-        kws = [kw for _, kw in points]
-        n_jobs = len(kws) * len(random_states)
-        reason = _grid_unfused_reason(matrices, rank, kws, len(random_states))
-        if reason is None and method == "auto" and n_jobs < _MULTISTART_AUTO_MIN_N:
-            n_el = sum(int(shape(matrices[i])[0]) for i in range(len(matrices))) * int(shape(matrices[0])[1])
-            if n_el > _MULTISTART_AUTO_ANY_N:
-                reason = f"{n_jobs} jobs of {n_el} elements run faster one by one"
-        if reason is None:
-            flat = _multistart_fused(matrices, rank, random_states, kws, per_job_options=True)
-            n = len(random_states)
-            return [flat[g * n: (g + 1) * n] for g in range(len(kws))]
-        if method == "fused":
-            raise NotImplementedError(f"{name}(method=\"fused\"): {reason}")
-    return [[cmf_aoadmm(matrices, rank, random_state=rs, **common, **point) for rs in random_states] for point, _ in points]
-
-
-def parafac2_aoadmm_grid(matrices, rank, param_grid, random_states, *, method="auto", **parafac2_aoadmm_kwargs):
-    """:func:`cmf_aoadmm_grid` with the PARAFAC2 constraint on mode 1: ``result[g][s]`` is what ``parafac2_aoadmm(matrices, rank,
-    random_state=random_states[s], **parafac2_aoadmm_kwargs, **param_grid[g])`` returns."""
-    param_grid = list(param_grid)
-    if "parafac2" in parafac2_aoadmm_kwargs or any(isinstance(p, dict) and "parafac2" in p for p in param_grid):
-        raise TypeError("parafac2_aoadmm_grid() got an unexpected keyword argument 'parafac2'")
-    common = dict(parafac2_aoadmm_kwargs, parafac2=True)
-    if not any(isinstance(p, dict) and "l2_penalty" in p for p in param_grid):
-        common.setdefault("l2_penalty", 0)  # the default of parafac2_aoadmm
-    else:
-        param_grid = [p if not isinstance(p, dict) or "l2_penalty" in p or "l2_penalty" in common else dict(p, l2_penalty=0)
-                      for p in param_grid]
-    return _aoadmm_grid("parafac2_aoadmm_grid", matrices, rank, param_grid, random_states, method, common)
-
-
-def best_start(results):
-    """The examples' selection among the starts of one grid point (or of :func:`cmf_aoadmm_multistart`), fitted with
-    ``return_errors=True``: the index of the lowest ``regularized_loss[-1]`` among the starts with
-    ``satisfied_stopping_condition`` (the first of equal ones), or ``None`` when no start satisfied it."""
-    best, best_loss = None, None
-    for s, result in enumerate(results):
-        diag = next((x for x in result if isinstance(x, DiagnosticMetrics)), None) if isinstance(result, tuple) else None
-        if diag is None:
-            raise ValueError("best_start needs results fitted with return_errors=True")
-        if diag.satisfied_stopping_condition and (best is None or diag.regularized_loss[-1] < best_loss):
-            best, best_loss = s, diag.regularized_loss[-1]
-    return best
-
-
-# ------------------------------------------------------------------------------------------------------------
-# many random starts of parafac2_als (csrc/pf2als_multistart.hip, DESIGN.md section 13)
-# ------------------------------------------------------------------------------------------------------------
-# method="auto" takes the fused kernel from the first start while elements of X x rank <= _PF2ALS_MS_AUTO_ANY_WORK, and from
-# _PF2ALS_MS_AUTO_MIN_N starts above (profiles/pf2als_multistart_rate.txt: one fused start is 0.91 x one call at the
-# semiconductor size, 2.5e5 elements x rank 2, and 5.1 x at 64 x 64 x 64 rank 8, where the crossover lies at about 5 starts)
-_PF2ALS_MS_AUTO_ANY_WORK = 1 << 19
-_PF2ALS_MS_AUTO_MIN_N = 8
-
-
-def _pf2als_kwargs(kwargs):
-    """the keyword arguments of a parafac2_als call as a complete dict of its parameters; TensorLy options stay in "kwargs"
-    (checked by _parafac2_als_options)"""
-    bound = _PF2ALS_SIGNATURE.bind(None, 1, **kwargs)
-    bound.apply_defaults()
-    kw = dict(bound.arguments)
-    del kw["matrices"], kw["rank"]
-    return kw
-
-
-_PF2ALS_SIGNATURE = inspect.signature(parafac2_als)
-
-
-def _pf2als_unfused_reason(rank, rows, K):
-    """why the fused kernel cannot run these starts (a sentence), or None.  Looks at the arguments only: no device call."""
-    if _test_engine_factory() is not None:
-        return "a substitute compute engine is installed (the fused kernel runs on the HIP engine only)"
-    if rank > _engine.PF2ALS_MS_MAX_RANK:
-        return f"rank {rank} is above {_engine.PF2ALS_MS_MAX_RANK}"
-    if sum(rows) * K > _MULTISTART_MAX_ELEMENTS:
-        return f"X has {sum(rows) * K} elements, above the fused bound of {_MULTISTART_MAX_ELEMENTS}"
-    return None
-
-
-def _pf2als_fused(matrices, rank, random_states, modes, kw):
-    device = _device()
-    X, row_ptr = _pack(matrices, device)
-    I, N, K = len(row_ptr) - 1, int(row_ptr[-1]), int(X.shape[1])
-    starts = [_pf2als_random_start(I, K, rank, rs) for rs in random_states]
-    factors = torch.from_numpy(np.stack([np.concatenate([np.ravel(F) for F in st]) for st in starts])).to(device)
-    tol = float(kw["tol"]) if kw["tol"] else 0.0
-    absolute_tol = float(kw["absolute_tol"]) if kw["absolute_tol"] else 0.0
-    P, errors, n_iter = _engine.pf2als_multistart_run(X, row_ptr, rank, factors, int(kw["n_iter_max"]), int(kw["n_iter_parafac"]),
-                                                      tol, absolute_tol, modes)
-    errors, n_iter = errors.cpu().numpy(), n_iter.cpu().numpy()
-    out = _Out(matrices)
-    results = []
-    for s in range(len(starts)):
-        f = factors[s]
-        A, B, C = f[: I * rank].view(I, rank), f[I * rank: (I + rank) * rank].view(rank, rank), f[(I + rank) * rank:].view(K, rank)
-        result = (None, (out(A), out(B), out(C)), out.split(P[s], row_ptr))
-        if kw["return_errors"]:
-            result = (result, [float(e) for e in errors[s, : int(n_iter[s]) if tol > 0 else 0]])
-        results.append(result)
-    return results
-
-
-def parafac2_als_multistart(matrices, rank, random_states, *, method="auto", **parafac2_als_kwargs):
-    """Fit one unconstrained PARAFAC2-ALS problem from several random starts: element ``s`` of the list returned is what
-    ``parafac2_als(matrices, rank, random_state=random_states[s], **parafac2_als_kwargs)`` returns (same tuple structure, array
-    types and dtypes).  The usual selection afterwards: the start with the lowest final error (``return_errors=True``).
-
-    ``method="sequential"`` calls ``parafac2_als`` once per start.  ``method="fused"`` fits all starts in one launch of a HIP
-    kernel, one workgroup per start, in fp64 (csrc/pf2als_multistart.hip); it serves rank <= 16 and X of at most
-    ``_MULTISTART_MAX_ELEMENTS`` elements, anything else raises ``NotImplementedError`` before the device is touched.  Being fp64,
-    it resolves the default ``tol=1e-8`` where the sequential fit's fp32 X passes do not, so the two
-    methods can stop at different iterations.  ``method="auto"`` takes the fused kernel when it serves the call and is faster
-    (DESIGN.md section 13), else the sequential loop.  Only ``init="random"``: any other start would be the same N times
-    (``ValueError``).  ``parafac2_als``'s own refusals raise for every method.
-    """
-    if method not in ("auto", "fused", "sequential"):
-        raise ValueError(f'method must be "auto", "fused" or "sequential", not {method!r}')
-    if "random_state" in parafac2_als_kwargs:
-        raise TypeError("parafac2_als_multistart takes random_states, not random_state")
-    init = parafac2_als_kwargs.get("init", "random")
-    if not (isinstance(init, str) and init == "random"):
-        raise ValueError(f"parafac2_als_multistart needs init=\"random\" (init={init!r} gives the same start every time)")
-    random_states = list(random_states)
-    kw = _pf2als_kwargs(parafac2_als_kwargs)
-    rank = int(rank)
-    _, K, rows, modes = _parafac2_als_options(matrices, rank, kw["init"], kw["nn_modes"], kw["n_iter_max"], kw["n_iter_parafac"],
-                                              kw["kwargs"])
-    if method != "sequential":
-        reason = _pf2als_unfused_reason(rank, rows, K)
-        if reason is None and method == "auto" and len(random_states) < _PF2ALS_MS_AUTO_MIN_N \
-                and sum(rows) * K * rank > _PF2ALS_MS_AUTO_ANY_WORK:
-            reason = f"{len(random_states)} starts of {sum(rows) * K} elements at rank {rank} run faster one by one"
-        if reason is None:
-            return _pf2als_fused(matrices, rank, random_states, modes, kw) if random_states else []
-        if method == "fused":
-            raise NotImplementedError(f"parafac2_als_multistart(method=\"fused\"): {reason}")
-    return [parafac2_als(matrices, rank, random_state=rs, **parafac2_als_kwargs) for rs in random_states]
+def __getattr__(name):  # the re-export: what moved to multistart.py (which imports this module) stays readable here
+    from . import multistart
+    if name.startswith("__") or name not in vars(multistart):
+        raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+    return getattr(multistart, name)

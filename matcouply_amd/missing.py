@@ -7,13 +7,8 @@ iteration the model ``B_i D_i C^T`` of that iteration.  Each outer iteration is 
 reconstruction error and the loss are taken over the observed entries alone."""
 import numpy as np
 
-from . import decomposition as dec
-from ._utils import check_random_state, is_torch, shape, to_numpy
-
-try:
-    import torch
-except ImportError:  # pragma: no cover
-    torch = None
+from . import _engine, decomposition as dec, multistart as ms
+from ._utils import check_random_state, is_torch, shape, to_numpy, torch
 
 FILLS = ("column_mean", "zero", "model")
 
@@ -102,17 +97,13 @@ def cmf_aoadmm_missing(matrices, rank, observed, random_states, *, fill="column_
     not serve raises ``NotImplementedError`` with its sentence before the device is touched: there is no sequential method.
     Only ``init="random"``.  ``ValueError``, before the device is touched: a mask of the wrong shape, a job in which a matrix has
     no observed entry, a NaN at an observed entry.  16-bit matrices are read as stored; results come back in the input's dtype."""
-    if "random_state" in cmf_aoadmm_kwargs:
-        raise TypeError("cmf_aoadmm_missing takes random_states, not random_state")
-    init = cmf_aoadmm_kwargs.get("init", "random")
-    if not (isinstance(init, str) and init == "random"):
-        raise ValueError(f"cmf_aoadmm_missing needs init=\"random\" (init={init!r} gives the same start every time)")
+    ms._check_start_keywords("cmf_aoadmm_missing", cmf_aoadmm_kwargs)
     if fill not in FILLS:
         raise ValueError(f"fill must be one of {FILLS}, not {fill!r}")
     random_states = list(random_states)
     rank = int(rank)
     kw = dec._cmf_kwargs(cmf_aoadmm_kwargs)
-    reason = dec._multistart_unfused_reason(matrices, rank, kw)
+    reason = ms._multistart_unfused_reason(matrices, rank, kw)
     if reason is not None:
         raise NotImplementedError(f"cmf_aoadmm_missing: {reason}")
     masks, X, _ = observed_masks(matrices, observed, len(random_states))
@@ -122,16 +113,18 @@ def cmf_aoadmm_missing(matrices, rank, observed, random_states, *, fill="column_
         fill_values = column_means(X, masks)
     else:
         fill_values = np.zeros((len(masks), X.shape[1])) if fill == "zero" else None
-    return dec._multistart_fused(matrices, rank, random_states, [kw], missing=(masks.astype(np.uint8), fill_values))
+
+    def run(X, row_ptr, rank, options, state):  # the masks and fills follow the state to the device
+        observed, fills = (None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(state.device)
+                           for a in (masks.astype(np.uint8), fill_values))
+        return _engine.multistart_run_missing(X, row_ptr, rank, options[0], observed, fills, state)
+    return ms._multistart_fused(matrices, rank, random_states, [kw], run)
 
 
 def parafac2_aoadmm_missing(matrices, rank, observed, random_states, *, fill="column_mean", **parafac2_aoadmm_kwargs):
     """:func:`cmf_aoadmm_missing` with the PARAFAC2 constraint on mode 1 (``parafac2_aoadmm``'s defaults)."""
-    if "parafac2" in parafac2_aoadmm_kwargs:
-        raise TypeError("parafac2_aoadmm_missing() got an unexpected keyword argument 'parafac2'")
-    kwargs = dict(parafac2_aoadmm_kwargs)
-    kwargs.setdefault("l2_penalty", 0)
-    return cmf_aoadmm_missing(matrices, rank, observed, random_states, fill=fill, parafac2=True, **kwargs)
+    kwargs = ms._parafac2_keywords("parafac2_aoadmm_missing", parafac2_aoadmm_kwargs)
+    return cmf_aoadmm_missing(matrices, rank, observed, random_states, fill=fill, **kwargs)
 
 
 def _model_of(result):

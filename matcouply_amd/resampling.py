@@ -22,14 +22,8 @@ import warnings
 
 import numpy as np
 
-from . import _engine
-from . import decomposition as dec
-from ._utils import check_random_state, is_tensor, to_numpy
-
-try:
-    import torch
-except ImportError:  # pragma: no cover
-    torch = None
+from . import _engine, decomposition as dec, multistart as ms
+from ._utils import check_random_state, is_tensor, to_numpy, torch
 
 __all__ = ["resampling_weights", "parafac2_als_resample", "resample_summary", "resample_heldout_sse", "ResampleSummary",
            "FactorSummary", "HeldOut", "cmf_aoadmm_resample", "parafac2_aoadmm_resample", "cmf_resample_summary",
@@ -136,42 +130,12 @@ def _job_starts(starts, n_jobs, I, K, rank):
     return [dec._pf2als_random_start(I, K, rank, rs) for rs in states]
 
 
-def _tolerances(kw):
-    return (float(kw["tol"]) if kw["tol"] else 0.0), (float(kw["absolute_tol"]) if kw["absolute_tol"] else 0.0)
-
-
-def _fused(matrices, rank, weights, starts, modes, kw):
-    device = dec._device()
-    X, row_ptr = dec._pack(matrices, device)
-    I, K = len(row_ptr) - 1, int(X.shape[1])
-    scale = np.sqrt(weights)
-    factors = torch.from_numpy(np.stack([np.concatenate([np.ravel(A0 * scale[j][:, None]), np.ravel(B0), np.ravel(C0)])
-                                         for j, (A0, B0, C0) in enumerate(starts)])).to(device)
-    slab_scale = torch.from_numpy(np.ascontiguousarray(scale)).to(device)
-    tol, absolute_tol = _tolerances(kw)
-    P, errors, n_iter = _engine.pf2als_multistart_run_weighted(X, row_ptr, rank, factors, slab_scale, int(kw["n_iter_max"]),
-                                                               int(kw["n_iter_parafac"]), tol, absolute_tol, modes)
-    errors, n_iter = errors.cpu().numpy(), n_iter.cpu().numpy()
-    out = dec._Out(matrices)
-    results = []
-    for j in range(len(starts)):
-        f = factors[j]
-        A, B, C = f[: I * rank].view(I, rank), f[I * rank: (I + rank) * rank].view(rank, rank), f[(I + rank) * rank:].view(K, rank)
-        s = slab_scale[j][:, None]
-        A = torch.where(s > 0, A / torch.where(s > 0, s, torch.ones_like(s)), torch.zeros_like(A))
-        result = (None, (out(A), out(B), out(C)), out.split(P[j], row_ptr))
-        if kw["return_errors"]:
-            result = (result, [float(e) for e in errors[j, : int(n_iter[j]) if tol > 0 else 0]])
-        results.append(result)
-    return results
-
-
 def _sequential(matrices, rank, weights, starts, modes, kw):
     device = dec._device()
     X, row_ptr = dec._pack(matrices, device)
     I, N = len(row_ptr) - 1, int(row_ptr[-1])
     rows = np.diff(row_ptr)
-    tol, absolute_tol = _tolerances(kw)
+    tol, absolute_tol = ms._pf2als_tolerances(kw)
     out = dec._Out(matrices)
     results = []
     for w, (A0, B0, C0) in zip(weights, starts):
@@ -213,26 +177,18 @@ def parafac2_als_resample(matrices, rank, slab_weights, *, starts, method="auto"
     ``sqrt(w_i)`` and fits them with the ``parafac2_als`` kernels (rank <= 32).  ``method="auto"`` follows
     ``parafac2_als_multistart``.  Weights that are not finite, negative or not [n_jobs, I], a job without a positive weight and
     ``parafac2_als``'s own refusals raise before the device is touched."""
-    if method not in ("auto", "fused", "sequential"):
-        raise ValueError(f'method must be "auto", "fused" or "sequential", not {method!r}')
+    ms._check_method(method)
     for key in ("random_state", "init"):
         if key in parafac2_als_kwargs:
             raise TypeError(f"parafac2_als_resample takes starts, not {key}")
-    kw = dec._pf2als_kwargs(parafac2_als_kwargs)
+    kw = ms._pf2als_kwargs(parafac2_als_kwargs)
     rank = int(rank)
     I, K, rows, modes = dec._parafac2_als_options(matrices, rank, "random", kw["nn_modes"], kw["n_iter_max"], kw["n_iter_parafac"],
                                                   kw["kwargs"])
     weights = _check_weights(slab_weights, I)
     job_starts = _job_starts(starts, len(weights), I, K, rank)
-    if method != "sequential":
-        reason = dec._pf2als_unfused_reason(rank, rows, K)
-        if reason is None and method == "auto" and len(weights) < dec._PF2ALS_MS_AUTO_MIN_N \
-                and sum(rows) * K * rank > dec._PF2ALS_MS_AUTO_ANY_WORK:
-            reason = f"{len(weights)} jobs of {sum(rows) * K} elements at rank {rank} run faster one by one"
-        if reason is None:
-            return _fused(matrices, rank, weights, job_starts, modes, kw)
-        if method == "fused":
-            raise NotImplementedError(f"parafac2_als_resample(method=\"fused\"): {reason}")
+    if ms._pf2als_fused_serves("parafac2_als_resample", method, rank, rows, K, len(weights), "jobs"):
+        return ms._pf2als_fused(matrices, rank, job_starts, modes, kw, scale=np.sqrt(weights))
     return _sequential(matrices, rank, weights, job_starts, modes, kw)
 
 
@@ -439,10 +395,8 @@ def cmf_aoadmm_resample(matrices, rank, slab_weights, random_states, *, method="
     list, which is not the fused job's start: the two agree in what they converge to, not iterate by iterate.
     ``method="auto"`` follows the rule of ``cmf_aoadmm_multistart``.  Weights that are not finite, negative or not [n_jobs, I]
     and a job without a positive weight raise ``ValueError`` before the device is touched."""
-    if method not in ("auto", "fused", "sequential"):
-        raise ValueError(f'method must be "auto", "fused" or "sequential", not {method!r}')
-    if "random_state" in cmf_aoadmm_kwargs:
-        raise TypeError("cmf_aoadmm_resample takes random_states, not random_state")
+    ms._check_method(method)
+    ms._check_start_keywords("cmf_aoadmm_resample", cmf_aoadmm_kwargs, check_init=False)  # init: "random" or a model, below
     kwargs = dict(cmf_aoadmm_kwargs)
     init = kwargs.get("init", "random")
     if isinstance(init, str):
@@ -464,16 +418,10 @@ def cmf_aoadmm_resample(matrices, rank, slab_weights, random_states, *, method="
     random_states = list(random_states)
     if len(random_states) != len(weights):
         raise ValueError(f"random_states holds {len(random_states)} states for {len(weights)} jobs (one per row of slab_weights)")
-    if method != "sequential":
-        reason = dec._multistart_unfused_reason(matrices, rank, kw)
-        if reason is None and method == "auto" and len(weights) < dec._MULTISTART_AUTO_MIN_N:
-            n_el = sum(int(dec.shape(matrices[i])[0]) for i in range(I)) * int(dec.shape(matrices[0])[1])
-            if n_el > dec._MULTISTART_AUTO_ANY_N:
-                reason = f"{len(weights)} jobs of {n_el} elements run faster one by one"
-        if reason is None:
-            return dec._multistart_fused(matrices, rank, random_states, [kw], slab_weights=weights)
-        if method == "fused":
-            raise NotImplementedError(f"cmf_aoadmm_resample(method=\"fused\"): {reason}")
+    if ms._fused_serves("cmf_aoadmm_resample", method, lambda: ms._multistart_unfused_reason(matrices, rank, kw), len(weights),
+                        lambda n: ms._few_aoadmm_jobs(matrices, n, "jobs")):
+        run = lambda X, row_ptr, r, options, state: _engine.multistart_run_weighted(X, row_ptr, r, options[0], weights, state)
+        return ms._multistart_fused(matrices, rank, random_states, [kw], run, zero_weights=weights)
     if isinstance(matrices, dec.PackedMatrices):
         matrices = [matrices[i] for i in range(I)]
     _, regs, _, _ = dec._start_penalties(kw, matrices, rank, np.random.RandomState(0))
@@ -483,11 +431,8 @@ def cmf_aoadmm_resample(matrices, rank, slab_weights, random_states, *, method="
 
 def parafac2_aoadmm_resample(matrices, rank, slab_weights, random_states, *, method="auto", **parafac2_aoadmm_kwargs):
     """:func:`cmf_aoadmm_resample` with the PARAFAC2 constraint on mode 1 (``parafac2_aoadmm``'s defaults)."""
-    if "parafac2" in parafac2_aoadmm_kwargs:
-        raise TypeError("parafac2_aoadmm_resample() got an unexpected keyword argument 'parafac2'")
-    kwargs = dict(parafac2_aoadmm_kwargs)
-    kwargs.setdefault("l2_penalty", 0)
-    return cmf_aoadmm_resample(matrices, rank, slab_weights, random_states, method=method, parafac2=True, **kwargs)
+    kwargs = ms._parafac2_keywords("parafac2_aoadmm_resample", parafac2_aoadmm_kwargs)
+    return cmf_aoadmm_resample(matrices, rank, slab_weights, random_states, method=method, **kwargs)
 
 
 def cmf_resample_summary(replicates, reference, slab_weights, quantiles=(0.025, 0.975)):

@@ -11,6 +11,7 @@ import pytest
 import matcouply_amd
 from matcouply_amd import _engine
 from matcouply_amd import decomposition as dec
+from matcouply_amd import multistart as ms
 from matcouply_amd import resampling as rs
 from oracle import aoadmm_oracle as orc
 from tests import weighted_aoadmm_restatement as W
@@ -177,7 +178,7 @@ def test_fused_serves_what_the_multistart_kernel_serves(problem, no_device, kw, 
     mats = problem[0]
     kw = dict(kw)
     rank = kw.pop("_rank", 3)
-    assert reason in dec._multistart_unfused_reason(mats, rank, dec._cmf_kwargs(kw))
+    assert reason in ms._multistart_unfused_reason(mats, rank, dec._cmf_kwargs(kw))
     with pytest.raises(NotImplementedError, match=r'cmf_aoadmm_resample\(method="fused"\)'):
         rs.cmf_aoadmm_resample(mats, rank, np.ones((2, 6)), [0, 1], method="fused", **kw)
 
@@ -253,7 +254,7 @@ def test_sequential_refuses_where_the_scaling_identity_fails(problem, recorded, 
 def test_auto_follows_the_multistart_rule(problem, monkeypatch):
     mats = problem[0]
     seen = []
-    monkeypatch.setattr(dec, "_multistart_fused", lambda *a, **k: seen.append(("fused", k["slab_weights"].shape)) or [])
+    monkeypatch.setattr(ms, "_multistart_fused", lambda *a, **k: seen.append(("fused", k["zero_weights"].shape)) or [])
     one = lambda m, r, **k: seen.append("call") or dec.CoupledMatrixFactorization(
         (None, (np.ones((len(m), r)), [np.ones((x.shape[0], r)) for x in m], np.ones((9, r)))))
     one.__signature__ = inspect.signature(dec.cmf_aoadmm)
@@ -270,7 +271,7 @@ def test_zero_weight_mask_follows_the_state_layout():
     row_ptr = np.array([0, 2, 5, 6])
     K, r = 4, 2
     kinds = [[_engine.PEN_NN], [_engine.PEN_PARAFAC2, _engine.PEN_NN], [_engine.PEN_L1]]
-    mask = dec._zero_weight_mask(row_ptr, K, r, kinds, np.array([1.0, 0.0, 2.0]))
+    mask = ms._StateLayout(row_ptr, K, r, kinds).zero_weight_mask(np.array([1.0, 0.0, 2.0]))
     assert mask.size == _engine.multistart_state_len(3, 6, K, r, kinds)
     A = [False] * 2 + [True] * 2 + [False] * 2
     B = [False] * 4 + [True] * 6 + [False] * 2

@@ -8,6 +8,7 @@ import pytest
 torch = pytest.importorskip("torch")
 
 from matcouply_amd import decomposition as dec  # noqa: E402
+from matcouply_amd import multistart as ms  # noqa: E402
 from matcouply_amd import penalties as pen  # noqa: E402
 from matcouply_amd._utils import check_random_state  # noqa: E402
 from oracle import aoadmm_oracle as orc  # noqa: E402
@@ -307,7 +308,7 @@ def test_oracle_parity_batches_and_strides(case, stack):
 
 def test_oracle_parity_near_the_size_bound():
     c = E.MS_CASES["near_bound_r16"]
-    assert sum(c["J_range"]) / 2 * c["I"] * c["K"] > 0.9 * dec._MULTISTART_MAX_ELEMENTS
+    assert sum(c["J_range"]) / 2 * c["I"] * c["K"] > 0.9 * ms._MULTISTART_MAX_ELEMENTS
     _per_start_parity("near_bound_r16", "ridge_constant", 2, n_iter=5)
 
 

@@ -10,6 +10,7 @@ torch = pytest.importorskip("torch")
 
 from matcouply_amd import _engine  # noqa: E402
 from matcouply_amd import decomposition as dec  # noqa: E402
+from matcouply_amd import multistart as ms  # noqa: E402
 from tests import parafac2_als_restatement as R  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -71,7 +72,7 @@ BARS = {3: (FAC_BAR, ERR_BAR), 50: (FAC_BAR, ERR_BAR)}
 def test_parity_per_start(size, nn_modes, n_iter):
     p = SIZES[size]
     mats = _problem(p)
-    assert sum(m.size for m in mats) <= dec._MULTISTART_MAX_ELEMENTS
+    assert sum(m.size for m in mats) <= ms._MULTISTART_MAX_ELEMENTS
     starts = [0, 1, 2, 3]
     got = _fused(_packed(mats), p["rank"], starts, n_iter_max=n_iter, tol=1e-300, absolute_tol=0, nn_modes=nn_modes)
     fac, err = BARS[n_iter]
@@ -218,7 +219,7 @@ def semiconductor_problem():
     """the size of the reference's semiconductor example: 108 matrices of 100-120 x 21, rank 2; this seed's draw of J_i keeps
     X under the fused bound of 2^18 elements"""
     mats = R.parafac2_problem(108, (100, 120), 21, 2, seed=3, noise=NOISE)[0]
-    assert sum(m.size for m in mats) <= dec._MULTISTART_MAX_ELEMENTS
+    assert sum(m.size for m in mats) <= ms._MULTISTART_MAX_ELEMENTS
     return mats
 
 

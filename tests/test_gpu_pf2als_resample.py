@@ -13,6 +13,7 @@ torch = pytest.importorskip("torch")
 
 from matcouply_amd import _engine  # noqa: E402
 from matcouply_amd import decomposition as dec  # noqa: E402
+from matcouply_amd import multistart as ms  # noqa: E402
 from matcouply_amd import resampling as rs  # noqa: E402
 from matcouply_amd.projection import parafac2_project  # noqa: E402
 from tests import parafac2_als_restatement as R  # noqa: E402
@@ -400,7 +401,7 @@ def test_no_scratch_in_the_weighted_kernel():
 def semiconductor_problem():
     """the size of the reference's semiconductor example (tests/test_gpu_pf2als_multistart.semiconductor_problem)"""
     mats = R.parafac2_problem(108, (100, 120), 21, 2, seed=3, noise=NOISE)[0]
-    assert sum(m.size for m in mats) <= dec._MULTISTART_MAX_ELEMENTS
+    assert sum(m.size for m in mats) <= ms._MULTISTART_MAX_ELEMENTS
     return mats
 
 

@@ -4,8 +4,9 @@ before the device is touched, the folds of entry_kfold, impute and heldout_entry
 the C entry mcl_multistart_run_missing in the manner of tests/test_entry_refusals_host.py."""
 import numpy as np
 import pytest
+import torch
 
-from matcouply_amd import _engine, decomposition as dec, missing
+from matcouply_amd import _engine, decomposition as dec, missing, multistart as ms
 from matcouply_amd.coupled_matrices import CoupledMatrixFactorization
 from oracle import aoadmm_oracle as orc
 from tests import missing_aoadmm_restatement as mr
@@ -154,7 +155,7 @@ def no_device(monkeypatch):
         raise AssertionError("the device was touched")
 
     monkeypatch.setattr(dec, "_device", refuse)
-    monkeypatch.setattr(dec, "_multistart_fused", refuse)
+    monkeypatch.setattr(ms, "_multistart_fused", refuse)
     monkeypatch.setattr(_engine, "multistart_run_missing", refuse)
 
 
@@ -205,7 +206,7 @@ def test_what_the_fused_kernel_does_not_serve_is_not_implemented(no_device, kwar
     with pytest.raises(NotImplementedError) as e:
         missing.cmf_aoadmm_missing(mats, rank, random_mask(shapes, 0.1, seed=0), range(2), **kwargs)
     assert str(e.value).startswith("cmf_aoadmm_missing: ") and sentence in str(e.value)
-    assert str(e.value) == "cmf_aoadmm_missing: " + dec._multistart_unfused_reason(mats, rank, dec._cmf_kwargs(kwargs))
+    assert str(e.value) == "cmf_aoadmm_missing: " + ms._multistart_unfused_reason(mats, rank, dec._cmf_kwargs(kwargs))
 
 
 def test_too_many_elements_is_not_implemented(no_device):
@@ -218,11 +219,17 @@ def test_the_launch_gets_masks_fills_and_keywords(monkeypatch):
     mats, shapes = _small()
     seen = {}
 
-    def fused(matrices, rank, random_states, kws, **kw):
-        seen.update(kw, rank=rank, states=list(random_states), kws=kws)
+    def fused(matrices, rank, random_states, kws, run):
+        seen.update(rank=rank, states=list(random_states), kws=kws)
+        run("X", "row_ptr", rank, ["the options of job 0"], torch.zeros(1))  # the launch the caller names, here on the host
         return ["result"] * len(random_states)
 
-    monkeypatch.setattr(dec, "_multistart_fused", fused)
+    def run_missing(X, row_ptr, rank, options, observed, fill_values, state):
+        assert (X, row_ptr, options) == ("X", "row_ptr", "the options of job 0")
+        seen["missing"] = (observed.numpy(), None if fill_values is None else fill_values.numpy())
+
+    monkeypatch.setattr(ms, "_multistart_fused", fused)
+    monkeypatch.setattr(_engine, "multistart_run_missing", run_missing)
     per_job = [random_mask(shapes, 0.3, seed=s) for s in range(2)]
     assert missing.cmf_aoadmm_missing(mats, 2, per_job, [5, 6], non_negative=True) == ["result"] * 2
     observed, fill = seen["missing"]

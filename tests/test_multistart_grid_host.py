@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import matcouply_amd
-from matcouply_amd import _engine, decomposition as dec
+from matcouply_amd import _engine, decomposition as dec, multistart as ms
 from matcouply_amd import penalties as pen
 from matcouply_amd.coupled_matrices import CoupledMatrixFactorization
 from tests.oracle_engine import OracleEngineFactory
@@ -177,23 +177,23 @@ def test_one_layout_is_not_refused_for_its_strengths(no_device):
            for lo, l1, l2, sc, tol, n, inner, itol, ftol, atol in [(-0.5, 0.1, None, 1, 1e-8, 10, 5, None, 1e-4, 1e-10),
                                                                     (0.0, 0.3, [0.1, 0.2, 0.3], 0.5, None, 50, 3, 1e-3, 1e-2, 1e-6),
                                                                     (-2.0, 1e-3, 0.7, 2, 1e-4, 0, 7, None, None, 1e-12)]]
-    assert dec._grid_unfused_reason(mats, 2, kws, 4) is None
+    assert ms._grid_unfused_reason(mats, 2, kws, 4) is None
 
 
 def test_fused_refuses_a_grid_beyond_the_memory_bound(no_fits, monkeypatch):
     mats = _mats()
     grid = [dict(l1_penalty=v) for v in (0.1, 0.2, 0.3)]
     kws = [dec._cmf_kwargs(dict(p, n_iter_max=9)) for p in grid]
-    assert dec._grid_unfused_reason(mats, 2, kws, 2) is None
+    assert ms._grid_unfused_reason(mats, 2, kws, 2) is None
     # one job: state 2 * (3 + 22 + 8) doubles of factors + 2 x that of aux and dual, scratch, 10 rows of diagnostics, options
     I, N, K, r = 3, 22, 8, 2
     per_job = 8 * (3 * (I + N + K) * r + _engine.multistart_scratch_len(I, N, K, r) + 10 * _engine.MS_DIAG) + _engine.MS_OPTIONS_BYTES
-    monkeypatch.setattr(dec, "_GRID_MAX_BYTES", 6 * per_job)
-    assert dec._grid_unfused_reason(mats, 2, kws, 2) is None
-    monkeypatch.setattr(dec, "_GRID_MAX_BYTES", 6 * per_job - 1)
+    monkeypatch.setattr(ms, "_GRID_MAX_BYTES", 6 * per_job)
+    assert ms._grid_unfused_reason(mats, 2, kws, 2) is None
+    monkeypatch.setattr(ms, "_GRID_MAX_BYTES", 6 * per_job - 1)
     with pytest.raises(NotImplementedError, match="6 jobs of"):
         dec.cmf_aoadmm_grid(mats, 2, grid, range(2), method="fused", n_iter_max=9)
-    assert dec._GRID_MAX_BYTES <= 1 << 33
+    assert ms._GRID_MAX_BYTES <= 1 << 33
 
 
 def test_scratch_len_restates_the_kernel_s_plan():
@@ -208,10 +208,10 @@ def test_scratch_len_restates_the_kernel_s_plan():
 def test_auto_counts_jobs_not_starts(no_device, monkeypatch):
     # above _MULTISTART_AUTO_ANY_N elements auto wants _MULTISTART_AUTO_MIN_N fits in the launch: 4 points x 2 starts are 8
     mats = _mats(((100, 100),))
-    assert 100 * 100 > dec._MULTISTART_AUTO_ANY_N and dec._MULTISTART_AUTO_MIN_N == 8
+    assert 100 * 100 > ms._MULTISTART_AUTO_ANY_N and ms._MULTISTART_AUTO_MIN_N == 8
     calls = []
-    monkeypatch.setattr(dec, "_multistart_fused", lambda m, r, rs, kws, per_job_options=False: calls.append(
-        (len(kws), len(rs), per_job_options)) or [("job", g, s) for g in range(len(kws)) for s in range(len(rs))])
+    monkeypatch.setattr(ms, "_multistart_fused", lambda m, r, rs, kws, run: calls.append(  # the launch: options per job
+        (len(kws), len(rs), run is _engine.multistart_run_grid)) or [("job", g, s) for g in range(len(kws)) for s in range(len(rs))])
     monkeypatch.setattr(dec, "cmf_aoadmm", functools.wraps(dec.cmf_aoadmm)(
         lambda m, r, random_state, **kw: ("call", kw["l1_penalty"], random_state)))
     grid = [dict(l1_penalty=v) for v in (0.1, 0.2, 0.3, 0.4)]
@@ -275,7 +275,7 @@ def _c_options(n):
 
     kw = dec._cmf_kwargs(dict(n_iter_max=3))
     nn, l1 = (_engine.PEN_NN, False, 0.0, 0.0), (_engine.PEN_L1, False, 0.1, 0.0)
-    array = (_engine.MultistartOptions * n)(*[dec._multistart_options(kw, [[nn], [], [l1]]) for _ in range(n)])
+    array = (_engine.MultistartOptions * n)(*[ms._multistart_options(kw, [[nn], [], [l1]]) for _ in range(n)])
     row_ptr = np.array([0, 5, 9], dtype=np.int64)
     return ctypes, array, row_ptr, row_ptr.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
 

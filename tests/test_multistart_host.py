@@ -3,7 +3,7 @@ single call per start, and the fused method refuses what its kernel does not ser
 import numpy as np
 import pytest
 
-from matcouply_amd import _engine, decomposition as dec
+from matcouply_amd import _engine, decomposition as dec, multistart as ms
 from matcouply_amd import penalties as pen
 from matcouply_amd.coupled_matrices import CoupledMatrixFactorization
 from tests.oracle_engine import OracleEngineFactory
@@ -132,9 +132,9 @@ def test_edge_fixture_is_served_fused(no_device, name):
 
     c = E.MS_CASES[name]
     mats, X, row_ptr = E.ms_problem(c["I"], c["J_range"], c["K"], c["r"], c["seed"])
-    assert X.size <= dec._MULTISTART_MAX_ELEMENTS
+    assert X.size <= ms._MULTISTART_MAX_ELEMENTS
     for stack in E.MS_RUNS[name]:
-        reason = dec._multistart_unfused_reason(mats, c["r"], dec._cmf_kwargs(dict(STACKS[stack], n_iter_max=20, tol=None)))
+        reason = ms._multistart_unfused_reason(mats, c["r"], dec._cmf_kwargs(dict(STACKS[stack], n_iter_max=20, tol=None)))
         assert reason is None, (name, stack, reason)
 
 

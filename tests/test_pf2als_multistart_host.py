@@ -4,7 +4,7 @@ the library's."""
 import numpy as np
 import pytest
 
-from matcouply_amd import _engine, decomposition as dec
+from matcouply_amd import _engine, decomposition as dec, multistart as ms
 from tests.oracle_engine import OracleEngineFactory
 
 
@@ -158,8 +158,8 @@ def test_auto_takes_the_loop_for_few_starts_of_a_large_problem(no_device, monkey
     rec = _Recorder()
     monkeypatch.setattr(dec, "parafac2_als", rec)
     mats = _mats(((64, 64),) * 64)
-    assert len(dec.parafac2_als_multistart(mats, 8, range(dec._PF2ALS_MS_AUTO_MIN_N - 1))) == dec._PF2ALS_MS_AUTO_MIN_N - 1
+    assert len(dec.parafac2_als_multistart(mats, 8, range(ms._PF2ALS_MS_AUTO_MIN_N - 1))) == ms._PF2ALS_MS_AUTO_MIN_N - 1
     with pytest.raises(AssertionError, match="device was touched"):  # from _PF2ALS_MS_AUTO_MIN_N starts: the fused kernel
-        dec.parafac2_als_multistart(mats, 8, range(dec._PF2ALS_MS_AUTO_MIN_N))
+        dec.parafac2_als_multistart(mats, 8, range(ms._PF2ALS_MS_AUTO_MIN_N))
     with pytest.raises(AssertionError, match="device was touched"):  # semiconductor-sized work: fused from the first start
         dec.parafac2_als_multistart(_mats(((110, 21),) * 108), 2, [0])
